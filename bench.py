@@ -64,7 +64,12 @@ def parse_args():
     ap.add_argument("--extra-adna-reads", type=int, default=6_250_000, help="config 5's share of one GPU: 50 M reads over 8 GPUs")
     ap.add_argument("--extra-repeat-reads", type=int, default=10_000_000)
     ap.add_argument("--extra-cpu-seconds", type=float, default=8.0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the run's own workload computed in its last "
+                    "timed step (rank 0) as DIR/<name>.npy, float64, at most 64 MB in all: a fixed seeded sample of the reads (pairs) when the output is larger")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args):
@@ -289,6 +294,8 @@ def se_workload(ctx, G, kind, n_reads, steps, warmup, primary, cpu_seconds, want
             dms = [batches[(steps - 1) % 2].last_deep_ms()]
     barrier(ctx)
     elapsed = max_over_ranks(ctx, time.time() - t1)
+    if primary and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, se_outputs(*batches[(steps - 1) % len(batches)].fetch_flat()))
     checksum, n_rows = batch.checksum()
     # the rows of the TIMED run, for the comparison with the CPU (the untimed instrumented run below overwrites the batch's results;
     # until round 2 the comparison read those by mistake)
@@ -369,6 +376,81 @@ def se_workload(ctx, G, kind, n_reads, steps, warmup, primary, cpu_seconds, want
     for b in batches:
         b.close()
     return out
+
+
+DUMP_LIMIT = 64 << 20          # --dump-outputs: bytes of array data at most
+DUMP_READS = 1 << 17           # single-end reads sampled when there are more
+DUMP_PAIRS = 1 << 14           # pairs sampled when there are more (a record carries its CIGAR)
+
+
+def dump_sample(n, k, seed=20261015):
+    """a fixed, seeded, sorted sample of min(n, k) of 0..n-1: the same indices for the same arguments on every run and every build"""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def rows_of(n_aln, rows, idx):
+    """the hit rows of reads idx, back to back in that order, and the position in idx each row belongs to"""
+    bnd = np.concatenate([[0], np.cumsum(n_aln, dtype=np.int64)])
+    cnt = n_aln[idx].astype(np.int64)
+    at = np.repeat(bnd[idx] - (np.cumsum(cnt) - cnt), cnt) + np.arange(int(cnt.sum()), dtype=np.int64)
+    return rows[at], np.repeat(np.arange(len(idx), dtype=np.int64), cnt)
+
+
+def hit_arrays(n_aln, rows, idx, fixed_bytes):
+    """n_aln and the hit rows (bwt_aln1_t fields) of reads idx; if the rows would pass DUMP_LIMIT, the longest prefix of idx whose rows fit"""
+    cnt = n_aln[idx].astype(np.int64)
+    used = fixed_bytes + 8 * 2 * np.arange(1, len(idx) + 1) + 8 * 5 * np.cumsum(cnt)
+    idx = idx[:int(np.searchsorted(used, DUMP_LIMIT, side="right"))]
+    r, which = rows_of(n_aln, rows, idx)
+    return {"read": idx, "n_aln": n_aln[idx], "aln_read": which, "aln_info": r["info"], "aln_k": r["k"], "aln_l": r["l"], "aln_score": r["score"]}
+
+
+def se_outputs(n_aln, rows, maxe):
+    """what nabwa_batch_fetch hands a caller of the single-end search: per read n_aln and max_entries, and its hit rows"""
+    idx = dump_sample(len(n_aln), DUMP_READS)
+    out = hit_arrays(n_aln, rows, idx, 8 * len(idx))
+    out["max_entries"] = maxe[out["read"]]
+    return out
+
+
+def pe_outputs(nabwa, recs, ii, n_aln, rows):
+    """what the paired-end step hands its caller: the finished records of both ends (nabwa_pe_t fields, CIGAR included), the insert-size
+    estimate, and the hit rows of the search"""
+    n_ends = len(recs)
+    idx = dump_sample(n_ends // 2, DUMP_PAIRS)
+    ends = np.stack([2 * idx, 2 * idx + 1], 1).ravel()
+    raw = np.frombuffer(recs, np.uint8).reshape(n_ends, C.sizeof(nabwa.PeRec))[ends]
+    se = nabwa.PeRec.se.offset
+
+    def field(off, dt, count=1):
+        a = raw[:, off:off + np.dtype(dt).itemsize * count].copy().view(dt)
+        return a[:, 0] if count == 1 else a
+
+    out = {"end": ends}
+    for name, ty in nabwa.SeRec._fields_:
+        if name in ("type", "strand", "n_mm", "n_gapo", "n_gape", "score", "sa", "pos", "c1", "c2", "mapQ", "seQ", "len", "full_len",
+                    "clip_len", "n_cigar", "nm", "n_multi", "flag", "seqid", "nn", "rpos"):
+            out["se_" + name] = field(se + getattr(nabwa.SeRec, name).offset, np.dtype(ty))
+    out["se_cigar"] = field(se + nabwa.SeRec.cigar.offset, np.uint16, nabwa.MAX_CIGAR)
+    for name in ("extra_flag", "m_seqid", "am", "mapQ_paired", "m_rpos", "isize"):
+        out[name] = field(getattr(nabwa.PeRec, name).offset, np.dtype(dict(nabwa.PeRec._fields_)[name]))
+    out["isize_est"] = np.array([ii.avg, ii.std, ii.ap_prior, ii.low, ii.high, ii.high_bayesian], np.float64)
+    fixed = sum(8 * np.asarray(a).size for a in out.values())
+    for k, a in hit_arrays(n_aln, rows, ends, fixed).items():
+        out["hit_" + k] = a
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    arrays = {k: np.ascontiguousarray(v, np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "outputs to dump: %d bytes" % total
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    log("dumped %d arrays (%.1f MB) to %s" % (len(arrays), total / 1e6, dirname))
 
 
 def quick_env():
@@ -671,6 +753,8 @@ def pe_workload(ctx, G, N, steps, warmup, cpu_seconds):
         kms.append(km)
     barrier(ctx)
     elapsed = max_over_ranks(ctx, time.time() - t1)
+    if ctx.args.pe and ctx.args.dump_outputs and rank == 0:          # before the streamed steps below reuse rec_buf
+        dump_outputs(ctx.args.dump_outputs, pe_outputs(nabwa, recs, ii, *hits))
     # the same steps as a stream: the next batch's search runs on the GPU (nabwa_batch_run returns at once) while the host finishes this one -- two
     # batch objects over the same resident reads, taken in turn; the results of every step are the sequential step's
     streamed = None

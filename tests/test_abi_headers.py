@@ -1,15 +1,16 @@
-"""The structs of include/nabwa.h against the reference's own headers, by the C compiler: sizes and member offsets of
-gap_opt_t / bwt_aln1_t / bwa_seq_t / pe_opt_t / isize_info_t / bwt_multi1_t (bwtaln.h, bwape.h), and INTEGRATION.md's C
-snippets compiled verbatim against both sets of headers.  Needs /root/reference (the build container); skipped elsewhere."""
+"""The structs of include/nabwa.h against the reference's own headers: sizes and member offsets of gap_opt_t / bwt_aln1_t /
+bwa_seq_t / pe_opt_t / isize_info_t / bwt_multi1_t (bwtaln.h, bwape.h), and INTEGRATION.md's C snippets compiled verbatim against
+both sets of headers.  The reference's layouts are stored as numbers in tests/golden/ref_abi.json (tests/golden/make_ref_abi.py,
+tests/refabi.py): nabwa.h is checked against them everywhere.  Where the reference's headers are at hand, the C compiler checks
+both sets of headers directly as well, and the stored numbers against them."""
 import os
 import re
 import subprocess
 
-import pytest
+import refabi as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference's headers are not on this machine")
+REF = R.REF
 
 PRELUDE = r'''
 #include <stdint.h>
@@ -62,23 +63,60 @@ int main(void) { return 0; }
 
 
 def cc(src, tmp_path, name, extra=()):
-    f = tmp_path / name
-    f.write_text(src)
-    r = subprocess.run(["gcc", "-std=gnu11", "-fgnu89-inline", "-w", "-fsyntax-only", "-I" + REF, "-I" + os.path.join(ROOT, "include"), str(f)] + list(extra),
+    f = os.path.join(str(tmp_path), name)
+    with open(f, "w") as fh:
+        fh.write(src)
+    r = subprocess.run(["gcc", "-std=gnu11", "-fgnu89-inline", "-w", "-fsyntax-only", "-I" + REF, "-I" + os.path.join(ROOT, "include"), f] + list(extra),
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
 
 
+def integration_glue():
+    """the reference's headers and nabwa.h, and the globals bam2bam.c keeps (bam2bam.c:88-101) declared extern, as a maintainer's
+    file would see them"""
+    return (PRELUDE + "extern gap_opt_t *gap_opt; extern pe_opt_t *pe_opt; extern bntseq_t *bns; extern bwt_t *bwt[2];\n"
+            "extern int only_aligned, debug_bam, broken_input, drop_aligned, skip_duplicates;      /* bam2bam.c:96-101 */\n")
+
+
+def compile_integration_snippets(tmp_path, blocks):
+    cc(integration_glue() + "\n".join(blocks) + "\nint main(void) { return 0; }\n", tmp_path, "integration.c")
+
+
 def test_struct_layouts_match_the_reference_headers(tmp_path):
-    cc(ASSERTS, tmp_path, "layout.c")
+    ref = R.load()["layouts"]
+    got = R.measure_nabwa_layouts()
+    for t, ms in R.MEMBERS.items():
+        if t not in R.NABWA_OF or t == "isize_info_t":
+            continue
+        n = R.NABWA_OF[t]
+        assert got[n] == ref[t], "sizeof %s vs %s" % (n, t)
+        for m in ms:
+            assert got["%s.%s" % (n, m)] == ref["%s.%s" % (t, m)], "offsetof %s.%s" % (n, m)
+    # the bit-field words: the member before and after pin where they sit
+    assert got["nabwa_bwa_seq_t.bits0"] == ref["bwa_seq_t.qual"] + 8 and got["nabwa_bwa_seq_t.bits1"] + 4 == ref["bwa_seq_t.score"], \
+        "len/strand/type/extra_flag and n_mm/../mapQ words"
+    assert got["nabwa_bwa_seq_t.c1c2seq"] == ref["bwa_seq_t.pos"] + 4 and got["nabwa_bwa_seq_t.lenbits"] + 4 in (ref["bwa_seq_t.md"], ref["bwa_seq_t.md"] - 4), \
+        "c1/c2/seQ and full_len/nm words"
+    # isize_info_t = the histogram pointer, then nabwa_isize_t (bwape.h:16-20): &ii->avg is a nabwa_isize_t
+    for m in R.MEMBERS["isize_info_t"]:
+        assert got["nabwa_isize_t." + m] + ref["isize_info_t.avg"] == ref["isize_info_t." + m], "isize_info_t." + m
+    assert got["nabwa_isize_t"] + ref["isize_info_t.avg"] == ref["isize_info_t"], "isize_info_t size"
+    assert ref["bwt_multi1_t"] == 16 and ref["bwt_multi1_t.cigar"] == 8, "bwt_multi1_t as bwa_structs.hip reads it"
+    if R.have_reference():
+        cc(ASSERTS, tmp_path, "layout.c")
+        assert R.measure_reference_layouts() == ref, "tests/golden/ref_abi.json is stale: run tests/golden/make_ref_abi.py"
 
 
 def test_integration_md_snippets_compile_against_the_reference_headers(tmp_path):
-    """every ```c block of INTEGRATION.md, in order, as one translation unit after the reference's headers and nabwa.h; the
-    globals bam2bam.c keeps (bam2bam.c:88-101) are declared extern, as a maintainer's file would see them"""
-    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    blocks = re.findall(r"```c\n(.*?)```", text, re.S)
+    """every ```c block of INTEGRATION.md, in order, as one translation unit after the reference's headers and nabwa.h.  Without
+    those headers: the snippets must be the ones that compiled when tests/golden/ref_abi.json was written, and every nabwa name
+    they use must still be declared by nabwa.h"""
+    blocks = R.integration_snippets()
     assert len(blocks) >= 4
-    glue = (PRELUDE + "extern gap_opt_t *gap_opt; extern pe_opt_t *pe_opt; extern bntseq_t *bns; extern bwt_t *bwt[2];\n"
-            "extern int only_aligned, debug_bam, broken_input, drop_aligned, skip_duplicates;      /* bam2bam.c:96-101 */\n")
-    cc(glue + "\n".join(blocks) + "\nint main(void) { return 0; }\n", tmp_path, "integration.c")
+    header = open(os.path.join(ROOT, "include", "nabwa.h")).read()
+    missing = sorted({w for w in re.findall(r"\b(?:nabwa|NABWA)_\w+", "\n".join(blocks)) if not re.search(r"\b%s\b" % w, header)})
+    assert not missing, "INTEGRATION.md uses names nabwa.h does not declare: %s" % missing
+    assert R.snippets_digest(blocks) == R.load()["integration_snippets_sha256"], \
+        "INTEGRATION.md's snippets changed since they were compiled against the reference's headers: run tests/golden/make_ref_abi.py"
+    if R.have_reference():
+        compile_integration_snippets(tmp_path, blocks)

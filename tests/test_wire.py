@@ -1,19 +1,17 @@
 """The record `bwa bam2bam -p` and `bwa worker` exchange (msg_init_from_pair / pair_init_from_msg, reference bam2bam.c:951-1097) and the
 configuration reply (:1255-1266), through the library's codec (csrc/wire_worker.cpp).  PARITY UNPINNED: libzmq is absent and bam2bam.c
 cannot be compiled, so there is no reference message to compare with; the expected bytes are built by hand, field by field, from the
-cited lines (tests/wirelib.py), and the struct sizes the raw blocks rely on are checked against the reference's headers."""
+cited lines (tests/wirelib.py), and the struct sizes the raw blocks rely on are checked against the reference's headers' layouts (tests/golden/ref_abi.json)."""
 import ctypes as C
 import importlib
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import bamlib as B
 import nabwa_testlib as T
+import refabi as R
 import wirelib as W
 
 nabwa = importlib.import_module("network-aware-bwa_amd")
@@ -120,23 +118,10 @@ def test_config_reply(L):
 
 def test_raw_block_sizes_are_the_reference_structs():
     """the message carries bam1_core_t, bwt_multi1_t, bwt_aln1_t, gap_opt_t and pe_opt_t as they lie in memory: their sizes (and the bit
-    order of bam1_core_t) asked of the C compiler with the reference's own headers"""
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("the reference's headers are only in the build container")
-    src = r'''
-#include <stdio.h>
-#include <string.h>
-#include "bamlite.h"
-#include "bwtaln.h"
-int main(void) {
-    bam1_core_t c; unsigned w[8]; bwt_multi1_t m; unsigned mw[4];
-    memset(&c, 0, sizeof c); c.bin = 4681; c.qual = 37; c.l_qname = 9; c.flag = 0x63; c.n_cigar = 5; memcpy(w, &c, 32);
-    memset(&m, 0, sizeof m); m.pos = 777; m.gap = 3; m.mm = 2; m.strand = 1; memcpy(mw, &m, 16);
-    printf("%zu %zu %zu %zu %zu %u %u %u %u\n", sizeof(bam1_core_t), sizeof(bwt_multi1_t), sizeof(bwt_aln1_t), sizeof(gap_opt_t), sizeof(pe_opt_t), w[2], w[3], mw[0], mw[1]);
-    return 0; }
-'''
-    with tempfile.TemporaryDirectory() as td:
-        open(os.path.join(td, "t.c"), "w").write(src)
-        subprocess.run(["gcc", "-I/root/reference", "-o", os.path.join(td, "t"), os.path.join(td, "t.c")], check=True)
-        out = subprocess.run([os.path.join(td, "t")], capture_output=True, text=True, check=True).stdout.split()
-    assert [int(x) for x in out] == [32, 16, 16, 64, 48, 4681 | 37 << 16 | 9 << 24, 0x63 | 5 << 16, 777, 3 << 15 | 2 << 23 | 1 << 31]
+    order of bam1_core_t) as the C compiler reported them from the reference's own headers (tests/golden/ref_abi.json; asked again
+    where those headers are at hand), and the sizes of the library's counterparts"""
+    want = [32, 16, 16, 64, 48, 4681 | 37 << 16 | 9 << 24, 0x63 | 5 << 16, 777, 3 << 15 | 2 << 23 | 1 << 31]
+    assert R.load()["raw_blocks"] == want
+    if R.have_reference():
+        assert R.measure_raw_blocks() == want
+    assert (C.sizeof(nabwa.GapOpt), C.sizeof(nabwa.PeOpt), nabwa.ALN_DT.itemsize) == tuple(want[3:5]) + (want[2],)

@@ -113,6 +113,22 @@ int nabwa_batch_fetch(nabwa_batch_t *b, int32_t *n_aln, nabwa_aln1_t *aln_out, i
 int nabwa_batch_width_records(nabwa_batch_t *b, int first, int n, uint32_t *w_out, uint8_t *bid_out, uint8_t *seed_bid_out);
 /* order-independent 64-bit checksum of (read id, row index, row) over all hits, computed on the device */
 int nabwa_batch_checksum(nabwa_batch_t *b, uint64_t *sum, int64_t *n_rows);
+/* tests, diagnostics: what the batch-wide switches of the search came to for this batch (read-only).  -1: not decided yet
+ * (n_sync, cls and hard_budget before a run, hard_budget also when kernel S does not run; coop_lanes and lds_rd while kernel D
+ * has not run). */
+typedef struct {
+	int32_t n, min_len, max_len;
+	int32_t deep_only;                        /* the option block is beyond kernel S's compact entries: every read goes to kernel D */
+	int32_t ns1, ns_wide;                     /* score levels of the first pass (kernel S; computed even when deep_only) and of kernel D */
+	int32_t w_sync;                           /* every read of the batch has one length: lockstep waves in kernels W and S */
+	int32_t trip_budget, trip_budget_hard;    /* kernel S -> D hand-over budgets (trips) */
+	int32_t n_sync;                           /* reads without an exact occurrence (kernel W's classes 1 and 2+), after a run */
+	int32_t hard_budget;                      /* kernel S ran with trip_budget_hard (2 n_sync > n) */
+	int32_t cls[3];                           /* reads by kernel W's class 0 / 1 / 2+, after a run */
+	int32_t coop_lanes;                       /* kernel D's wave-wide one-row chains (0: off) */
+	int32_t lds_rd;                           /* kernel D: bytes of one read's data in LDS (0: the read is read from HBM) */
+} nabwa_batch_config_t;
+int nabwa_batch_config(nabwa_batch_t *b, nabwa_batch_config_t *out);
 void nabwa_batch_destroy(nabwa_batch_t *b);
 
 /* ---- paired-end host pieces (config 3) --------------------------------------------------------- */
@@ -179,6 +195,11 @@ int nabwa_global_align(int device, int n, const int64_t *ref_off, const uint8_t 
 
 /* The alignment entry points keep their device working memory (score rows, traceback matrices) between calls; this frees it. */
 void nabwa_dp_scratch_release(int device);
+
+/* tests, diagnostics: launches of the alignment kernels by form since the library was loaded, each picked per launch from the
+ * batch's largest task: [0] global, one wavefront per task; [1] global, lanes with rows in LDS; [2] global, lanes with rows in
+ * HBM; [3] local, rows in LDS; [4] local, rows in HBM.  Writes min(n, 5) counts. */
+void nabwa_dp_form_counts(uint64_t *out, int n);
 
 /* Batch form of aln_extend_core (stdaln.c:862-1007): left-anchored extension seeded with G0[i], then the
  * path by global alignment of the two prefixes (gap_end = -1, band doubled until the scores agree or it

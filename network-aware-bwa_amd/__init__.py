@@ -34,6 +34,14 @@ class GapOpt(C.Structure):
 MAX_CIGAR, MAX_MD, MAX_MULTI = 64, 512, 16
 
 
+class BatchConfig(C.Structure):
+    """nabwa_batch_config_t (include/nabwa.h): what the batch-wide switches of one batch's search came to."""
+    _fields_ = [("n", C.c_int32), ("min_len", C.c_int32), ("max_len", C.c_int32), ("deep_only", C.c_int32),
+                ("ns1", C.c_int32), ("ns_wide", C.c_int32), ("w_sync", C.c_int32), ("trip_budget", C.c_int32),
+                ("trip_budget_hard", C.c_int32), ("n_sync", C.c_int32), ("hard_budget", C.c_int32), ("cls", C.c_int32 * 3),
+                ("coop_lanes", C.c_int32), ("lds_rd", C.c_int32)]
+
+
 class SeMulti(C.Structure):
     """nabwa_multi_t"""
     _fields_ = [("pos", C.c_uint32), ("gap", C.c_int32), ("mm", C.c_int32), ("strand", C.c_int32),
@@ -183,6 +191,14 @@ def extend_align(ref, ref_off, qry, qry_off, gap_open, gap_ext, matrix25, band, 
     return score[:n], [cig[i, :ncig[i]] for i in range(n)]
 
 
+def dp_form_counts():
+    """launches of the alignment kernels by form since the library was loaded (nabwa_dp_form_counts):
+    global wave / global LDS lanes / global HBM lanes / local rows in LDS / local rows in HBM"""
+    out = (C.c_uint64 * 5)()
+    lib().nabwa_dp_form_counts(out, 5)
+    return list(out)
+
+
 class NabwaError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libnabwa error %d: %s" % (code, msg))
@@ -236,6 +252,9 @@ def lib():
     L.nabwa_batch_fetch.argtypes = [_P, _P, _P, C.c_int64, _P, _P]
     L.nabwa_batch_checksum.argtypes = [_P, _P, _P]
     L.nabwa_batch_count_touches.argtypes = [_P, _P, _P]
+    L.nabwa_batch_config.argtypes = [_P, _P]
+    L.nabwa_dp_form_counts.argtypes = [_P, C.c_int]
+    L.nabwa_dp_form_counts.restype = None
     L.nabwa_batch_destroy.argtypes = [_P]
     L.nabwa_batch_destroy.restype = None
     L.nabwa_sa_lookup.argtypes = [_P, C.c_int, _P, _P, _P]
@@ -536,6 +555,12 @@ class Batch:
         if keep is not None:
             keep["n_aln"], keep["maxe"], keep["rows"] = n_aln, maxe, buf
         return n_aln[:self.n], buf[:rows.value], maxe[:self.n]
+
+    def config(self):
+        """the batch's derived configuration as a dict (nabwa_batch_config); -1: not decided yet"""
+        c = BatchConfig()
+        _chk(lib().nabwa_batch_config(self._h, C.byref(c)))
+        return {f: (list(getattr(c, f)) if f == "cls" else getattr(c, f)) for f, _ in BatchConfig._fields_}
 
     def close(self):
         if self._h:

@@ -14,6 +14,7 @@
 // open come here, so this kernel is small next to the FM search.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 
 #define NINF (-1073741823)   // MINOR_INF, stdaln.h:84
 #define FM 0
@@ -332,6 +333,13 @@ __global__ __launch_bounds__(64) void dp_global_wave_kernel(const DpParams P)
 #undef TBW
 }
 
+/* launches by form (nabwa_dp_form_counts): [0..2] here, [3..4] in dp_wave.hip */
+std::atomic<uint64_t> g_dp_form_count[5];
+extern "C" void nabwa_dp_form_counts(uint64_t *out, int n)
+{
+	for (int i = 0; i < n && i < 5; ++i) out[i] = g_dp_form_count[i].load();
+}
+
 extern "C" void nabwa_launch_dp_global(const DpParams *P, hipStream_t s)
 {
 	if (P->n <= 0) return;
@@ -341,12 +349,16 @@ extern "C" void nabwa_launch_dp_global(const DpParams *P, hipStream_t s)
 	const size_t wlds = P->wb > 0 ? (size_t)6 * P->W * 4 + (size_t)P->H * ((P->wb + 1) / 2 + 1) + (size_t)(P->W + P->H) * 2 + 16 : 0;
 	if (wlds && wlds <= 64000 && !(getenv("NABWA_DP_WAVE") && atoi(getenv("NABWA_DP_WAVE")) == 0)) {
 		hipLaunchKernelGGL(dp_global_wave_kernel, dim3(P->n), dim3(64), wlds, s, *P);
+		++g_dp_form_count[0];
 		return;
 	}
-	if (P->n <= small_max && lds <= 60000)
+	if (P->n <= small_max && lds <= 60000) {
 		hipLaunchKernelGGL(dp_global_kernel<true>, dim3((P->n + DP_SMALL_LANES - 1) / DP_SMALL_LANES), dim3(DP_SMALL_LANES), lds, s, *P);
-	else
+		++g_dp_form_count[1];
+	} else {
 		hipLaunchKernelGGL(dp_global_kernel<false>, dim3((P->n + 255) / 256), dim3(256), 0, s, *P);
+		++g_dp_form_count[2];
+	}
 }
 
 // aln_local_core and aln_extend_core (forward / reverse Smith-Waterman passes): dp_wave.hip, one wavefront per task.

@@ -446,6 +446,8 @@ struct nabwa_batch {
 	size_t deep_pages, deep_own_words, deep_stage_ent;
 	hipEvent_t evd0, evd1; float last_ms_deep; int deep_ran, deep_only;
 	int deep_cfg; uint32_t deep_K, deep_lds_rd, deep_rd_pl; size_t deep_n_pages; uint64_t deep_cap_pages; long deep_waves_max;
+	// what nabwa_batch_config reports and nothing reads back otherwise
+	int min_len, ran, deep_coop; uint32_t NS1;
 };
 
 static uint32_t align_up(uint32_t x, uint32_t a) { return (x + a - 1) / a * a; }
@@ -592,7 +594,7 @@ extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 	// reads: upload as given, then re-lay out on the device with 16-byte aligned starts
 	const size_t nb = (size_t)off[n] > 0 ? (size_t)off[n] : 1, pnb = (size_t)padded_total + 64;
 	if ((uint64_t)pnb >= (1ull << 32)) { nabwa_batch_destroy(b); return fail(NABWA_EINVAL, "batch holds 4 Gi padded bases or more: split it (lane state keeps a 32-bit read offset)"); }
-	b->max_len = max_len;
+	b->max_len = max_len; b->min_len = n ? min_len : 0; b->NS1 = NS1; b->deep_coop = -1;
 	BCHK(pool_malloc(b->ix, (void**)&b->d_seq, pnb)); BCHK(pool_malloc(b->ix, (void**)&b->d_rseq, pnb));
 	BCHK(pool_malloc(b->ix, (void**)&b->d_poff, (size_t)(n + 1) * 8)); BCHK(pool_malloc(b->ix, (void**)&b->d_len, (size_t)(n ? n : 1) * 4));
 	BCHK(pool_malloc(b->ix, (void**)&b->d_md, n ? n : 1)); BCHK(pool_malloc(b->ix, (void**)&b->d_mg, n ? n : 1)); BCHK(pool_malloc(b->ix, (void**)&b->d_key, (size_t)(n ? n : 1) * 24));
@@ -730,6 +732,7 @@ extern "C" int nabwa_batch_run(nabwa_batch_t *b)
 	if (b->class_sort && env_int("NABWA_DEEP_ORDER", 1)) nabwa_launch_collect_keyed(b->n, b->d_status, b->d_ovf_ids, b->d_novf, NABWA_ST_OVERFLOW, b->d_cls, b->d_md, 7, b->d_naln, b->P.aln_cap, b->stream);
 	else nabwa_launch_collect(b->n, b->d_status, b->d_ovf_ids, b->d_novf, NABWA_ST_OVERFLOW, b->stream);
 	HIPCHK(hipGetLastError());
+	b->ran = 1;
 	return NABWA_OK;
 }
 
@@ -896,6 +899,7 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 		/* the wave-wide expansion of one-row chains pays where chains are long: reads of 100 bases and more (PE D -24 %); on reads of 50-76 bases
 		 * its chains end after a level or two, and the kernel built without it is the faster one (profiles/r03_deep_variants.txt) */
 		D.coop_lanes = (uint32_t)env_int("NABWA_DEEP_COOP", b->max_len >= 90 ? 4 : 0);
+		b->deep_coop = (int)D.coop_lanes;
 		/* NABWA_DEEP_DUMP=<file> (investigations of the work order): per search of the first launch its read, length, max_diff, the width
 		 * passes' restart classes, what kernel S saw of it (trips, hits) and the rounds kernel D needed -- int32 x 8 per search */
 		const char *dump_path = getenv("NABWA_DEEP_DUMP");
@@ -1118,6 +1122,30 @@ extern "C" int nabwa_batch_checksum(nabwa_batch_t *b, uint64_t *sum, int64_t *n_
 	HIPCHK(hipStreamSynchronize(b->stream));
 	if (sum) *sum = h[0];
 	if (n_rows) *n_rows = (int64_t)h[1];
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_batch_config(nabwa_batch_t *b, nabwa_batch_config_t *out)
+{
+	if (!b || !out) return fail(NABWA_EINVAL, "null argument");
+	memset(out, 0, sizeof(*out));
+	out->n = b->n; out->min_len = b->min_len; out->max_len = b->max_len;
+	out->deep_only = b->deep_only; out->ns1 = (int32_t)b->NS1; out->ns_wide = (int32_t)b->NS_wide;
+	out->w_sync = b->P.w_sync; out->trip_budget = (int32_t)b->P.trip_budget; out->trip_budget_hard = (int32_t)b->P.trip_budget_hard;
+	out->n_sync = out->hard_budget = -1;
+	for (int q = 0; q < 3; ++q) out->cls[q] = -1;
+	if (b->ran && b->class_sort) {
+		HIPCHK(hipSetDevice(b->ix->device));
+		unsigned int c[12];
+		HIPCHK(hipMemcpyAsync(c, b->d_ncls, 48, hipMemcpyDeviceToHost, b->stream));
+		HIPCHK(hipStreamSynchronize(b->stream));
+		for (int q = 0; q < 3; ++q) out->cls[q] = (int32_t)c[q];
+		out->n_sync = (int32_t)c[10];
+		/* the rule of fm_search_kernel: the hard budget when most reads occur exactly on neither strand */
+		if (!b->deep_only) out->hard_budget = b->P.trip_budget_hard && 2u * c[10] > (uint32_t)b->n ? 1 : 0;
+	}
+	out->coop_lanes = b->deep_coop;
+	out->lds_rd = b->deep_cfg ? (int32_t)b->deep_lds_rd : -1;
 	return NABWA_OK;
 }
 

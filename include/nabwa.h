@@ -471,6 +471,26 @@ int nabwa_index_export(const nabwa_index_t *ix, int which, int what, uint64_t fi
 /* Rank primitives for tests: Occ of all four bases at rows k[i] (bwt_occ4, bwt.c:159-176). */
 int nabwa_occ4(nabwa_index_t *ix, int which, int n, const uint32_t *k, uint32_t *cnt_out /* n x 4 */);
 
+/* ---- index construction: `bwa index` (bwtindex.c:39-196) ------------------------------------------------------------
+ * nabwa_index_fa2pac   = bns_fasta2bntseq + bns_dump (bntseq.c:58-85,166-256) and bwa_pac_rev_core (bwtmisc.c:168-193): FASTA or
+ *                        FASTQ, plain or gzip, in; <prefix>.pac, .ann, .amb and .rpac out, byte for byte the reference's (ambiguous
+ *                        bases drawn from lrand48 after srand48(11), holes, the stale-comment quirk of kseq).  Host only, no GPU.
+ *                        Returns l_pac, or a negative NABWA_E*: NABWA_EINVAL for an input without bases or over 4 Gbp (nothing is
+ *                        written then), NABWA_EIO for a file that cannot be read or written.  prefix NULL: read and check the
+ *                        input only, write nothing.
+ * nabwa_index_fa2cspac = the same for `bwa index -c` (bwtindex.c:84-98, bwa_pac2cspac, bwtmisc.c:210-254): <prefix>.nt.pac/.ann/.amb
+ *                        of the bases, then the colour text as <prefix>.pac/.ann/.amb/.rpac.  Host only.
+ * nabwa_index_build    = the BWT, Occ and SA steps (bwtindex.c:104-191) on the GPU: <prefix>.pac in, <prefix>.bwt, .rbwt (of the
+ *                        reversed text), .sa and .rsa (every sa_intv-th row; the reference uses 32) out, the words the reference writes
+ *                        whichever of -a is / bwtsw it runs.  The worst-case device memory (nabwa_index_build_estimate, about
+ *                        41 bytes per base) is checked against the device's free memory and against NABWA_INDEX_MAX_BYTES when that
+ *                        is set: NABWA_ENOMEM before any allocation if it does not fit.  Texts up to 4 294 967 279 bases.
+ *                        verbose != 0: stage times and peak device memory on stderr. */
+int64_t nabwa_index_fa2pac(const char *fasta, const char *prefix);
+int64_t nabwa_index_fa2cspac(const char *fasta, const char *prefix);
+int nabwa_index_build(const char *prefix, int device, int sa_intv, int verbose);
+int nabwa_index_build_estimate(uint64_t l_pac, uint64_t *bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,6 +277,12 @@ def lib():
     L.nabwa_pe_opt_default.restype = None
     L.nabwa_pe_posn.argtypes = [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P]
     L.nabwa_pe_finish.argtypes = [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]
+    L.nabwa_index_fa2pac.restype = C.c_int64
+    L.nabwa_index_fa2pac.argtypes = [C.c_char_p, C.c_char_p]
+    L.nabwa_index_fa2cspac.restype = C.c_int64
+    L.nabwa_index_fa2cspac.argtypes = [C.c_char_p, C.c_char_p]
+    L.nabwa_index_build.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int]
+    L.nabwa_index_build_estimate.argtypes = [C.c_uint64, _P]
     _lib = L
     return L
 
@@ -300,6 +306,29 @@ def gap_init_opt():
 def cal_maxdiff(length, err=0.02, thres=0.04):
     """bwa_cal_maxdiff (reference bwtaln.c:37-49)."""
     return lib().nabwa_cal_maxdiff(int(length), float(err), float(thres))
+
+
+def index_fa2pac(fasta, prefix, colour=False):
+    """`bwa index` up to the BWT (reference bntseq.c:166-256, bwtmisc.c:168-193): FASTA (plain or gzip) -> <prefix>.pac, .ann,
+    .amb, .rpac; colour=True: `bwa index -c`'s <prefix>.nt.pac/.ann/.amb and the colour <prefix>.pac/.ann/.amb/.rpac
+    (bwtmisc.c:210-254).  Host only.  Returns l_pac."""
+    f = lib().nabwa_index_fa2cspac if colour else lib().nabwa_index_fa2pac
+    n = f(os.fsencode(fasta), os.fsencode(prefix))
+    if n < 0:
+        raise NabwaError(int(n), lib().nabwa_last_error().decode())
+    return int(n)
+
+
+def index_build(prefix, device=0, sa_intv=32, verbose=False):
+    """The FM-indexes of <prefix>.pac on the GPU: <prefix>.bwt, .rbwt, .sa, .rsa (reference bwtindex.c:104-191)."""
+    _chk(lib().nabwa_index_build(os.fsencode(prefix), int(device), int(sa_intv), int(verbose)))
+
+
+def index_build_estimate(l_pac):
+    """Worst-case device bytes nabwa_index_build needs for l_pac bases (what it checks before allocating)."""
+    out = C.c_uint64()
+    _chk(lib().nabwa_index_build_estimate(int(l_pac), C.byref(out)))
+    return out.value
 
 
 class Index:

@@ -19,41 +19,15 @@
 #include <stdlib.h>
 #include <string.h>
 #include <sys/mman.h>
-#include <chrono>
-#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 #include "../../include/nabwa.h"
 #include "nabwa_internal.hpp"
 #include "finish_common.hpp"
 
-void nabwa_poscache_register(nabwa_poscache_t *cache, int max_occ, int n, const int *first, const int32_t *n_aln, const int64_t *row0,
-							 const nabwa_aln1_t *rows, const nabwa_pe_t *res);                                                       /* pe_finish.hip */
-/* the single-end chain on records of any stride whose head is a nabwa_se_t (se_finish.hip): this file works in place */
-int nabwa_se_posn_strided(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, const int64_t *off, const int32_t *full_len,
-						  const int32_t *n_aln, const nabwa_aln1_t *aln, const uint8_t *n_occ_v, uint64_t *rng48, void *out_base, size_t stride);
-int nabwa_se_refine_strided(nabwa_index_t *ix, int n, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, void *out_base, size_t stride);
-
-/* slices of independent records on the host's threads */
-static int bam_threads(size_t n)
-{
-	int nt = (int)std::thread::hardware_concurrency(); if (nt < 1) nt = 1; if (nt > 16) nt = 16;
-	if (getenv("NABWA_HOST_THREADS")) nt = atoi(getenv("NABWA_HOST_THREADS")) > 0 ? atoi(getenv("NABWA_HOST_THREADS")) : 1;
-	if (n < 8192) nt = 1;
-	return nt;
-}
-static double bam_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static void bam_parallel(size_t n, const std::function<void(int, size_t, size_t)> &f)
-{
-	const int nt = bam_threads(n);
-	if (nt == 1) { f(0, 0, n); return; }
-	std::vector<std::thread> th;
-	for (int t = 0; t < nt; ++t) th.emplace_back(f, t, n * t / nt, n * (t + 1) / nt);
-	for (auto &x : th) x.join();
-}
+static const size_t BAM_MIN_N = 8192;          /* records below which the host work of a batch stays on one thread */
 
 #define F_PD 1
 #define F_PP 2
@@ -487,14 +461,14 @@ struct RecArr {
 		if (!p) { bytes = 0; return false; }
 		n = m;
 		BamRec *const q = p;
-		bam_parallel(m, [q](int, size_t lo, size_t hi) { for (size_t i = lo; i < hi; ++i) new (q + i) BamRec(); });
+		host_parallel(host_threads(m, BAM_MIN_N), m, [q](int, size_t lo, size_t hi) { for (size_t i = lo; i < hi; ++i) new (q + i) BamRec(); });
 		return true;
 	}
 	void clear()
 	{
 		if (p) {
 			BamRec *const q = p;
-			bam_parallel(n, [q](int, size_t lo, size_t hi) { for (size_t i = lo; i < hi; ++i) q[i].~BamRec(); });
+			host_parallel(host_threads(n, BAM_MIN_N), n, [q](int, size_t lo, size_t hi) { for (size_t i = lo; i < hi; ++i) q[i].~BamRec(); });
 			res_give(p, bytes);
 		}
 		p = 0; n = 0; bytes = 0;
@@ -563,7 +537,7 @@ extern "C" int nabwa_bam_batch_create_ex(nabwa_index_t *ix, const nabwa_gap_opt_
 	nabwa_bam_batch *b = new nabwa_bam_batch();
 	b->ix = ix; b->opt = *opt; b->popt = *popt; b->phase = 0; b->flags = flags;
 	const bool timing = getenv("NABWA_TIMING") != 0;
-	const double tc0 = bam_now();
+	const double tc0 = now_s();
 	std::vector<uint32_t> flag_or;
 	if (!b->rec.make((size_t)n_rec)) { delete b; return nabwa_fail(NABWA_ENOMEM, "out of memory for the records"); }
 	{
@@ -571,9 +545,10 @@ extern "C" int nabwa_bam_batch_create_ex(nabwa_index_t *ix, const nabwa_gap_opt_
 		b->arena_bytes = (size_t)(n_rec ? in_off[n_rec] - in_off[0] : 0) + (size_t)n_rec * (REC_ROOM - 36) + 64;
 		b->arena = (uint8_t*)res_take(b->arena_bytes);
 		if (!b->arena) { b->arena_bytes = 0; delete b; return nabwa_fail(NABWA_ENOMEM, "out of memory for the records"); }
-		std::vector<int> bad(bam_threads((size_t)n_rec), 0);
-		flag_or.assign(bam_threads((size_t)n_rec) * 16, 0u);          /* (a line per thread) */
-		bam_parallel((size_t)n_rec, [&](int t, size_t lo, size_t hi) {
+		const int nt = host_threads((size_t)n_rec, BAM_MIN_N);
+		std::vector<int> bad(nt, 0);
+		flag_or.assign((size_t)nt * 16, 0u);          /* (a line per thread) */
+		host_parallel(nt, (size_t)n_rec, [&](int t, size_t lo, size_t hi) {
 			uint32_t fo = 0;
 			for (size_t i = lo; i < hi; ++i)
 			{
@@ -590,7 +565,7 @@ extern "C" int nabwa_bam_batch_create_ex(nabwa_index_t *ix, const nabwa_gap_opt_
 		});
 		for (int x : bad) if (x) { delete b; return nabwa_fail(NABWA_EINVAL, x == 2 ? "malformed tags in a BAM record" : "malformed BAM record"); }
 	}
-	const double tc1 = bam_now();
+	const double tc1 = now_s();
 	/* logical records (read_bam_pair_core, bwaseqio.c:346-410): a paired read takes the next record as its mate -- same name,
 	 * flags read 1 / read 2 in either order.  Anything else is an error, or with NABWA_BAM_BROKEN_INPUT (allow_broken) is mended as
 	 * the reference mends it: wrong flags are set right, a paired read whose successor has another name is discarded and that
@@ -605,7 +580,7 @@ extern "C" int nabwa_bam_batch_create_ex(nabwa_index_t *ix, const nabwa_gap_opt_
 			/* single-end records only and nothing to leave out: every record is a logical record of its own */
 			b->kind.assign((size_t)n_rec, 1); b->skip.assign((size_t)n_rec, 0); b->first.resize((size_t)n_rec);
 			int *const fp = b->first.data();
-			bam_parallel((size_t)n_rec, [fp](int, size_t lo, size_t hi) { for (size_t i = lo; i < hi; ++i) fp[i] = (int)i; });
+			host_parallel(host_threads((size_t)n_rec, BAM_MIN_N), (size_t)n_rec, [fp](int, size_t lo, size_t hi) { for (size_t i = lo; i < hi; ++i) fp[i] = (int)i; });
 			src.resize((size_t)n_rec);      /* (only its size is looked at) */
 		} else {
 		src.reserve(n_rec); b->kind.reserve(n_rec); b->first.reserve(n_rec); b->skip.reserve(n_rec);
@@ -647,15 +622,15 @@ extern "C" int nabwa_bam_batch_create_ex(nabwa_index_t *ix, const nabwa_gap_opt_
 			n_rec = (int)src.size();
 		}
 	}
-	const double tc1a = bam_now();
-	const double tc1b = bam_now();
+	const double tc1a = now_s();
+	const double tc1b = now_s();
 	{
 		const size_t nk = b->kind.size();
 		b->rg.resize(nk);
 		std::map<std::string, int> ids;
 		/* "the same read group as the logical record before" by all threads (the records' bytes are touched there); the names that change, in order, by one */
 		std::vector<uint8_t> same_rg(nk ? nk : 1, 0);
-		bam_parallel(nk, [&](int, size_t lo, size_t hi) {
+		host_parallel(host_threads(nk, BAM_MIN_N), nk, [&](int, size_t lo, size_t hi) {
 			for (size_t k = lo ? lo : 1; k < hi; ++k) {
 				const BamRec &r0 = b->rec[b->first[k]], &rp = b->rec[b->first[k - 1]];
 				same_rg[k] = r0.rg_n == rp.rg_n && !memcmp(r0.rg_p, rp.rg_p, r0.rg_n);
@@ -670,14 +645,14 @@ extern "C" int nabwa_bam_batch_create_ex(nabwa_index_t *ix, const nabwa_gap_opt_
 			b->rg[k] = ins.first->second;
 		}
 	}
-	const double tc2 = bam_now();
+	const double tc2 = now_s();
 	/* bam1_to_seq (bwaseqio.c:272-307): the (trimmed) lengths first, then every thread encodes its slice of the reads in place */
 	b->off.assign(n_rec + 1, 0); b->full_len.assign(n_rec ? n_rec : 1, 0);
 	{
 		std::vector<int32_t> lens(n_rec ? n_rec : 1, 0);
 		std::vector<uint8_t> rskip(n_rec ? n_rec : 1, 0);       /* a duplicate that is passed through is searched as a read without bases */
 		for (size_t k = 0; k < b->kind.size(); ++k) if (b->skip[k]) for (int e = 0; e < b->kind[k]; ++e) rskip[b->first[k] + e] = 1;
-		bam_parallel((size_t)n_rec, [&](int, size_t lo, size_t hi) {
+		host_parallel(host_threads((size_t)n_rec, BAM_MIN_N), (size_t)n_rec, [&](int, size_t lo, size_t hi) {
 			for (size_t i = lo; i < hi; ++i) {
 				const BamRec &x = b->rec[i];
 				const int L = x.l_qseq;
@@ -699,7 +674,7 @@ extern "C" int nabwa_bam_batch_create_ex(nabwa_index_t *ix, const nabwa_gap_opt_
 		});
 		for (int i = 0; i < n_rec; ++i) b->off[i + 1] = b->off[i] + lens[i];
 		if (!b->seq.alloc((size_t)b->off[n_rec] + 1) || !b->rseq.alloc((size_t)b->off[n_rec] + 1)) { delete b; return nabwa_fail(NABWA_ENOMEM, "out of memory for the reads"); }
-		bam_parallel((size_t)n_rec, [&](int, size_t lo, size_t hi) {
+		host_parallel(host_threads((size_t)n_rec, BAM_MIN_N), (size_t)n_rec, [&](int, size_t lo, size_t hi) {
 			for (size_t i = lo; i < hi; ++i) {
 				const BamRec &x = b->rec[i];
 				const int L = x.l_qseq, len = lens[i];
@@ -729,7 +704,7 @@ extern "C" int nabwa_bam_batch_create_ex(nabwa_index_t *ix, const nabwa_gap_opt_
 		b->seq.data()[b->off[n_rec]] = 0; b->rseq.data()[b->off[n_rec]] = 0;
 	}
 	if (timing) fprintf(stderr, "[nabwa] bam_batch_create %d records: parse %.3f s, pairing %.3f s, tag erase %.3f s, read groups %.3f s, bam1_to_seq %.3f s (%d threads)\n",
-						n_rec, tc1 - tc0, tc1a - tc1, tc1b - tc1a, tc2 - tc1b, bam_now() - tc2, bam_threads((size_t)n_rec));
+						n_rec, tc1 - tc0, tc1a - tc1, tc1b - tc1a, tc2 - tc1b, now_s() - tc2, host_threads((size_t)n_rec, BAM_MIN_N));
 	*out = b;
 	return NABWA_OK;
 }
@@ -747,7 +722,7 @@ static void park(nabwa_bam_batch *b)
 	b->parked_at.assign(n + 1, 0);
 	for (size_t i = 0; i < n; ++i) b->parked_at[i + 1] = b->parked_at[i] + PARK_HEAD + 4 + PARK_MULTI * (size_t)b->res[i].se.n_multi;
 	b->parked.resize(b->parked_at[n] ? b->parked_at[n] : 1);
-	bam_parallel(n, [&](int, size_t lo, size_t hi) {
+	host_parallel(host_threads(n, BAM_MIN_N), n, [&](int, size_t lo, size_t hi) {
 		for (size_t i = lo; i < hi; ++i) {
 			const nabwa_se_t &s = b->res[i].se;
 			uint8_t *o = b->parked.data() + b->parked_at[i];
@@ -763,7 +738,7 @@ static bool unpark(nabwa_bam_batch *b)
 	const size_t n = b->rec.size();
 	b->res = (nabwa_pe_t*)res_take(b->res_bytes);
 	if (!b->res) return false;
-	bam_parallel(n, [&](int, size_t lo, size_t hi) {
+	host_parallel(host_threads(n, BAM_MIN_N), n, [&](int, size_t lo, size_t hi) {
 		for (size_t i = lo; i < hi; ++i) {
 			nabwa_pe_t &r = b->res[i]; nabwa_se_t &s = r.se;
 			const uint8_t *o = b->parked.data() + b->parked_at[i];
@@ -814,7 +789,7 @@ extern "C" int nabwa_bam_batch_pass1(nabwa_bam_batch_t *b, uint64_t *rng48, nabw
 	if (b->phase != 0) return nabwa_fail(NABWA_EINVAL, "pass 1 already ran on this batch");
 	const int n = (int)b->rec.size();
 	const bool timing = getenv("NABWA_TIMING") != 0;
-	const double tp0 = bam_now();
+	const double tp0 = now_s();
 	int rc = b->searched ? NABWA_OK : nabwa_bam_batch_search(b);
 	if (rc != NABWA_OK) return rc;
 	for (int i = 0; i < n; ++i) b->row0[i + 1] = b->row0[i] + b->n_aln[i];
@@ -827,17 +802,17 @@ extern "C" int nabwa_bam_batch_pass1(nabwa_bam_batch_t *b, uint64_t *rng48, nabw
 	b->res_bytes = sizeof(nabwa_pe_t) * (size_t)(n ? n : 1);
 	b->res = (nabwa_pe_t*)res_take(b->res_bytes);
 	if (!b->res) return nabwa_fail(NABWA_ENOMEM, "out of memory for the batch's records");
-	const double tp1 = bam_now();
+	const double tp1 = now_s();
 	rc = nabwa_se_posn_strided(b->ix, &b->opt, n, b->off.data(), b->full_len.data(), b->n_aln.data(), b->rows.data(), n_occ.data(), rng48, b->res, sizeof(nabwa_pe_t));
 	if (rc != NABWA_OK) return rc;
-	bam_parallel((size_t)n, [&](int, size_t lo, size_t hi) {
+	host_parallel(host_threads((size_t)n, BAM_MIN_N), (size_t)n, [&](int, size_t lo, size_t hi) {
 		for (size_t i = lo; i < hi; ++i) { nabwa_pe_t &r = b->res[i]; r.extra_flag = 0; r.m_seqid = 0; r.am = 0; r.mapQ_paired = 0; r.m_rpos = 0; r.isize = 0; }
 	});
 	/* improve_isize_est (insert_size.c:141-165): the bins by many threads, the counts in record order */
 	{
 		const size_t nk = b->kind.size();
 		std::vector<int> bin(nk ? nk : 1, -1);
-		bam_parallel(nk, [&](int, size_t lo, size_t hi) {
+		host_parallel(host_threads(nk, BAM_MIN_N), nk, [&](int, size_t lo, size_t hi) {
 			for (size_t k = lo; k < hi; ++k) {
 				if (b->skip[k]) continue;
 				const int i = b->first[k];
@@ -856,7 +831,7 @@ extern "C" int nabwa_bam_batch_pass1(nabwa_bam_batch_t *b, uint64_t *rng48, nabw
 	}
 	if (b->kind.size() != b->rec.size()) park(b);
 	b->phase = 1;
-	if (timing) fprintf(stderr, "[nabwa] bam_batch_pass1 %d records: search (upload, kernels, rows back) %.3f s, posn + insert-size bins %.3f s\n", n, tp1 - tp0, bam_now() - tp1);
+	if (timing) fprintf(stderr, "[nabwa] bam_batch_pass1 %d records: search (upload, kernels, rows back) %.3f s, posn + insert-size bins %.3f s\n", n, tp1 - tp0, now_s() - tp1);
 	return NABWA_OK;
 }
 
@@ -902,7 +877,7 @@ extern "C" int nabwa_bam_batch_restore(nabwa_bam_batch_t *b, const nabwa_wire_re
 	b->res_bytes = sizeof(nabwa_pe_t) * (size_t)(n ? n : 1);
 	b->res = (nabwa_pe_t*)res_take(b->res_bytes);
 	if (!b->res) return nabwa_fail(NABWA_ENOMEM, "out of memory for the batch's records");
-	bam_parallel((size_t)n, [&](int, size_t lo, size_t hi) {
+	host_parallel(host_threads((size_t)n, BAM_MIN_N), (size_t)n, [&](int, size_t lo, size_t hi) {
 		for (size_t i = lo; i < hi; ++i) {
 			const nabwa_wire_read_t &w = in[i]; nabwa_pe_t &r = b->res[i]; nabwa_se_t &s = r.se;
 			if (w.n_aln) memcpy(b->rows.data() + b->row0[i], w.aln, 16 * (size_t)w.n_aln);
@@ -946,7 +921,7 @@ extern "C" int nabwa_bam_batch_pass2(nabwa_bam_batch_t *b, const nabwa_isize_tab
 	if (b->phase != 1) return nabwa_fail(NABWA_EINVAL, "pass 2 needs a batch that went through pass 1 once");
 	const nabwa_reference *R = b->ix->ref;
 	const bool timing = getenv("NABWA_TIMING") != 0;
-	const double tq0 = bam_now();
+	const double tq0 = now_s();
 	if (!b->res && !unpark(b)) return nabwa_fail(NABWA_ENOMEM, "out of memory for the batch's records");
 	/* ---- singletons: bwa_refine_gapped + what bwa_update_bam1 derives */
 	{
@@ -998,7 +973,7 @@ extern "C" int nabwa_bam_batch_pass2(nabwa_bam_batch_t *b, const nabwa_isize_tab
 			nabwa_pe_t *pe = (nabwa_pe_t*)res_take(pe_bytes);
 			if (!pe || !sq.alloc((size_t)off[nr] + 1) || !rq.alloc((size_t)off[nr] + 1) || !rowb.alloc(sizeof(nabwa_aln1_t) * ((size_t)r0[nr] + 1))) { res_give(pe, pe_bytes); return nabwa_fail(NABWA_ENOMEM, "out of memory for a read group's pairs"); }
 			nabwa_aln1_t *rows = (nabwa_aln1_t*)rowb.data();
-			bam_parallel(nr, [&](int, size_t lo, size_t hi) {
+			host_parallel(host_threads(nr, BAM_MIN_N), nr, [&](int, size_t lo, size_t hi) {
 				for (size_t q = lo; q < hi; ++q) {
 					const int i = idx[q >> 1] + (int)(q & 1);
 					memcpy(sq.data() + off[q], b->seq.data() + b->off[i], (size_t)(off[q + 1] - off[q]));
@@ -1009,14 +984,14 @@ extern "C" int nabwa_bam_batch_pass2(nabwa_bam_batch_t *b, const nabwa_isize_tab
 			});
 			sq.data()[off[nr]] = 0; rq.data()[off[nr]] = 0; memset(&rows[r0[nr]], 0, sizeof(nabwa_aln1_t));
 			int rc = nabwa_pe_finish_cached(b->ix, &b->opt, &b->popt, &ii, np, off.data(), sq.data(), rq.data(), na.data(), rows, pe, n_tot, n_mapped, tab->poscache);
-			if (rc == NABWA_OK) bam_parallel(nr, [&](int, size_t lo, size_t hi) { for (size_t q = lo; q < hi; ++q) copy_filled(b->res[idx[q >> 1] + (int)(q & 1)], pe[q]); });
+			if (rc == NABWA_OK) host_parallel(host_threads(nr, BAM_MIN_N), nr, [&](int, size_t lo, size_t hi) { for (size_t q = lo; q < hi; ++q) copy_filled(b->res[idx[q >> 1] + (int)(q & 1)], pe[q]); });
 			res_give(pe, pe_bytes);
 			if (rc != NABWA_OK) return rc;
 		}
 	}
 	/* ---- bwa_update_bam1 */
-	const double tq1 = bam_now();
-	bam_parallel(b->kind.size(), [&](int, size_t lo, size_t hi) {
+	const double tq1 = now_s();
+	host_parallel(host_threads(b->kind.size(), BAM_MIN_N), b->kind.size(), [&](int, size_t lo, size_t hi) {
 		for (size_t k = lo; k < hi; ++k) {
 			/* (a record's pieces lie far apart -- its parsed head, the end of its bytes in the arena where the tags go, the head and the MD field of
 			 * its 3 KB working record: asked for ahead, the ones behind a pointer once that pointer is at hand) */
@@ -1035,7 +1010,7 @@ extern "C" int nabwa_bam_batch_pass2(nabwa_bam_batch_t *b, const nabwa_isize_tab
 	b->phase = 2;
 	/* the records are complete: the 3 KB per read that led to them go back to the pool (a batch may wait long for its turn to be written) */
 	res_give(b->res, b->res_bytes); b->res = 0;
-	if (timing) fprintf(stderr, "[nabwa] bam_batch_pass2 %zu records: finishing chains %.3f s, bwa_update_bam1 %.3f s\n", b->rec.size(), tq1 - tq0, bam_now() - tq1);
+	if (timing) fprintf(stderr, "[nabwa] bam_batch_pass2 %zu records: finishing chains %.3f s, bwa_update_bam1 %.3f s\n", b->rec.size(), tq1 - tq0, now_s() - tq1);
 	return NABWA_OK;
 }
 
@@ -1058,17 +1033,17 @@ extern "C" int nabwa_bam_batch_output(const nabwa_bam_batch_t *b, uint8_t *out, 
 	} else {       /* every record, in the order they lie in (logical records are consecutive) */
 		pick.resize(n);
 		int *const pp = pick.data();
-		bam_parallel(n, [pp](int, size_t lo, size_t hi) { for (size_t t = lo; t < hi; ++t) pp[t] = (int)t; });
+		host_parallel(host_threads(n, BAM_MIN_N), n, [pp](int, size_t lo, size_t hi) { for (size_t t = lo; t < hi; ++t) pp[t] = (int)t; });
 	}
 	const size_t m = pick.size();
 	std::vector<int64_t> at(n + 1, 0);
-	bam_parallel(m, [&](int, size_t lo, size_t hi) { for (size_t t = lo; t < hi; ++t) at[t + 1] = 36 + (int64_t)b->rec[pick[t]].data.size(); });      /* the sizes by all threads ... */
+	host_parallel(host_threads(m, BAM_MIN_N), m, [&](int, size_t lo, size_t hi) { for (size_t t = lo; t < hi; ++t) at[t + 1] = 36 + (int64_t)b->rec[pick[t]].data.size(); });      /* the sizes by all threads ... */
 	for (size_t t = 0; t < m; ++t) at[t + 1] += at[t];                                                                                                     /* ... their sums by one */
 	for (size_t t = m; t < n; ++t) at[t + 1] = at[m];
 	if (out_off) memcpy(out_off, at.data(), sizeof(int64_t) * (n + 1));
 	*n_bytes = at[m];
 	if (!out || cap < at[m]) return nabwa_fail(NABWA_ECAP, "output buffer too small");
-	bam_parallel(m, [&](int, size_t lo, size_t hi) {
+	host_parallel(host_threads(m, BAM_MIN_N), m, [&](int, size_t lo, size_t hi) {
 		for (size_t t = lo; t < hi; ++t) {
 			if (t + 8 < hi) { const BamRec &fr = b->rec[pick[t + 8]]; __builtin_prefetch(fr.data.p); __builtin_prefetch(fr.data.p + 64); __builtin_prefetch(fr.data.p + 128); __builtin_prefetch(fr.data.p + 192); }
 			if (t + 16 < hi) __builtin_prefetch(&b->rec[pick[t + 16]]);

@@ -1,5 +1,5 @@
 // dp_params.hpp -- launch parameters of the alignment kernels (dp_global.hip, dp_wave.hip), shared with the host code that fills them
-// (se_finish.hip).
+// (dp_align.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

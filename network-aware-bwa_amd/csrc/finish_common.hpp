@@ -1,7 +1,6 @@
 // finish_common.hpp -- host pieces shared by the single-end and paired-end finishing chains.
 // Records are nabwa_se_t laid out with a caller-given stride (nabwa_pe_t starts with a nabwa_se_t).
 #pragma once
-#include <sys/time.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -10,10 +9,10 @@
 #include <algorithm>
 #include <memory>
 #include <string>
-#include <thread>
 #include <vector>
 #include "../../include/nabwa.h"
 #include "nabwa_internal.hpp"
+#include "host_util.hpp"
 
 /* ------------------------------------------------------------------ small host pieces */
 
@@ -159,7 +158,6 @@ static inline bool make_md(const nabwa_reference *R, int n_cigar, const uint16_t
 }
 
 
-static inline double fin_now() { struct timeval tv; gettimeofday(&tv, 0); return tv.tv_sec + 1e-6 * tv.tv_usec; }
 static inline nabwa_se_t *rec_at(void *base, size_t stride, int i) { return (nabwa_se_t*)((char*)base + (size_t)i * stride); }
 
 /* bwa_aln2seq_core with set_main (bwase.c:28-46): reservoir choice among the best-score rows with the caller's
@@ -226,22 +224,6 @@ static inline int64_t rec_pos_end(const nabwa_se_t &s)
 	return x;
 }
 
-/* host threads of the finishing chains: slices of independent records */
-static inline int fin_threads(size_t n)
-{
-	int nt = (int)std::thread::hardware_concurrency(); if (nt < 1) nt = 1; if (nt > 16) nt = 16;
-	if (getenv("NABWA_HOST_THREADS")) nt = std::max(1, atoi(getenv("NABWA_HOST_THREADS")));
-	if (n < 4096) nt = 1;
-	return nt;
-}
-template <class F> static inline void fin_parallel(int nt, size_t count, F f)       /* f(slice, lo, hi) */
-{
-	if (nt <= 1) { f(0, (size_t)0, count); return; }
-	std::vector<std::thread> th;
-	for (int t = 0; t < nt; ++t) th.emplace_back([=]() { f(t, count * t / nt, count * (t + 1) / nt); });
-	for (auto &x : th) x.join();
-}
-
 /* Gap refinement of every gapped hit of the batch (main hits and multi hits) as ONE batch of banded global
  * alignments on the GPU (refine_gapped_core, bwase.c:189-237; driver bwase.c:366-381: mate-rescued and
  * unmapped records are skipped).  The host work around the kernel -- finding the jobs, cutting their reference windows out
@@ -252,10 +234,10 @@ static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int
 {
 	const nabwa_reference *R = ix->ref;
 	const bool timing = getenv("NABWA_TIMING") != 0;
-	const double tr0 = fin_now();
-	const int nt = fin_threads((size_t)n);
+	const double tr0 = now_s();
+	const int nt = host_threads((size_t)n, 4096);
 	std::vector<std::vector<RefineJob>> part((size_t)nt);
-	fin_parallel(nt, (size_t)n, [&](int t, size_t lo, size_t hi) {
+	host_parallel(nt, (size_t)n, [&](int t, size_t lo, size_t hi) {
 		std::vector<RefineJob> &v = part[(size_t)t];
 		for (size_t i = lo; i < hi; ++i) {
 			const nabwa_se_t &s = *rec_at(base, stride, (int)i);
@@ -270,7 +252,7 @@ static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int
 	if (jobs.empty()) return NABWA_OK;
 	static const int maq[25] = { 11,-19,-19,-19,-13, -19,11,-19,-19,-13, -19,-19,11,-19,-13, -19,-19,-19,11,-13, -13,-13,-13,-13,-13 };  /* aln_sm_maq */
 	const size_t nj = jobs.size();
-	const int ntj = fin_threads(nj);
+	const int ntj = host_threads(nj, 4096);
 	std::vector<int64_t> ro(nj + 1, 0), qo(nj + 1, 0);
 	for (size_t t = 0; t < nj; ++t) {                      /* the windows' extents (bwase.c:197-209), then where each starts in the batch */
 		RefineJob &J = jobs[t];
@@ -290,7 +272,7 @@ static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int
 	static thread_local Scratch scr_r, scr_q, scr_c;
 	struct { uint8_t *p; uint8_t *data() const { return p; } } rbuf{ scr_r.get((size_t)ro[nj] + 1) }, qbuf{ scr_q.get((size_t)qo[nj] + 1) };
 	rbuf.p[ro[nj]] = 0; qbuf.p[qo[nj]] = 0;
-	fin_parallel(ntj, nj, [&](int, size_t lo_t, size_t hi_t) {
+	host_parallel(ntj, nj, [&](int, size_t lo_t, size_t hi_t) {
 		for (size_t t = lo_t; t < hi_t; ++t) {
 			const RefineJob &J = jobs[t];
 			uint8_t *rb = rbuf.data() + ro[t], *qb = qbuf.data() + qo[t];
@@ -309,16 +291,16 @@ static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int
 			else for (int k = 0; k < J.len; ++k) qb[k] = src[J.len - 1 - k];
 		}
 	});
-	const double tr1 = fin_now();
+	const double tr1 = now_s();
 	const int MAXC = NABWA_MAX_CIGAR;
 	std::vector<int32_t> sc(nj), nc(nj);
 	struct { uint32_t *p; uint32_t *get() const { return p; } uint32_t &operator[](size_t i) const { return p[i]; } } c32{ (uint32_t*)scr_c.get(nj * (size_t)MAXC * 4) };      /* row t: its first nc[t] words are valid */
 	int r = nabwa_global_align(ix->device, (int)nj, ro.data(), rbuf.data(), qo.data(), qbuf.data(), 26, 9, 5, maq, 50,
 							   sc.data(), nc.data(), c32.get(), MAXC);                       /* aln_param_bwa, stdaln.c:227 */
 	if (r != NABWA_OK) return r;
-	const double tr2 = fin_now();
+	const double tr2 = now_s();
 	std::vector<int> bad((size_t)ntj, 0);
-	fin_parallel(ntj, nj, [&](int slice, size_t lo_t, size_t hi_t) {
+	host_parallel(ntj, nj, [&](int slice, size_t lo_t, size_t hi_t) {
 		for (size_t t = lo_t; t < hi_t; ++t) {
 			const RefineJob &J = jobs[t];
 			if (nc[t] > MAXC || nc[t] < 1) { bad[(size_t)slice] = 1; continue; }
@@ -339,7 +321,7 @@ static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int
 		}
 	});
 	for (int b : bad) if (b) return nabwa_fail(NABWA_ECAP, "refined CIGAR longer than NABWA_MAX_CIGAR");
-	if (timing) fprintf(stderr, "[nabwa] refine_batch %zu jobs: jobs + windows %.3f s, nabwa_global_align %.3f s, CIGARs %.3f s\n", nj, tr1 - tr0, tr2 - tr1, fin_now() - tr2);
+	if (timing) fprintf(stderr, "[nabwa] refine_batch %zu jobs: jobs + windows %.3f s, nabwa_global_align %.3f s, CIGARs %.3f s\n", nj, tr1 - tr0, tr2 - tr1, now_s() - tr2);
 	return NABWA_OK;
 }
 

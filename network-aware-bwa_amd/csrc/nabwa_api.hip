@@ -6,7 +6,6 @@
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
-#include <chrono>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -16,6 +15,7 @@
 #include "fm_search.hpp"
 #include "fm_deep.hpp"
 #include "nabwa_internal.hpp"
+#include "host_util.hpp"
 
 extern "C" {
 void nabwa_launch_repack(const uint32_t *w, uint32_t seq_len, uint32_t n_buckets, uint4 *out, hipStream_t s);
@@ -59,9 +59,6 @@ static int fail(int code, const char *fmt, const char *a = "")
 	char buf[512]; snprintf(buf, sizeof buf, fmt, a); g_err = buf; return code;
 }
 int nabwa_fail(int code, const char *fmt, const char *a) { return fail(code, fmt, a); }
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-	char b_[512]; snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-	g_err = b_; return NABWA_ENODEV; } } while (0)
 
 extern "C" const char *nabwa_last_error(void) { return g_err.c_str(); }
 
@@ -105,7 +102,7 @@ static int build_one(nabwa_index *ix, int t_, const uint32_t *words, uint64_t n_
 {
 	uint32_t hdr[5];
 	if (n_words < 5) return fail(NABWA_EIO, "bwt array too short");
-	if (on_device) HIPCHK(hipMemcpy(hdr, words, 20, hipMemcpyDeviceToHost)); else memcpy(hdr, words, 20);
+	if (on_device) HIP_CHECK(hipMemcpy(hdr, words, 20, hipMemcpyDeviceToHost)); else memcpy(hdr, words, 20);
 	DevBwt &B = ix->bwt[t_];
 	memset(&B, 0, sizeof(B));
 	B.primary = hdr[0]; B.L2[0] = 0; B.L2[1] = hdr[1]; B.L2[2] = hdr[2]; B.L2[3] = hdr[3]; B.seq_len = hdr[4];
@@ -116,15 +113,15 @@ static int build_one(nabwa_index *ix, int t_, const uint32_t *words, uint64_t n_
 	uint32_t *raw = 0;
 	const uint32_t *src = words + 5;
 	if (!on_device) {
-		HIPCHK(hipMalloc(&raw, (n_words - 5) * 4));
-		HIPCHK(hipMemcpy(raw, words + 5, (n_words - 5) * 4, hipMemcpyHostToDevice));
+		HIP_CHECK(hipMalloc(&raw, (n_words - 5) * 4));
+		HIP_CHECK(hipMemcpy(raw, words + 5, (n_words - 5) * 4, hipMemcpyHostToDevice));
 		src = raw;
 	}
-	HIPCHK(hipMalloc(&ix->bk[t_], (size_t)B.n_buckets * 64));
+	HIP_CHECK(hipMalloc(&ix->bk[t_], (size_t)B.n_buckets * 64));
 	nabwa_launch_repack(src, B.seq_len, B.n_buckets, ix->bk[t_], 0);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipDeviceSynchronize());
-	if (raw) HIPCHK(hipFree(raw));
+	HIP_CHECK(hipGetLastError());
+	HIP_CHECK(hipDeviceSynchronize());
+	if (raw) HIP_CHECK(hipFree(raw));
 	B.bk = ix->bk[t_];
 	ix->bytes += (uint64_t)B.n_buckets * 64;
 	{	/* interval table, ALL levels 1..T back to back (level t at offset (4^t - 4) / 3): T = floor(log4(seq_len)) + 1 (about a
@@ -138,7 +135,7 @@ static int build_one(nabwa_index *ix, int t_, const uint32_t *words, uint64_t n_
 		if (e) T = atoi(e);
 		if (T > 16) T = 16;
 		size_t free_b = 0, total_b = 0;
-		HIPCHK(hipMemGetInfo(&free_b, &total_b));
+		HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
 		auto table_entries = [](int t) { size_t x = 0; for (int u = 1; u <= t; ++u) x += (size_t)1 << (2 * u); return x; };
 		/* both directions must get the same depth (the search runs without tables otherwise): the first one built decides, leaving
 		 * room for the second; the second takes that depth, and says so loudly if it cannot */
@@ -155,14 +152,14 @@ static int build_one(nabwa_index *ix, int t_, const uint32_t *words, uint64_t n_
 		}
 		if (T >= 1) {
 			const size_t lo_n = table_entries(T);
-			HIPCHK(hipMalloc(&ix->kmer[t_], lo_n * 8));
+			HIP_CHECK(hipMalloc(&ix->kmer[t_], lo_n * 8));
 			uint2 *prev = 0, *cur = ix->kmer[t_];
 			for (int t = 1; t <= T; ++t) {
 				nabwa_launch_kmer_level(&B, prev, cur, (uint64_t)1 << (2 * t), 0);
 				prev = cur; cur += (size_t)1 << (2 * t);
 			}
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipDeviceSynchronize());
+			HIP_CHECK(hipGetLastError());
+			HIP_CHECK(hipDeviceSynchronize());
 			ix->bytes += lo_n * 8;
 			B.kmer = prev; B.kmer_T = (uint32_t)T; B.kmer_lo = ix->kmer[t_]; B.kmer_LW = (uint32_t)T;
 		}
@@ -170,14 +167,14 @@ static int build_one(nabwa_index *ix, int t_, const uint32_t *words, uint64_t n_
 	if (sa_words) {
 		uint32_t sh[7];
 		if (n_sa_words < 7) return fail(NABWA_EIO, "sa array too short");
-		if (on_device) HIPCHK(hipMemcpy(sh, sa_words, 28, hipMemcpyDeviceToHost)); else memcpy(sh, sa_words, 28);
+		if (on_device) HIP_CHECK(hipMemcpy(sh, sa_words, 28, hipMemcpyDeviceToHost)); else memcpy(sh, sa_words, 28);
 		if (sh[0] != B.primary || sh[6] != B.seq_len) return fail(NABWA_EIO, "SA-BWT inconsistency");   /* bwtio.c:169,173 */
 		B.sa_intv = sh[5];
 		B.n_sa = (uint32_t)(((uint64_t)B.seq_len + B.sa_intv) / B.sa_intv);
 		if (n_sa_words - 7 < (uint64_t)B.n_sa - 1) return fail(NABWA_EIO, "sa array shorter than n_sa");
-		HIPCHK(hipMalloc(&ix->sa[t_], (size_t)B.n_sa * 4));
-		HIPCHK(hipMemset(ix->sa[t_], 0xff, 4));
-		HIPCHK(hipMemcpy(ix->sa[t_] + 1, sa_words + 7, (size_t)(B.n_sa - 1) * 4,
+		HIP_CHECK(hipMalloc(&ix->sa[t_], (size_t)B.n_sa * 4));
+		HIP_CHECK(hipMemset(ix->sa[t_], 0xff, 4));
+		HIP_CHECK(hipMemcpy(ix->sa[t_] + 1, sa_words + 7, (size_t)(B.n_sa - 1) * 4,
 						 on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
 		B.sa = ix->sa[t_];
 		ix->bytes += (uint64_t)B.n_sa * 4;
@@ -185,13 +182,13 @@ static int build_one(nabwa_index *ix, int t_, const uint32_t *words, uint64_t n_
 		if (!(tm && atoi(tm) == 0)) {      /* full SA + inverse + text, ~8.3 B per base (NABWA_TEXT_MODE=0: keep the samples only) */
 			const size_t rows = (size_t)B.seq_len + 1, words = ((size_t)B.seq_len + 15) / 16 + 4;
 			uint8_t *tb = 0;
-			HIPCHK(hipMalloc(&ix->sa_full[t_], rows * 4)); HIPCHK(hipMalloc(&ix->isa[t_], rows * 4));
-			HIPCHK(hipMalloc(&ix->text[t_], words * 4)); HIPCHK(hipMalloc(&tb, rows));
+			HIP_CHECK(hipMalloc(&ix->sa_full[t_], rows * 4)); HIP_CHECK(hipMalloc(&ix->isa[t_], rows * 4));
+			HIP_CHECK(hipMalloc(&ix->text[t_], words * 4)); HIP_CHECK(hipMalloc(&tb, rows));
 			nabwa_launch_sa_fill(&B, ix->sa_full[t_], ix->isa[t_], tb, 0);
 			nabwa_launch_text_pack(tb, B.seq_len, (uint32_t)words, ix->text[t_], 0);
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipDeviceSynchronize());
-			HIPCHK(hipFree(tb));
+			HIP_CHECK(hipGetLastError());
+			HIP_CHECK(hipDeviceSynchronize());
+			HIP_CHECK(hipFree(tb));
 			B.sa_full = ix->sa_full[t_]; B.isa = ix->isa[t_]; B.text = ix->text[t_];
 			ix->bytes += rows * 8 + words * 4;
 		}
@@ -323,7 +320,7 @@ extern "C" int nabwa_index_from_arrays(int device, int is_device, const uint32_t
 {
 	if (!out || !bwt0 || !bwt1) return fail(NABWA_EINVAL, "null argument");
 	if (nabwa_device_count() <= device) return fail(NABWA_ENODEV, "no such HIP device");
-	HIPCHK(hipSetDevice(device));
+	HIP_CHECK(hipSetDevice(device));
 	nabwa_index *ix = new nabwa_index();
 	ix->pool = new nabwa_dev_pool();
 	ix->pool->limit = (size_t)env_int("NABWA_POOL_GB", 80) << 30;
@@ -391,25 +388,25 @@ extern "C" void nabwa_index_destroy(nabwa_index_t *ix)
 extern "C" int nabwa_index_export(const nabwa_index_t *ix, int which, int what, uint64_t first, uint64_t n, uint32_t *out)
 {
 	if (!ix || !out || which < 0 || which > 1) return fail(NABWA_EINVAL, "bad argument");
-	HIPCHK(hipSetDevice(ix->device));
+	HIP_CHECK(hipSetDevice(ix->device));
 	const DevBwt &B = ix->bwt[which];
 	if (what == 4) { out[0] = B.kmer_T; return NABWA_OK; }
 	if (what == 3) {
 		if (!B.kmer || first + n > (1ull << (2 * B.kmer_T))) return fail(NABWA_EINVAL, "no interval table / out of range");
-		HIPCHK(hipMemcpy(out, B.kmer + first, n * 8, hipMemcpyDeviceToHost));
+		HIP_CHECK(hipMemcpy(out, B.kmer + first, n * 8, hipMemcpyDeviceToHost));
 		return NABWA_OK;
 	}
 	if (!B.sa_full) return fail(NABWA_EINVAL, "index has no text-mode companions (no SA given, or NABWA_TEXT_MODE=0)");
 	if (what == 0 || what == 1) {
 		if (first + n > (uint64_t)B.seq_len + 1) return fail(NABWA_EINVAL, "out of range");
-		HIPCHK(hipMemcpy(out, (what ? B.isa : B.sa_full) + first, n * 4, hipMemcpyDeviceToHost));
+		HIP_CHECK(hipMemcpy(out, (what ? B.isa : B.sa_full) + first, n * 4, hipMemcpyDeviceToHost));
 		return NABWA_OK;
 	}
 	if (what == 2) {
 		if (first + n > (uint64_t)B.seq_len) return fail(NABWA_EINVAL, "out of range");
 		const uint64_t w0 = first / 16, w1 = (first + n + 15) / 16;
 		std::vector<uint32_t> w(w1 - w0);
-		HIPCHK(hipMemcpy(w.data(), B.text + w0, (w1 - w0) * 4, hipMemcpyDeviceToHost));
+		HIP_CHECK(hipMemcpy(w.data(), B.text + w0, (w1 - w0) * 4, hipMemcpyDeviceToHost));
 		for (uint64_t j = 0; j < n; ++j) { const uint64_t p = first + j; out[j] = w[p / 16 - w0] >> (2 * (p & 15)) & 3u; }
 		return NABWA_OK;
 	}
@@ -486,18 +483,17 @@ extern "C" void nabwa_batch_destroy(nabwa_batch_t *b)
 	delete b;
 }
 
-#define BCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-	char b_[512]; snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-	g_err = b_; nabwa_batch_destroy(b); return NABWA_ENODEV; } } while (0)
+/* HIP_CHECK that also frees the half-built batch */
+#define BCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { \
+	const int r_ = nabwa_hip_fail(e_, #x, __FILE__, __LINE__); nabwa_batch_destroy(b); return r_; } } while (0)
 
 extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, const int64_t *off,
 								  const uint8_t *seq, const uint8_t *rseq, int per_read, nabwa_batch_t **out)
 {
 	if (!ix || !opt || !off || !out || n < 0 || (n && (!seq || !rseq))) return fail(NABWA_EINVAL, "null argument");
-	HIPCHK(hipSetDevice(ix->device));
+	HIP_CHECK(hipSetDevice(ix->device));
 	const bool timing = getenv("NABWA_TIMING") != 0;
-	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-	const double tc0 = now();
+	const double tc0 = now_s();
 	// ---- per-read option derivation, on the host in double (bwtaln.c:102-106,125)
 	// One threaded pass over the read boundaries: validity, the lengths that occur, the padded size.  Everything per read
 	// that follows from its length alone (max_diff, max_gapo) is a table over lengths, applied on the device.
@@ -507,23 +503,17 @@ extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 		const int NT = n >= (1 << 20) ? 4 : 1;
 		struct Part { int mx = 0, mn = 65535; int64_t padded = 0; bool bad = false; std::vector<uint8_t> seen; };
 		std::vector<Part> part(NT);
-		std::vector<std::thread> th;
-		for (int t = 0; t < NT; ++t) {
-			part[t].seen.assign(65536, 0);
-			auto work = [&, t]() {
-				Part &q = part[t];
-				const int64_t i0 = (int64_t)n * t / NT, i1 = (int64_t)n * (t + 1) / NT;
-				for (int64_t i = i0; i < i1; ++i) {
-					const int64_t L = off[i + 1] - off[i];
-					if (L < 0 || L > 65535) { q.bad = true; continue; }
-					q.seen[L] = 1; q.padded += (L + 15) / 16 * 16;
-					if (L > q.mx) q.mx = (int)L;
-					if (L < q.mn) q.mn = (int)L;
-				}
-			};
-			if (NT == 1) work(); else th.emplace_back(work);
-		}
-		for (auto &x : th) x.join();
+		for (Part &q : part) q.seen.assign(65536, 0);
+		host_parallel(NT, (size_t)n, [&](int t, size_t i0, size_t i1) {
+			Part &q = part[t];
+			for (size_t i = i0; i < i1; ++i) {
+				const int64_t L = off[i + 1] - off[i];
+				if (L < 0 || L > 65535) { q.bad = true; continue; }
+				q.seen[L] = 1; q.padded += (L + 15) / 16 * 16;
+				if (L > q.mx) q.mx = (int)L;
+				if (L < q.mn) q.mn = (int)L;
+			}
+		});
 		for (auto &q : part) {
 			bad_len |= q.bad; padded_total += q.padded;
 			if (q.mx > max_len) max_len = q.mx;
@@ -577,7 +567,7 @@ extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 	 * the only child of its own score (fm_deep_body.hpp), so every penalty has to be positive (-M / -O / -E 0 have no use in practice) */
 	if (opt->s_mm < 1 || opt->s_gapo < 1 || opt->s_gape < 1) return fail(NABWA_EINVAL, "s_mm, s_gapo and s_gape must be >= 1 (-M / -O / -E 0 are not supported)");
 
-	const double tc1 = now();
+	const double tc1 = now_s();
 	nabwa_batch *b = new nabwa_batch();
 	memset(b, 0, sizeof(*b));
 	b->ix = ix; b->opt = *opt; b->n = n; b->deep_only = deep_only ? 1 : 0;
@@ -606,9 +596,9 @@ extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 		uint8_t *raw_s = 0, *raw_r = 0; int64_t *raw_off = 0;
 		BCHK(pool_malloc(b->ix, (void**)&raw_s, nb)); BCHK(pool_malloc(b->ix, (void**)&raw_r, nb)); BCHK(pool_malloc(b->ix, (void**)&raw_off, (size_t)(n + 1) * 8));
 		const UploadJob jobs[3] = { { raw_s, seq, (size_t)off[n] }, { raw_r, rseq, (size_t)off[n] }, { raw_off, off, (size_t)(n + 1) * 8 } };
-		const double tu0 = now();
+		const double tu0 = now_s();
 		BCHK(staged_upload(ix, jobs, 3));
-		if (timing) fprintf(stderr, "[nabwa] upload of %.2f GB: %.3f s (%.3f s into batch_create)\n", 2e-9 * (double)off[n], now() - tu0, tu0 - tc0);
+		if (timing) fprintf(stderr, "[nabwa] upload of %.2f GB: %.3f s (%.3f s into batch_create)\n", 2e-9 * (double)off[n], now_s() - tu0, tu0 - tc0);
 		// padded starts: exclusive scan of the padded lengths, on the device
 		int64_t *plen = 0; void *d_tmp = 0; size_t tmp_bytes = 0; uint8_t *d_tab = 0;
 		BCHK(pool_malloc(b->ix, (void**)&plen, (size_t)(n + 1) * 8));
@@ -623,12 +613,12 @@ extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 							   ix->bwt[0].kmer_T == ix->bwt[1].kmer_T ? (int)ix->bwt[0].kmer_T : 0, opt->seed_len, b->d_pack, b->pack_stride,
 							   d_tab, d_tab + max_len + 1, b->d_md, b->d_mg, b->stream);
 		BCHK(hipStreamSynchronize(b->stream));
-		if (timing) fprintf(stderr, "[nabwa] re-layout kernel done %.3f s into batch_create\n", now() - tc0);
+		if (timing) fprintf(stderr, "[nabwa] re-layout kernel done %.3f s into batch_create\n", now_s() - tc0);
 		BCHK(pool_free(b->ix, raw_s)); BCHK(pool_free(b->ix, raw_r)); BCHK(pool_free(b->ix, raw_off));
 		BCHK(pool_free(b->ix, plen)); BCHK(pool_free(b->ix, d_tmp)); BCHK(pool_free(b->ix, d_tab));
 	}
 
-	const double tc2 = now();
+	const double tc2 = now_s();
 	SearchParams &P = b->P;
 	memset(&P, 0, sizeof(P));
 	P.bwt[0] = ix->bwt[0]; P.bwt[1] = ix->bwt[1];
@@ -696,42 +686,42 @@ extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 	P.scratch = b->d_scratch; P.n_aln = b->d_naln; P.max_ent = b->d_maxent; P.status = b->d_status; P.aln = b->d_aln;
 	P.work_counter = b->d_counter;
 	*out = b;
-	if (timing) fprintf(stderr, "[nabwa] batch_create %d reads: host option derivation %.3f s, read upload + device layout %.3f s, working buffers %.3f s\n", n, tc1 - tc0, tc2 - tc1, now() - tc2);
+	if (timing) fprintf(stderr, "[nabwa] batch_create %d reads: host option derivation %.3f s, read upload + device layout %.3f s, working buffers %.3f s\n", n, tc1 - tc0, tc2 - tc1, now_s() - tc2);
 	return NABWA_OK;
 }
 
 extern "C" int nabwa_batch_run(nabwa_batch_t *b)
 {
 	if (!b) return fail(NABWA_EINVAL, "null batch");
-	HIPCHK(hipSetDevice(b->ix->device));
+	HIP_CHECK(hipSetDevice(b->ix->device));
 	b->unresolved = 0;
 	if (b->n == 0) return NABWA_OK;
 	if (b->n_grown) {          /* row blocks of the previous run's longest hit lists: that run's results are gone with this one */
-		HIPCHK(hipStreamSynchronize(b->stream));
-		for (int t = 0; t < b->n_grown; ++t) HIPCHK(pool_free(b->ix, b->grown[t]));
+		HIP_CHECK(hipStreamSynchronize(b->stream));
+		for (int t = 0; t < b->n_grown; ++t) HIP_CHECK(pool_free(b->ix, b->grown[t]));
 		b->n_grown = 0; b->grown_used = 0;
 	}
-	HIPCHK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
-	HIPCHK(hipMemsetAsync(b->d_novf, 0, 4, b->stream));
-	HIPCHK(hipEventRecord(b->evw, b->stream));
+	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
+	HIP_CHECK(hipMemsetAsync(b->d_novf, 0, 4, b->stream));
+	HIP_CHECK(hipEventRecord(b->evw, b->stream));
 	SearchParams PW = b->P; PW.ids = 0; PW.rd_cls = b->class_sort ? b->d_cls : 0;
 	nabwa_launch_fm_width(&PW, b->n_blocks_w, b->stream);
 	if (b->class_sort) {      /* work order of the search: reads with an exact occurrence first, in lockstep waves */
-		HIPCHK(hipMemsetAsync(b->d_ncls, 0, 64, b->stream));
+		HIP_CHECK(hipMemsetAsync(b->d_ncls, 0, 64, b->stream));
 		nabwa_launch_partition(b->n, b->d_cls, b->d_perm, b->d_ncls, b->stream);
 	}
-	HIPCHK(hipEventRecord(b->ev0, b->stream));
+	HIP_CHECK(hipEventRecord(b->ev0, b->stream));
 	SearchParams PS = b->P; PS.ids = b->class_sort ? b->d_perm : 0; PS.n_sync = b->class_sort ? b->d_ncls + 10 : 0;
 	if (!b->deep_only) nabwa_launch_fm_search(&PS, b->n_blocks, b->stream);
 	else {      /* option blocks the first-pass kernel's compact entries cannot hold: every read goes to kernel D */
-		HIPCHK(hipMemsetAsync(b->d_status, NABWA_ST_OVERFLOW, b->n, b->stream));
-		HIPCHK(hipMemsetAsync(b->d_naln, 0, (size_t)b->n * 4, b->stream));
+		HIP_CHECK(hipMemsetAsync(b->d_status, NABWA_ST_OVERFLOW, b->n, b->stream));
+		HIP_CHECK(hipMemsetAsync(b->d_naln, 0, (size_t)b->n * 4, b->stream));
 	}
-	HIPCHK(hipEventRecord(b->ev1, b->stream));
+	HIP_CHECK(hipEventRecord(b->ev1, b->stream));
 	/* the reads the first pass hands on, in the order kernel D should start them (largest-looking searches first) */
 	if (b->class_sort && env_int("NABWA_DEEP_ORDER", 1)) nabwa_launch_collect_keyed(b->n, b->d_status, b->d_ovf_ids, b->d_novf, NABWA_ST_OVERFLOW, b->d_cls, b->d_md, 7, b->d_naln, b->P.aln_cap, b->stream);
 	else nabwa_launch_collect(b->n, b->d_status, b->d_ovf_ids, b->d_novf, NABWA_ST_OVERFLOW, b->stream);
-	HIPCHK(hipGetLastError());
+	HIP_CHECK(hipGetLastError());
 	b->ran = 1;
 	return NABWA_OK;
 }
@@ -739,14 +729,14 @@ extern "C" int nabwa_batch_run(nabwa_batch_t *b)
 extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 {
 	if (!b) return fail(NABWA_EINVAL, "null batch");
-	HIPCHK(hipSetDevice(b->ix->device));
+	HIP_CHECK(hipSetDevice(b->ix->device));
 	if (n_second_pass) *n_second_pass = 0;
 	if (b->n == 0) return NABWA_OK;
 	unsigned int novf = 0;
-	HIPCHK(hipMemcpyAsync(&novf, b->d_novf, 4, hipMemcpyDeviceToHost, b->stream));
-	HIPCHK(hipStreamSynchronize(b->stream));
-	HIPCHK(hipEventElapsedTime(&b->last_ms, b->ev0, b->ev1));
-	HIPCHK(hipEventElapsedTime(&b->last_ms_w, b->evw, b->ev0));
+	HIP_CHECK(hipMemcpyAsync(&novf, b->d_novf, 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipStreamSynchronize(b->stream));
+	HIP_CHECK(hipEventElapsedTime(&b->last_ms, b->ev0, b->ev1));
+	HIP_CHECK(hipEventElapsedTime(&b->last_ms_w, b->evw, b->ev0));
 	if (n_second_pass) *n_second_pass = (int)novf;
 	if (novf == 0) return NABWA_OK;
 	// ---- the flagged reads go to kernel D (fm_deep_body.hpp): one search per wavefront, arenas paged out of one pool.
@@ -754,7 +744,6 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 	// ancient-DNA workload, the launch as long as its longest search.)  Optionally the first-pass kernel runs once more
 	// before that with the largest arena its 16-bit links address (NABWA_TIER_A=1).
 	const bool timing = getenv("NABWA_TIMING") != 0;
-	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	unsigned int cur = novf;
 	b->deep_ran = 0; b->last_ms_deep = 0.f;
 	// the kernel-W records of the listed reads again: a search edits them in place (gap_shadow)
@@ -770,14 +759,14 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 		nabwa_launch_fm_width(&QW, (int)bw2, b->stream);
 	};
 	auto recollect = [&](int which, unsigned int *left) -> int {
-		HIPCHK(hipMemsetAsync(b->d_novf, 0, 4, b->stream));
+		HIP_CHECK(hipMemsetAsync(b->d_novf, 0, 4, b->stream));
 		nabwa_launch_collect(b->n, b->d_status, b->d_ovf_ids, b->d_novf, which, b->stream);
-		HIPCHK(hipMemcpyAsync(left, b->d_novf, 4, hipMemcpyDeviceToHost, b->stream));
-		HIPCHK(hipStreamSynchronize(b->stream));
+		HIP_CHECK(hipMemcpyAsync(left, b->d_novf, 4, hipMemcpyDeviceToHost, b->stream));
+		HIP_CHECK(hipStreamSynchronize(b->stream));
 		return NABWA_OK;
 	};
 	if (env_int("NABWA_TIER_A", 0) && b->P.cap < 65534 && b->deep_only == 0) {
-		const double tt0 = now();
+		const double tt0 = now_s();
 		SearchParams Q = b->P;
 		layout(Q, 65534u, b->max_len, b->opt.seed_len, b->P.NS);
 		long blocks = ((long)cur + NABWA_SEARCH_BLOCK - 1) / NABWA_SEARCH_BLOCK;
@@ -786,25 +775,25 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 		if (blocks > fit) blocks = fit < 1 ? 1 : fit;
 		const size_t need = (size_t)blocks * NABWA_SEARCH_BLOCK * Q.lane_stride;
 		if (b->scratch2_bytes < need) {
-			if (b->d_scratch2) { HIPCHK(pool_free(b->ix, b->d_scratch2)); b->d_scratch2 = 0; b->scratch2_bytes = 0; }
-			HIPCHK(pool_malloc(b->ix, (void**)&b->d_scratch2, need));
+			if (b->d_scratch2) { HIP_CHECK(pool_free(b->ix, b->d_scratch2)); b->d_scratch2 = 0; b->scratch2_bytes = 0; }
+			HIP_CHECK(pool_malloc(b->ix, (void**)&b->d_scratch2, need));
 			b->scratch2_bytes = need;
 		}
 		Q.scratch = b->d_scratch2; Q.ids = b->d_ovf_ids; Q.n = (int)cur; Q.n_sync = 0; Q.w_sync = 0;
 		rebuild_widths(Q, cur, false);
-		HIPCHK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
+		HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
 		nabwa_launch_fm_search(&Q, (int)blocks, b->stream);
-		HIPCHK(hipGetLastError());
+		HIP_CHECK(hipGetLastError());
 		unsigned int left = 0;
 		int r = recollect(NABWA_ST_OVERFLOW, &left);
 		if (r != NABWA_OK) return r;
-		if (timing) fprintf(stderr, "[nabwa] first-pass kernel again, arena of 65534 entries: %u reads on %ld blocks, %u left, %.3f s\n", cur, blocks, left, now() - tt0);
+		if (timing) fprintf(stderr, "[nabwa] first-pass kernel again, arena of 65534 entries: %u reads on %ld blocks, %u left, %.3f s\n", cur, blocks, left, now_s() - tt0);
 		cur = left;
 	}
 	if (cur) {
 		/* a chain's matching child must be the only child of its own score (fm_deep_body.hpp) */
 		if (b->opt.s_mm < 1 || b->opt.s_gapo < 1 || b->opt.s_gape < 1) return fail(NABWA_EINVAL, "deep searches need s_mm, s_gapo, s_gape >= 1");
-		const double tt0 = now();
+		const double tt0 = now_s();
 		const uint32_t NS = b->NS_wide;
 		// rows of the wide result arrays for the reads that are left
 		if (b->n2 < (int)cur || b->aln_cap2 != env_int("NABWA_ALNCAP2", 1024)) {
@@ -813,15 +802,15 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 			b->d_naln2 = b->d_maxent2 = 0; b->d_status2 = 0; b->d_aln2 = 0;
 			b->aln_cap2 = env_int("NABWA_ALNCAP2", 1024);
 			if (b->aln_cap2 < 1) b->aln_cap2 = 1;
-			HIPCHK(pool_malloc(b->ix, (void**)&b->d_naln2, (size_t)cur * 4)); HIPCHK(pool_malloc(b->ix, (void**)&b->d_maxent2, (size_t)cur * 4));
-			HIPCHK(pool_malloc(b->ix, (void**)&b->d_status2, cur)); HIPCHK(pool_malloc(b->ix, (void**)&b->d_aln2, (size_t)cur * b->aln_cap2 * 16));
+			HIP_CHECK(pool_malloc(b->ix, (void**)&b->d_naln2, (size_t)cur * 4)); HIP_CHECK(pool_malloc(b->ix, (void**)&b->d_maxent2, (size_t)cur * 4));
+			HIP_CHECK(pool_malloc(b->ix, (void**)&b->d_status2, cur)); HIP_CHECK(pool_malloc(b->ix, (void**)&b->d_aln2, (size_t)cur * b->aln_cap2 * 16));
 			b->n2 = (int)cur;
 		}
 		nabwa_launch_assign_slots((int)cur, b->d_ovf_ids, b->d_wide_idx, b->stream);
 		// kernel D's launch shape and pool size: worked out once per batch (device queries cost as much as a small launch)
 		if (!b->deep_cfg) {
 			hipDeviceProp_t prop;
-			HIPCHK(hipGetDeviceProperties(&prop, b->ix->device));
+			HIP_CHECK(hipGetDeviceProperties(&prop, b->ix->device));
 			uint32_t K = (uint32_t)env_int("NABWA_DEEP_STAGE", (int)DEEP_STAGE_MAX);
 			if (K < 1u) K = 1u;
 			if (K > DEEP_STAGE_MAX) K = DEEP_STAGE_MAX;
@@ -835,7 +824,7 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 			size_t budget = (size_t)env_int("NABWA_DEEP_GB", 32) << 30;
 			{
 				size_t fr = 0, tot = 0;
-				HIPCHK(hipMemGetInfo(&fr, &tot));
+				HIP_CHECK(hipMemGetInfo(&fr, &tot));
 				size_t avail = fr;
 				{ std::lock_guard<std::mutex> lk(b->ix->pool->mu); avail += b->ix->pool->idle_bytes; }
 				avail = avail > ((size_t)6 << 30) ? avail - ((size_t)6 << 30) : ((size_t)64 << 20);
@@ -858,22 +847,22 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 		long n_waves = b->deep_waves_max;
 		if (n_waves > (long)cur) n_waves = (long)cur;
 		if (b->deep_pages < n_pages) {
-			if (b->d_pages) { HIPCHK(pool_free(b->ix, b->d_pages)); HIPCHK(pool_free(b->ix, b->d_page_prev)); b->d_pages = 0; b->d_page_prev = 0; b->deep_pages = 0; }
-			HIPCHK(pool_malloc(b->ix, (void**)&b->d_pages, n_pages * DEEP_PAGE * 16)); HIPCHK(pool_malloc(b->ix, (void**)&b->d_page_prev, n_pages * 4));
+			if (b->d_pages) { HIP_CHECK(pool_free(b->ix, b->d_pages)); HIP_CHECK(pool_free(b->ix, b->d_page_prev)); b->d_pages = 0; b->d_page_prev = 0; b->deep_pages = 0; }
+			HIP_CHECK(pool_malloc(b->ix, (void**)&b->d_pages, n_pages * DEEP_PAGE * 16)); HIP_CHECK(pool_malloc(b->ix, (void**)&b->d_page_prev, n_pages * 4));
 			b->deep_pages = n_pages;
 		}
 		const size_t own_words = (size_t)n_waves * 2 * cap_pages, stage_ent = (size_t)n_waves * 64 * K * 4;
 		if (b->deep_own_words < own_words) {
-			if (b->d_deep_own) HIPCHK(pool_free(b->ix, b->d_deep_own));
+			if (b->d_deep_own) HIP_CHECK(pool_free(b->ix, b->d_deep_own));
 			b->d_deep_own = 0; b->deep_own_words = 0;
-			HIPCHK(pool_malloc(b->ix, (void**)&b->d_deep_own, own_words * 4)); b->deep_own_words = own_words;
+			HIP_CHECK(pool_malloc(b->ix, (void**)&b->d_deep_own, own_words * 4)); b->deep_own_words = own_words;
 		}
 		if (b->deep_stage_ent < stage_ent) {
-			if (b->d_deep_stage) HIPCHK(pool_free(b->ix, b->d_deep_stage));
+			if (b->d_deep_stage) HIP_CHECK(pool_free(b->ix, b->d_deep_stage));
 			b->d_deep_stage = 0; b->deep_stage_ent = 0;
-			HIPCHK(pool_malloc(b->ix, (void**)&b->d_deep_stage, stage_ent * 16)); b->deep_stage_ent = stage_ent;
+			HIP_CHECK(pool_malloc(b->ix, (void**)&b->d_deep_stage, stage_ent * 16)); b->deep_stage_ent = stage_ent;
 		}
-		if (!b->d_deep_ctr) HIPCHK(pool_malloc(b->ix, (void**)&b->d_deep_ctr, 1024));
+		if (!b->d_deep_ctr) HIP_CHECK(pool_malloc(b->ix, (void**)&b->d_deep_ctr, 1024));
 		DeepParams D;
 		memset(&D, 0, sizeof(D));
 		D.S = b->P;
@@ -907,12 +896,12 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 		if (dump_path) {
 			D.stats = b->d_deep_ctr;
 			dump_ids.resize(cur); dump_trips.resize(b->n); dump_naln.resize(b->n);
-			HIPCHK(hipStreamSynchronize(b->stream));
-			HIPCHK(hipMemcpy(dump_ids.data(), b->d_ovf_ids, (size_t)cur * 4, hipMemcpyDeviceToHost));
-			HIPCHK(hipMemcpy(dump_trips.data(), b->d_maxent, (size_t)b->n * 4, hipMemcpyDeviceToHost));
-			HIPCHK(hipMemcpy(dump_naln.data(), b->d_naln, (size_t)b->n * 4, hipMemcpyDeviceToHost));
-			HIPCHK(pool_malloc(b->ix, (void**)&d_rounds, (size_t)cur * 4));
-			HIPCHK(hipMemsetAsync(d_rounds, 0, (size_t)cur * 4, b->stream));
+			HIP_CHECK(hipStreamSynchronize(b->stream));
+			HIP_CHECK(hipMemcpy(dump_ids.data(), b->d_ovf_ids, (size_t)cur * 4, hipMemcpyDeviceToHost));
+			HIP_CHECK(hipMemcpy(dump_trips.data(), b->d_maxent, (size_t)b->n * 4, hipMemcpyDeviceToHost));
+			HIP_CHECK(hipMemcpy(dump_naln.data(), b->d_naln, (size_t)b->n * 4, hipMemcpyDeviceToHost));
+			HIP_CHECK(pool_malloc(b->ix, (void**)&d_rounds, (size_t)cur * 4));
+			HIP_CHECK(hipMemsetAsync(d_rounds, 0, (size_t)cur * 4, b->stream));
 			D.rounds_out = d_rounds;
 		}
 		// pass 1: as many waves as fit the CUs, pages on demand; pass 2 (only if the pool ran dry under some reads): as many
@@ -928,22 +917,22 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 			if (waves > (long)todo) waves = (long)todo;
 			D.S.n = (int)todo; D.own_cap = (uint32_t)own_cap;
 			rebuild_widths(D.S, todo, pass == 0);
-			HIPCHK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
-			HIPCHK(hipMemsetAsync(b->d_deep_ctr, 0, 1024, b->stream));
+			HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
+			HIP_CHECK(hipMemsetAsync(b->d_deep_ctr, 0, 1024, b->stream));
 			D.S.work_counter = b->d_counter;
-			if (pass == 0) HIPCHK(hipEventRecord(b->evd0, b->stream));
+			if (pass == 0) HIP_CHECK(hipEventRecord(b->evd0, b->stream));
 			nabwa_launch_fm_deep(&D, (int)waves, b->stream);
-			if (pass == 0) HIPCHK(hipEventRecord(b->evd1, b->stream));
+			if (pass == 0) HIP_CHECK(hipEventRecord(b->evd1, b->stream));
 			nabwa_launch_scatter_wide((int)todo, b->d_ovf_ids, b->d_naln2, b->d_maxent2, b->d_status2,
 									  b->d_naln, b->d_maxent, b->d_status, b->d_wide_idx, b->stream);
-			HIPCHK(hipGetLastError());
+			HIP_CHECK(hipGetLastError());
 			int r = recollect(NABWA_ST_POOL, &n_pool);
 			if (r != NABWA_OK) return r;
 			if (timing) {
 				unsigned long long st[128];
-				HIPCHK(hipMemcpy(st, b->d_deep_ctr, 1024, hipMemcpyDeviceToHost));
+				HIP_CHECK(hipMemcpy(st, b->d_deep_ctr, 1024, hipMemcpyDeviceToHost));
 				fprintf(stderr, "[nabwa] kernel D%s: %u reads on %ld waves (%zu pages of 4 KB, %u handed out), %u left for the guaranteed pass, %.3f s; rounds %llu, chains run %llu / committed %llu, wave-steps %llu, careful rounds %llu, exact tails: %llu rank steps, %llu finished by text; longest read %.3f s / %llu rounds, all reads %.1f wave-s, longest wave %.3f s\n",
-						pass ? " (guaranteed pass)" : "", todo, waves, n_pages, (unsigned int)(st[8] & 0xffffffffu), n_pool, now() - tt0, st[0], st[1], st[2], st[3], st[4], st[6], st[7], st[10] * 1e-8, st[11], st[12] * 1e-8, st[13] * 1e-8);
+						pass ? " (guaranteed pass)" : "", todo, waves, n_pages, (unsigned int)(st[8] & 0xffffffffu), n_pool, now_s() - tt0, st[0], st[1], st[2], st[3], st[4], st[6], st[7], st[10] * 1e-8, st[11], st[12] * 1e-8, st[13] * 1e-8);
 				fprintf(stderr, "[nabwa] kernel D phases (wave-s): pop %.1f, chains %.1f, exact tails %.1f (%llu turns), commit %.1f, hit bookkeeping %.1f; active lanes per chain step %.1f\n",
 						st[16] * 1e-8, st[17] * 1e-8, st[18] * 1e-8, st[21], st[19] * 1e-8, st[20] * 1e-8, st[3] ? (double)st[22] / (double)st[3] : 0.0);
 				fprintf(stderr, "[nabwa] kernel D lane-steps %llu: pruned at the pop %llu, expansions %llu (in key form %llu, on two buckets %llu), records %llu, children stored %llu; key-form tails / hits %llu; expansions without a difference allowed: %llu in key form, %llu on one row, %llu on several\n",
@@ -964,10 +953,10 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 			if (pass == 0 && dump_path) {
 				std::vector<uint32_t> rounds(dump_ids.size());
 				std::vector<uint8_t> cls((size_t)b->n * 2), md((size_t)b->n); std::vector<int32_t> lens((size_t)b->n);
-				HIPCHK(hipMemcpy(rounds.data(), d_rounds, rounds.size() * 4, hipMemcpyDeviceToHost));
-				if (b->d_cls) HIPCHK(hipMemcpy(cls.data(), b->d_cls, cls.size(), hipMemcpyDeviceToHost));
-				HIPCHK(hipMemcpy(md.data(), b->d_md, md.size(), hipMemcpyDeviceToHost));
-				HIPCHK(hipMemcpy(lens.data(), b->d_len, lens.size() * 4, hipMemcpyDeviceToHost));
+				HIP_CHECK(hipMemcpy(rounds.data(), d_rounds, rounds.size() * 4, hipMemcpyDeviceToHost));
+				if (b->d_cls) HIP_CHECK(hipMemcpy(cls.data(), b->d_cls, cls.size(), hipMemcpyDeviceToHost));
+				HIP_CHECK(hipMemcpy(md.data(), b->d_md, md.size(), hipMemcpyDeviceToHost));
+				HIP_CHECK(hipMemcpy(lens.data(), b->d_len, lens.size() * 4, hipMemcpyDeviceToHost));
 				FILE *f = fopen(dump_path, "wb");
 				if (f) {
 					for (size_t t = 0; t < dump_ids.size(); ++t) {
@@ -979,16 +968,16 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 				}
 				{	/* <file>.all: per read of the batch its two restart classes and whether kernel S handed it on */
 					std::vector<uint8_t> st((size_t)b->n);
-					HIPCHK(hipMemcpy(st.data(), b->d_status, st.size(), hipMemcpyDeviceToHost));
+					HIP_CHECK(hipMemcpy(st.data(), b->d_status, st.size(), hipMemcpyDeviceToHost));
 					FILE *g = fopen((std::string(dump_path) + ".all").c_str(), "wb");
 					if (g) { for (int i = 0; i < b->n; ++i) { const uint8_t row[4] = { cls[2 * (size_t)i], cls[2 * (size_t)i + 1], (uint8_t)(st[i] != NABWA_ST_OK), md[i] }; fwrite(row, 1, 4, g); } fclose(g); }
 				}
-				HIPCHK(pool_free(b->ix, d_rounds)); D.rounds_out = 0;
+				HIP_CHECK(pool_free(b->ix, d_rounds)); D.rounds_out = 0;
 			}
 			todo = n_pool;
 		}
 		b->deep_ran = 1;
-		HIPCHK(hipEventElapsedTime(&b->last_ms_deep, b->evd0, b->evd1));
+		HIP_CHECK(hipEventElapsedTime(&b->last_ms_deep, b->evd0, b->evd1));
 		if (todo) { b->unresolved = (int)todo; return fail(NABWA_ENOMEM, "kernel D: the page pool cannot hold one worst-case search (raise NABWA_DEEP_GB or lower max_entries)"); }
 		unsigned int n_hit = 0;
 		int r = recollect(NABWA_ST_HITCAP, &n_hit);
@@ -1002,14 +991,14 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 			const size_t bytes = (size_t)n_hit * cap3 * 16;
 			if (bytes > ((size_t)env_int("NABWA_HIT_GROW_GB", 8) << 30) || cap3 > 0x7fffffffu) break;
 			uint8_t *raw = 0; int32_t *n3 = 0, *m3 = 0; uint8_t *s3 = 0;
-			HIPCHK(pool_malloc(b->ix, (void**)&raw, bytes));
+			HIP_CHECK(pool_malloc(b->ix, (void**)&raw, bytes));
 			b->grown[b->n_grown++] = raw;
-			HIPCHK(pool_malloc(b->ix, (void**)&n3, (size_t)n_hit * 4)); HIPCHK(pool_malloc(b->ix, (void**)&m3, (size_t)n_hit * 4)); HIPCHK(pool_malloc(b->ix, (void**)&s3, n_hit));
+			HIP_CHECK(pool_malloc(b->ix, (void**)&n3, (size_t)n_hit * 4)); HIP_CHECK(pool_malloc(b->ix, (void**)&m3, (size_t)n_hit * 4)); HIP_CHECK(pool_malloc(b->ix, (void**)&s3, n_hit));
 			uint8_t *const base = raw;
 			if (!b->d_grown_tab || (b->grown_used == 0 && b->grown_cap < 8 * (int)n_hit + 8)) {      /* every step resolves or repeats reads of the first step's list */
-				if (b->d_grown_tab) { HIPCHK(hipStreamSynchronize(b->stream)); HIPCHK(pool_free(b->ix, (void*)b->d_grown_tab)); b->d_grown_tab = 0; }
+				if (b->d_grown_tab) { HIP_CHECK(hipStreamSynchronize(b->stream)); HIP_CHECK(pool_free(b->ix, (void*)b->d_grown_tab)); b->d_grown_tab = 0; }
 				b->grown_cap = 8 * (int)n_hit + 8;
-				HIPCHK(pool_malloc(b->ix, (void**)&b->d_grown_tab, (size_t)b->grown_cap * 8));
+				HIP_CHECK(pool_malloc(b->ix, (void**)&b->d_grown_tab, (size_t)b->grown_cap * 8));
 				b->grown_used = 0;
 			}
 			if (b->grown_used + (int)n_hit > b->grown_cap) break;
@@ -1022,15 +1011,15 @@ extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 			if (waves > (long)n_hit) waves = (long)n_hit;
 			G.S.n = (int)n_hit; G.own_cap = (uint32_t)cap_pages;
 			rebuild_widths(G.S, n_hit, false);
-			HIPCHK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
-			HIPCHK(hipMemsetAsync(b->d_deep_ctr, 0, 1024, b->stream));
+			HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
+			HIP_CHECK(hipMemsetAsync(b->d_deep_ctr, 0, 1024, b->stream));
 			G.S.work_counter = b->d_counter;
 			nabwa_launch_fm_deep(&G, (int)waves, b->stream);
 			nabwa_launch_scatter_grown((int)n_hit, b->d_ovf_ids, n3, m3, s3, b->d_naln, b->d_maxent, b->d_status, b->d_wide_idx, (const uint4*)base, cap3, b->d_grown_tab, b->grown_used, b->stream);
 			b->grown_used += (int)n_hit;
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipStreamSynchronize(b->stream));
-			HIPCHK(pool_free(b->ix, n3)); HIPCHK(pool_free(b->ix, m3)); HIPCHK(pool_free(b->ix, s3));
+			HIP_CHECK(hipGetLastError());
+			HIP_CHECK(hipStreamSynchronize(b->stream));
+			HIP_CHECK(pool_free(b->ix, n3)); HIP_CHECK(pool_free(b->ix, m3)); HIP_CHECK(pool_free(b->ix, s3));
 			if (timing) fprintf(stderr, "[nabwa] kernel D, hit lists beyond %d rows: %u reads searched again with %zu rows each\n", b->aln_cap2, n_hit, cap3);
 			r = recollect(NABWA_ST_HITCAP, &n_hit);
 			if (r != NABWA_OK) return r;
@@ -1050,8 +1039,8 @@ extern "C" float nabwa_batch_last_deep_ms(nabwa_batch_t *b) { return b ? b->last
 extern "C" int nabwa_batch_count_touches(nabwa_batch_t *b, uint64_t *n_bucket, uint64_t *n_bucket_width)
 {
 	if (!b || !n_bucket) return fail(NABWA_EINVAL, "null argument");
-	HIPCHK(hipSetDevice(b->ix->device));
-	HIPCHK(hipMemsetAsync(b->d_sum, 0, 256, b->stream));
+	HIP_CHECK(hipSetDevice(b->ix->device));
+	HIP_CHECK(hipMemsetAsync(b->d_sum, 0, 256, b->stream));
 	b->P.touch_counter = b->d_sum;
 	/* the reference walks every exact tail row by row: count with the tail jump off (NABWA_TRIP_STATS=jump keeps it
 	 * on to profile the production trips; the touch totals are then not the reference's) */
@@ -1064,17 +1053,17 @@ extern "C" int nabwa_batch_count_touches(nabwa_batch_t *b, uint64_t *n_bucket, u
 	b->P.bwt[0].kmer_T = kt0; b->P.bwt[1].kmer_T = kt1; b->P.text_mode = tm0;
 	if (r != NABWA_OK) return r;
 	unsigned long long v[2] = { 0, 0 };
-	HIPCHK(hipMemcpy(v, b->d_sum, 16, hipMemcpyDeviceToHost));
+	HIP_CHECK(hipMemcpy(v, b->d_sum, 16, hipMemcpyDeviceToHost));
 	*n_bucket = v[0];                          /* search kernel (bwt_match_gap) */
 	if (n_bucket_width) *n_bucket_width = v[1];  /* width kernel (bwt_cal_width) */
 	if (getenv("NABWA_TRIP_STATS") && b->class_sort) {
 		unsigned int c[12];
-		HIPCHK(hipMemcpy(c, b->d_ncls, 48, hipMemcpyDeviceToHost));
+		HIP_CHECK(hipMemcpy(c, b->d_ncls, 48, hipMemcpyDeviceToHost));
 		fprintf(stderr, "[nabwa] read classes by restarts 0 / 1 / 2+: %u / %u / %u\n", c[0], c[1], c[2]);
 	}
 	if (getenv("NABWA_TRIP_STATS")) {
 		unsigned long long t[32];
-		HIPCHK(hipMemcpy(t, b->d_sum, 256, hipMemcpyDeviceToHost));
+		HIP_CHECK(hipMemcpy(t, b->d_sum, 256, hipMemcpyDeviceToHost));
 		fprintf(stderr, "[nabwa] search kernel: wave-trips %llu; lane-trips: expand %llu exact %llu entry-load %llu spec %llu query %llu two-bucket %llu exited %llu tail-jump %llu text-expand %llu text-tail %llu; longest read %llu trips, %llu reads over 2000 trips, %llu over 500\n",
 				t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], t[15]);
 		fprintf(stderr, "[nabwa] the %llu reads over 8000 trips: %llu trips = expansions key-form %llu, rows two-bucket %llu, rows one-bucket %llu, text %llu (of all: %llu with gaps); pops %llu, tail steps %llu, jumps %llu\n",
@@ -1090,14 +1079,14 @@ extern "C" int nabwa_batch_width_records(nabwa_batch_t *b, int first, int n, uin
 {
 	if (!b || first < 0 || n < 0 || first + n > b->n || (n && (!w_out || !bid_out))) return fail(NABWA_EINVAL, "bad argument");
 	if (n == 0) return NABWA_OK;
-	HIPCHK(hipSetDevice(b->ix->device));
-	HIPCHK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
+	HIP_CHECK(hipSetDevice(b->ix->device));
+	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
 	SearchParams PW = b->P; PW.ids = 0; PW.rd_cls = 0; PW.touch_counter = 0;
 	nabwa_launch_fm_width(&PW, b->n_blocks_w, b->stream);
-	HIPCHK(hipGetLastError());
+	HIP_CHECK(hipGetLastError());
 	std::vector<uint8_t> rec((size_t)n * b->P.wstride);
-	HIPCHK(hipMemcpyAsync(rec.data(), b->d_wdata + (size_t)first * b->P.wstride, rec.size(), hipMemcpyDeviceToHost, b->stream));
-	HIPCHK(hipStreamSynchronize(b->stream));
+	HIP_CHECK(hipMemcpyAsync(rec.data(), b->d_wdata + (size_t)first * b->P.wstride, rec.size(), hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipStreamSynchronize(b->stream));
 	const int W = b->max_len + 1, SW = b->opt.seed_len + 1;
 	for (int i = 0; i < n; ++i) {
 		const uint8_t *r = rec.data() + (size_t)i * b->P.wstride;
@@ -1113,13 +1102,13 @@ extern "C" int nabwa_batch_width_records(nabwa_batch_t *b, int first, int n, uin
 extern "C" int nabwa_batch_checksum(nabwa_batch_t *b, uint64_t *sum, int64_t *n_rows)
 {
 	if (!b) return fail(NABWA_EINVAL, "null batch");
-	HIPCHK(hipSetDevice(b->ix->device));
+	HIP_CHECK(hipSetDevice(b->ix->device));
 	unsigned long long h[2] = { 0, 0 };
-	HIPCHK(hipMemsetAsync(b->d_sum, 0, 16, b->stream));
+	HIP_CHECK(hipMemsetAsync(b->d_sum, 0, 16, b->stream));
 	nabwa_launch_checksum(b->n, b->d_naln, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
 						  b->d_sum, b->d_sum + 1, b->stream);
-	HIPCHK(hipMemcpyAsync(h, b->d_sum, 16, hipMemcpyDeviceToHost, b->stream));
-	HIPCHK(hipStreamSynchronize(b->stream));
+	HIP_CHECK(hipMemcpyAsync(h, b->d_sum, 16, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipStreamSynchronize(b->stream));
 	if (sum) *sum = h[0];
 	if (n_rows) *n_rows = (int64_t)h[1];
 	return NABWA_OK;
@@ -1135,10 +1124,10 @@ extern "C" int nabwa_batch_config(nabwa_batch_t *b, nabwa_batch_config_t *out)
 	out->n_sync = out->hard_budget = -1;
 	for (int q = 0; q < 3; ++q) out->cls[q] = -1;
 	if (b->ran && b->class_sort) {
-		HIPCHK(hipSetDevice(b->ix->device));
+		HIP_CHECK(hipSetDevice(b->ix->device));
 		unsigned int c[12];
-		HIPCHK(hipMemcpyAsync(c, b->d_ncls, 48, hipMemcpyDeviceToHost, b->stream));
-		HIPCHK(hipStreamSynchronize(b->stream));
+		HIP_CHECK(hipMemcpyAsync(c, b->d_ncls, 48, hipMemcpyDeviceToHost, b->stream));
+		HIP_CHECK(hipStreamSynchronize(b->stream));
 		for (int q = 0; q < 3; ++q) out->cls[q] = (int32_t)c[q];
 		out->n_sync = (int32_t)c[10];
 		/* the rule of fm_search_kernel: the hard budget when most reads occur exactly on neither strand */
@@ -1153,34 +1142,34 @@ extern "C" int nabwa_batch_fetch(nabwa_batch_t *b, int32_t *n_aln, nabwa_aln1_t 
 								 int32_t *max_entries)
 {
 	if (!b || !n_aln) return fail(NABWA_EINVAL, "null argument");
-	HIPCHK(hipSetDevice(b->ix->device));
+	HIP_CHECK(hipSetDevice(b->ix->device));
 	if (n_rows) *n_rows = 0;
 	if (b->n == 0) return NABWA_OK;
 	// device-side compaction: exclusive scan of n_aln, then gather rows
 	uint32_t *d_off = 0; void *d_tmp = 0; size_t tmp_bytes = 0; uint4 *d_rows = 0;
-	HIPCHK(pool_malloc(b->ix, (void**)&d_off, (size_t)(b->n + 1) * 4));
-	HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const uint32_t*)b->d_naln, d_off, b->n, b->stream));
-	HIPCHK(pool_malloc(b->ix, (void**)&d_tmp, tmp_bytes ? tmp_bytes : 16));
-	HIPCHK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, (const uint32_t*)b->d_naln, d_off, b->n, b->stream));
+	HIP_CHECK(pool_malloc(b->ix, (void**)&d_off, (size_t)(b->n + 1) * 4));
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const uint32_t*)b->d_naln, d_off, b->n, b->stream));
+	HIP_CHECK(pool_malloc(b->ix, (void**)&d_tmp, tmp_bytes ? tmp_bytes : 16));
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, (const uint32_t*)b->d_naln, d_off, b->n, b->stream));
 	uint32_t last_off = 0; int32_t last_n = 0;
-	HIPCHK(hipMemcpyAsync(&last_off, d_off + (b->n - 1), 4, hipMemcpyDeviceToHost, b->stream));
-	HIPCHK(hipMemcpyAsync(&last_n, b->d_naln + (b->n - 1), 4, hipMemcpyDeviceToHost, b->stream));
-	HIPCHK(hipMemcpyAsync(n_aln, b->d_naln, (size_t)b->n * 4, hipMemcpyDeviceToHost, b->stream));
-	if (max_entries) HIPCHK(hipMemcpyAsync(max_entries, b->d_maxent, (size_t)b->n * 4, hipMemcpyDeviceToHost, b->stream));
-	HIPCHK(hipStreamSynchronize(b->stream));
+	HIP_CHECK(hipMemcpyAsync(&last_off, d_off + (b->n - 1), 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipMemcpyAsync(&last_n, b->d_naln + (b->n - 1), 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipMemcpyAsync(n_aln, b->d_naln, (size_t)b->n * 4, hipMemcpyDeviceToHost, b->stream));
+	if (max_entries) HIP_CHECK(hipMemcpyAsync(max_entries, b->d_maxent, (size_t)b->n * 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipStreamSynchronize(b->stream));
 	const int64_t total = (int64_t)last_off + last_n;
 	if (n_rows) *n_rows = total;
 	int rc = NABWA_OK;
 	if (total > aln_cap || (total && !aln_out)) rc = fail(NABWA_ECAP, "aln_cap too small");
 	else if (total) {
-		HIPCHK(pool_malloc(b->ix, (void**)&d_rows, (size_t)total * 16));
+		HIP_CHECK(pool_malloc(b->ix, (void**)&d_rows, (size_t)total * 16));
 		nabwa_launch_gather(b->n, b->d_naln, d_off, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
 							d_rows, b->stream);
-		HIPCHK(hipMemcpyAsync(aln_out, d_rows, (size_t)total * 16, hipMemcpyDeviceToHost, b->stream));
-		HIPCHK(hipStreamSynchronize(b->stream));
-		HIPCHK(pool_free(b->ix, d_rows));
+		HIP_CHECK(hipMemcpyAsync(aln_out, d_rows, (size_t)total * 16, hipMemcpyDeviceToHost, b->stream));
+		HIP_CHECK(hipStreamSynchronize(b->stream));
+		HIP_CHECK(pool_free(b->ix, d_rows));
 	}
-	HIPCHK(pool_free(b->ix, d_off)); HIPCHK(pool_free(b->ix, d_tmp));
+	HIP_CHECK(pool_free(b->ix, d_off)); HIP_CHECK(pool_free(b->ix, d_tmp));
 	return rc;
 }
 
@@ -1191,25 +1180,24 @@ extern "C" int nabwa_cal_sa_reg_gap(nabwa_index_t *ix, const nabwa_gap_opt_t *op
 {
 	nabwa_batch_t *b = 0;
 	const bool timing = getenv("NABWA_TIMING") != 0;
-	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-	const double t0 = now();
+	const double t0 = now_s();
 	if (n_rows) *n_rows = 0;
 	int r = nabwa_batch_create(ix, opt, n, off, seq, rseq, per_read, &b);
 	if (r != NABWA_OK) return r;
-	const double t1 = now();
+	const double t1 = now_s();
 	r = nabwa_batch_run(b);
 	if (r == NABWA_OK) r = nabwa_batch_sync(b, 0);
-	const double t2 = now();
+	const double t2 = now_s();
 	if (r == NABWA_OK) r = nabwa_batch_fetch(b, n_aln, aln_out, aln_cap, n_rows, max_entries);
 	else if (r == NABWA_EHITS) {      /* a few reads have more hit rows than NABWA_ALNCAP2: every other read's result is still handed out */
 		const std::string msg = g_err;
 		const int r2 = nabwa_batch_fetch(b, n_aln, aln_out, aln_cap, n_rows, max_entries);
 		if (r2 != NABWA_OK) r = r2; else g_err = msg;
 	}
-	const double t3 = now();
+	const double t3 = now_s();
 	nabwa_batch_destroy(b);
 	if (timing) fprintf(stderr, "[nabwa] cal_sa_reg_gap %d reads: upload + layout %.3f s, kernels %.3f s, compaction + download %.3f s, release %.3f s\n",
-						n, t1 - t0, t2 - t1, t3 - t2, now() - t3);
+						n, t1 - t0, t2 - t1, t3 - t2, now_s() - t3);
 	return r;
 }
 
@@ -1220,16 +1208,16 @@ extern "C" int nabwa_sa_lookup(nabwa_index_t *ix, int n, const uint8_t *which, c
 	if (!ix || n < 0 || (n && (!which || !k || !sa_out))) return fail(NABWA_EINVAL, "null argument");
 	if (!ix->bwt[0].sa || !ix->bwt[1].sa) return fail(NABWA_EINVAL, "index was loaded without suffix arrays");
 	if (n == 0) return NABWA_OK;
-	HIPCHK(hipSetDevice(ix->device));
+	HIP_CHECK(hipSetDevice(ix->device));
 	uint8_t *dw = 0; uint32_t *dk = 0, *dout = 0;
 	/* (buffers from the pool kept with the index: this is called once per batch by the finishing chains) */
-	HIPCHK(pool_malloc(ix, (void**)&dw, (size_t)n)); HIPCHK(pool_malloc(ix, (void**)&dk, (size_t)n * 4)); HIPCHK(pool_malloc(ix, (void**)&dout, (size_t)n * 4));
-	HIPCHK(hipMemcpy(dw, which, n, hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(dk, k, (size_t)n * 4, hipMemcpyHostToDevice));
+	HIP_CHECK(pool_malloc(ix, (void**)&dw, (size_t)n)); HIP_CHECK(pool_malloc(ix, (void**)&dk, (size_t)n * 4)); HIP_CHECK(pool_malloc(ix, (void**)&dout, (size_t)n * 4));
+	HIP_CHECK(hipMemcpy(dw, which, n, hipMemcpyHostToDevice));
+	HIP_CHECK(hipMemcpy(dk, k, (size_t)n * 4, hipMemcpyHostToDevice));
 	nabwa_launch_sa_lookup(ix->bwt, n, dw, dk, dout, 0);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(sa_out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
-	HIPCHK(pool_free(ix, dw)); HIPCHK(pool_free(ix, dk)); HIPCHK(pool_free(ix, dout));
+	HIP_CHECK(hipGetLastError());
+	HIP_CHECK(hipMemcpy(sa_out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
+	HIP_CHECK(pool_free(ix, dw)); HIP_CHECK(pool_free(ix, dk)); HIP_CHECK(pool_free(ix, dout));
 	return NABWA_OK;
 }
 
@@ -1237,13 +1225,13 @@ extern "C" int nabwa_occ4(nabwa_index_t *ix, int which, int n, const uint32_t *k
 {
 	if (!ix || n < 0 || (n && (!k || !cnt_out))) return fail(NABWA_EINVAL, "null argument");
 	if (n == 0) return NABWA_OK;
-	HIPCHK(hipSetDevice(ix->device));
+	HIP_CHECK(hipSetDevice(ix->device));
 	uint32_t *dk = 0, *dout = 0;
-	HIPCHK(hipMalloc(&dk, (size_t)n * 4)); HIPCHK(hipMalloc(&dout, (size_t)n * 16));
-	HIPCHK(hipMemcpy(dk, k, (size_t)n * 4, hipMemcpyHostToDevice));
+	HIP_CHECK(hipMalloc(&dk, (size_t)n * 4)); HIP_CHECK(hipMalloc(&dout, (size_t)n * 16));
+	HIP_CHECK(hipMemcpy(dk, k, (size_t)n * 4, hipMemcpyHostToDevice));
 	nabwa_launch_occ4(&ix->bwt[which & 1], n, dk, dout, 0);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(cnt_out, dout, (size_t)n * 16, hipMemcpyDeviceToHost));
-	HIPCHK(hipFree(dk)); HIPCHK(hipFree(dout));
+	HIP_CHECK(hipGetLastError());
+	HIP_CHECK(hipMemcpy(cnt_out, dout, (size_t)n * 16, hipMemcpyDeviceToHost));
+	HIP_CHECK(hipFree(dk)); HIP_CHECK(hipFree(dout));
 	return NABWA_OK;
 }

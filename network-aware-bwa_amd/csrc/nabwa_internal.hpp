@@ -1,8 +1,10 @@
 // nabwa_internal.hpp -- host-side structures shared by the translation units of libnabwa.so
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
 #include <string>
 #include <vector>
+#include "../../include/nabwa.h"
 #include "fm_search.hpp"
 
 struct nabwa_ann { int64_t offset; int32_t len, n_ambs; std::string name; };    // bntann1_t, bntseq.h:39-45
@@ -29,4 +31,21 @@ struct nabwa_index {
 };
 
 int nabwa_fail(int code, const char *fmt, const char *a = "");
+
+/* a failed HIP call: "<expr> failed: <hip error> (<file>:<line>)" as the last error, NABWA_ENODEV as the result */
+static inline int nabwa_hip_fail(hipError_t e, const char *expr, const char *file, int line)
+{
+	char b[512]; snprintf(b, sizeof b, "%s failed: %s (%s:%d)", expr, hipGetErrorString(e), file, line);
+	return nabwa_fail(NABWA_ENODEV, "%s", b);
+}
+#define HIP_CHECK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return nabwa_hip_fail(e_, #x, __FILE__, __LINE__); } while (0)
+
+/* entry points on records of any stride whose head is a nabwa_se_t (nabwa_pe_t starts with one), for the files that work in place
+ * (se_finish.hip) */
+int nabwa_se_posn_strided(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, const int64_t *off, const int32_t *full_len,
+						  const int32_t *n_aln, const nabwa_aln1_t *aln, const uint8_t *n_occ_v, uint64_t *rng48, void *out_base, size_t stride);
+int nabwa_se_refine_strided(nabwa_index_t *ix, int n, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, void *out_base, size_t stride);
+/* the wide rows of a batch's pairs into finish_pair's position cache, in record order (pe_finish.hip) */
+void nabwa_poscache_register(nabwa_poscache_t *cache, int max_occ, int n, const int *first, const int32_t *n_aln, const int64_t *row0,
+							 const nabwa_aln1_t *rows, const nabwa_pe_t *res);
 

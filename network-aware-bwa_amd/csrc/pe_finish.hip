@@ -12,9 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
-#include <chrono>
 #include <atomic>
-#include <thread>
 #include "finish_common.hpp"
 
 #define F_PD 1
@@ -30,9 +28,6 @@
 
 static inline nabwa_pe_t &PE(nabwa_pe_t *out, int pair, int end) { return out[2 * (size_t)pair + end]; }
 
-int nabwa_se_posn_strided(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, const int64_t *off, const int32_t *full_len,
-						  const int32_t *n_aln, const nabwa_aln1_t *aln, const uint8_t *n_occ_v, uint64_t *rng48, void *out_base, size_t stride);      /* se_finish.hip */
-
 /* posn_pair (bam2bam.c:683-703) for n_pairs pairs; records and reads are interleaved: index 2*pair + end. */
 extern "C" int nabwa_pe_posn(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n_pairs, const int64_t *off, const int32_t *full_len,
 							 const int32_t *n_aln, const nabwa_aln1_t *aln, uint64_t *rng48, nabwa_pe_t *out)
@@ -43,7 +38,7 @@ extern "C" int nabwa_pe_posn(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int 
 	 * drand48 stream, the bwt_sa batch, mapQ -- done by the single-end chain's code on these records in place (its head is theirs) */
 	int rc = nabwa_se_posn_strided(ix, opt, n, off, full_len, n_aln, aln, 0, rng48, out, sizeof(nabwa_pe_t));
 	if (rc != NABWA_OK) return rc;
-	fin_parallel(fin_threads((size_t)n), (size_t)n, [&](int, size_t lo, size_t hi) {
+	host_parallel(host_threads((size_t)n, 4096), (size_t)n, [&](int, size_t lo, size_t hi) {
 		for (size_t i = lo; i < hi; ++i) {
 			nabwa_pe_t &r = out[i];
 			r.se.seqid = -1;
@@ -147,8 +142,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 	const uint32_t rlen = ix->bwt[1].seq_len;
 	const int n = 2 * n_pairs;
 	const bool timing = getenv("NABWA_TIMING") != 0;
-	auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-	double t0 = now(), t1, t2, t3, t4;
+	double t0 = now_s(), t1, t2, t3, t4;
 	std::vector<size_t> a_off((size_t)n + 1, 0);
 	for (int i = 0; i < n; ++i) a_off[i + 1] = a_off[i] + (size_t)n_aln[i];
 	uint64_t tot_dummy[2] = { 0, 0 }, map_dummy[2] = { 0, 0 };
@@ -163,7 +157,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 	/* which pairs are paired here -- both ends mapped, neither with more than max_occ hit rows -- and how many rows each brings:
 	 * the records are read by all threads, the chunks are then cut from the counts alone */
 	std::vector<uint32_t> prow((size_t)(n_pairs ? n_pairs : 1), 0);
-	fin_parallel(fin_threads((size_t)n_pairs), (size_t)n_pairs, [&](int, size_t p_lo, size_t p_hi) {
+	host_parallel(host_threads((size_t)n_pairs, 4096), (size_t)n_pairs, [&](int, size_t p_lo, size_t p_hi) {
 		for (size_t pr = p_lo; pr < p_hi; ++pr) {
 			if (pr + 8 < p_hi) { __builtin_prefetch(&PE(out, (int)pr + 8, 0)); __builtin_prefetch(&PE(out, (int)pr + 8, 1)); }      /* (3 KB records: the next ones asked for ahead) */
 			uint32_t rows_here = 0;
@@ -177,7 +171,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 	std::unordered_map<size_t, uint32_t> foreign;
 	if (cache) {
 		std::vector<uint8_t> wide((size_t)(n_pairs ? n_pairs : 1), 0);
-		fin_parallel(fin_threads((size_t)n_pairs), (size_t)n_pairs, [&](int, size_t p_lo, size_t p_hi) {
+		host_parallel(host_threads((size_t)n_pairs, 4096), (size_t)n_pairs, [&](int, size_t p_lo, size_t p_hi) {
 			for (size_t pr = p_lo; pr < p_hi; ++pr) {
 				if (!prow[pr]) continue;
 				for (size_t r = a_off[2 * pr]; r < a_off[2 * pr + 2]; ++r) if (aln[r].l - aln[r].k + 1 >= MIN_HASH_WIDTH) { wide[pr] = 1; break; }
@@ -199,7 +193,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 		if (!foreign.empty()) { auto it = foreign.find(r); if (it != foreign.end()) { a = it->second >> 31; len = it->second & 0x7fffffffu; } }
 	};
 	for (int p0 = 0; p0 < n_pairs;) {
-		const double tA0 = now();
+		const double tA0 = now_s();
 		std::vector<uint8_t> which; std::vector<uint32_t> rows; std::vector<size_t> pair_lo; std::vector<int> pairs;
 		int p1 = p0;
 		size_t n_rows = 0;
@@ -208,7 +202,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 			pairs.push_back(p1); pair_lo.push_back(n_rows); n_rows += prow[(size_t)p1];
 		}
 		which.resize(n_rows); rows.resize(n_rows);
-		fin_parallel(fin_threads(pairs.size()), pairs.size(), [&](int, size_t t_lo, size_t t_hi) {
+		host_parallel(host_threads(pairs.size(), 4096), pairs.size(), [&](int, size_t t_lo, size_t t_hi) {
 			for (size_t t = t_lo; t < t_hi; ++t) {
 				const int pr = pairs[t];
 				size_t u = pair_lo[t];
@@ -223,11 +217,11 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 		});
 		pair_lo.push_back(rows.size());
 		n_hit_rows += rows.size();
-		const double tA1 = now();
+		const double tA1 = now_s();
 		std::vector<uint32_t> sa(rows.size());
 		if (!rows.empty()) { int r = nabwa_sa_lookup(ix, (int)rows.size(), which.data(), rows.data(), sa.data()); if (r != NABWA_OK) return r; }
-		const double tA2 = now();
-		fin_parallel(fin_threads(pairs.size()), pairs.size(), [&](int, size_t t_lo, size_t t_hi) {      /* pairs are independent of each other */
+		const double tA2 = now_s();
+		host_parallel(host_threads(pairs.size(), 4096), pairs.size(), [&](int, size_t t_lo, size_t t_hi) {      /* pairs are independent of each other */
 		std::vector<uint64_t> hits;
 		for (size_t t = t_lo; t < t_hi; ++t) {
 			if (t + 8 < t_hi) { const int f = pairs[t + 8]; __builtin_prefetch(&PE(out, f, 0), 1); __builtin_prefetch(&PE(out, f, 1), 1); }
@@ -258,18 +252,18 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 			}
 		}
 		});
-		ta[0] += tA1 - tA0; ta[1] += tA2 - tA1; ta[2] += now() - tA2;
+		ta[0] += tA1 - tA0; ta[1] += tA2 - tA1; ta[2] += now_s() - tA2;
 		p0 = p1;
 	}
-	t1 = now();
+	t1 = now_s();
 
 	/* ---- B. multi-hit lists and their positions (bam2bam.c:773-790) */
 	{
 		std::vector<uint8_t> which; std::vector<uint32_t> rows; std::vector<int> look_rec, look_multi;
-		const int ntb = fin_threads((size_t)n_pairs);
+		const int ntb = host_threads((size_t)n_pairs, 4096);
 		struct MultiPart { std::vector<uint8_t> which; std::vector<uint32_t> rows; std::vector<int> look_rec, look_multi; };
 		std::vector<MultiPart> parts((size_t)ntb);
-		fin_parallel(ntb, (size_t)n_pairs, [&](int slice, size_t p_lo, size_t p_hi) {
+		host_parallel(ntb, (size_t)n_pairs, [&](int slice, size_t p_lo, size_t p_hi) {
 		MultiPart &M = parts[(size_t)slice];
 		std::vector<uint8_t> &which = M.which; std::vector<uint32_t> &rows = M.rows; std::vector<int> &look_rec = M.look_rec, &look_multi = M.look_multi;
 		for (int pr = (int)p_lo; pr < (int)p_hi; ++pr)
@@ -300,7 +294,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 			s.multi[look_multi[t]].pos = which[t] == 0 ? sa[t] : rlen - (sa[t] + (uint32_t)s.len);
 		}
 	}
-	t2 = now();
+	t2 = now_s();
 
 	/* ---- C. mate rescue (bwa_paired_sw1, bwape.c:519-633; bam2bam calls it unconditionally).
 	 *         Quirk F4 kept: a pair with an unmapped end returns before anything is changed. */
@@ -311,10 +305,10 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 		std::vector<int64_t> begs((size_t)n, 0);                         /* beg[k] of every attempted end, by record index */
 		std::vector<int> job_of((size_t)n, -1);
 		{	/* which pairs are tried: unpaired, one end with a high mapping quality, both ends mapped (slices of pairs in threads) */
-			const int ntc = fin_threads((size_t)n_pairs);
+			const int ntc = host_threads((size_t)n_pairs, 4096);
 			std::vector<std::vector<int>> cparts((size_t)ntc);
 			std::vector<uint64_t> tot0((size_t)ntc, 0), tot1((size_t)ntc, 0);
-			fin_parallel(ntc, (size_t)n_pairs, [&](int slice, size_t p_lo, size_t p_hi) {
+			host_parallel(ntc, (size_t)n_pairs, [&](int slice, size_t p_lo, size_t p_hi) {
 				for (int pr = (int)p_lo; pr < (int)p_hi; ++pr) {
 					if (pr + 8 < (int)p_hi) for (int e = 0; e < 2; ++e) { const nabwa_pe_t *const f = &PE(out, pr + 8, e); __builtin_prefetch(f); __builtin_prefetch(&f->extra_flag); }
 					const nabwa_pe_t &r0 = PE(out, pr, 0), &r1 = PE(out, pr, 1);
@@ -326,7 +320,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 			});
 			for (int t = 0; t < ntc; ++t) { n_tot[0] += tot0[(size_t)t]; n_tot[1] += tot1[(size_t)t]; cand.insert(cand.end(), cparts[(size_t)t].begin(), cparts[(size_t)t].end()); }
 		}
-		tc[0] = now() - t2; n_cand = cand.size();
+		tc[0] = now_s() - t2; n_cand = cand.size();
 		for (int pr : cand) {
 			for (int k = 0; k < 2; ++k) {
 				const nabwa_se_t &ref = PE(out, pr, 1 - k).se, &mate = PE(out, pr, k).se;
@@ -360,7 +354,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 				jobs.push_back({ pr, k, a, l, ref.strand != 0 });
 			}
 		}
-		tc[1] = now() - t2;
+		tc[1] = now_s() - t2;
 		n_sw = jobs.size();
 		const int MAXC = NABWA_MAX_CIGAR - 2;
 		std::vector<int32_t> sc(jobs.size()), co(jobs.size() * 4), nc(jobs.size()); std::vector<uint32_t> c32(jobs.size() * (size_t)MAXC);
@@ -370,7 +364,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 									  sc.data(), co.data(), 0, nc.data(), c32.data(), MAXC);
 			if (r != NABWA_OK) return r;
 		}
-		tc[2] = now() - t2;
+		tc[2] = now_s() - t2;
 		const int sw_isize_term = (int)(-4.343 * log(.5 * erfc(M_SQRT1_2 * 1.5) + .499));     /* bwape.c:593 */
 		for (int pr : cand) {
 			int n_cig[2] = { 0, 0 }, mq_adjust[2] = { 255, 255 }; uint16_t cig[2][NABWA_MAX_CIGAR]; uint32_t cnt[2] = { 0, 0 };
@@ -452,14 +446,14 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 			}
 		}
 	}
-	t3 = now();
+	t3 = now_s();
 
 	/* ---- D. gap refinement of both ends and their multi hits, one GPU batch (bwa_refine_gapped, bwase.c:356-381) */
 	{
 		int r = refine_batch(ix, out, sizeof(nabwa_pe_t), n, off, seq, rseq, &n_refine);
 		if (r != NABWA_OK) return r;
 	}
-	t4 = now();
+	t4 = now_s();
 
 	/* ---- E. MD / NM / trimmed tail per end, then the flag and mate fields (bwase.c:399-419, bam2bam.c:430-525) */
 	int md_over = 0;
@@ -506,19 +500,12 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 			}
 		}
 	};
-	{
-		int nt = (int)std::thread::hardware_concurrency(); if (nt < 1) nt = 1; if (nt > 16) nt = 16;
-		if (getenv("NABWA_HOST_THREADS")) nt = std::max(1, atoi(getenv("NABWA_HOST_THREADS")));
-		if (n_pairs < 4096) nt = 1;
-		std::vector<std::thread> th;
-		for (int t = 0; t < nt; ++t) th.emplace_back(phaseE, (int)((int64_t)n_pairs * t / nt), (int)((int64_t)n_pairs * (t + 1) / nt));
-		for (auto &x : th) x.join();
-	}
+	host_parallel(host_threads((size_t)n_pairs, 4096), (size_t)n_pairs, [&](int, size_t lo, size_t hi) { phaseE((int)lo, (int)hi); });
 	if (md_over) return nabwa_fail(NABWA_ECAP, "MD string longer than NABWA_MAX_MD");
 	if (timing) fprintf(stderr, "[nabwa] pe_finish pairing: rows collected %.3f s, bwt_sa %.3f s, pairing %.3f s; rescue: scan %.3f s, windows %.3f s (%zu candidates), local alignments %.3f s, applied %.3f s\n",
 						ta[0], ta[1], ta[2], tc[0], tc[1] - tc[0], n_cand, tc[2] - tc[1], (t3 - t2) - tc[2]);
 	if (timing) fprintf(stderr, "[nabwa] pe_finish %d pairs: pairing (%zu hit rows) %.3f s, multi %.3f s, mate rescue (%zu alignments) %.3f s, "
-						"refinement (%zu jobs) %.3f s, md/flags %.3f s\n", n_pairs, n_hit_rows, t1 - t0, t2 - t1, n_sw, t3 - t2, n_refine, t4 - t3, now() - t4);
+						"refinement (%zu jobs) %.3f s, md/flags %.3f s\n", n_pairs, n_hit_rows, t1 - t0, t2 - t1, n_sw, t3 - t2, n_refine, t4 - t3, now_s() - t4);
 	if (cnt_chg) *cnt_chg = chg.load();
 	return NABWA_OK;
 }

@@ -6,10 +6,10 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
-#include <thread>
 #include <vector>
 #include "../../include/nabwa.h"
 #include "nabwa_internal.hpp"
+#include "host_util.hpp"
 
 #define MAX_ISIZE 100000          /* insert_size.c:47 */
 #define OUTLIER_BOUND 2.0         /* bwape.h:34 */
@@ -85,19 +85,13 @@ extern "C" int nabwa_isize_add_pairs(int n_pairs, const nabwa_pe_t *recs, uint16
 	if (n_pairs < 0 || (n_pairs && !recs) || !hist) return nabwa_fail(NABWA_EINVAL, "null argument");
 	/* the bins by all threads (two 3 KB records per pair: the next ones are asked for ahead), the counts by one: uint16 sums do not care for the order */
 	std::vector<int32_t> bin((size_t)(n_pairs ? n_pairs : 1));
-	int nt = (int)std::thread::hardware_concurrency(); if (nt < 1) nt = 1; if (nt > 16) nt = 16;
-	if (getenv("NABWA_HOST_THREADS")) nt = atoi(getenv("NABWA_HOST_THREADS")) > 0 ? atoi(getenv("NABWA_HOST_THREADS")) : 1;
-	if (n_pairs < 65536) nt = 1;
-	auto work = [&](int t) {
-		const size_t lo = (size_t)n_pairs * t / nt, hi = (size_t)n_pairs * (t + 1) / nt;
+	host_parallel(host_threads((size_t)n_pairs, 65536), (size_t)n_pairs, [&](int, size_t lo, size_t hi) {
 		for (size_t i = lo; i < hi; ++i) {
 			if (i + 8 < hi) { __builtin_prefetch(&recs[2 * (i + 8)]); __builtin_prefetch(&recs[2 * (i + 8) + 1]); }
 			const nabwa_se_t &a = recs[2 * i].se, &b = recs[2 * i + 1].se;
 			bin[i] = nabwa_isize_bin(2, a.mapQ, b.mapQ, a.pos, a.len, b.pos, b.len);
 		}
-	};
-	if (nt == 1) work(0);
-	else { std::vector<std::thread> th; for (int t = 0; t < nt; ++t) th.emplace_back(work, t); for (auto &x : th) x.join(); }
+	});
 	for (int i = 0; i < n_pairs; ++i) if (bin[(size_t)i] >= 0) ++hist[bin[(size_t)i]];
 	return NABWA_OK;
 }

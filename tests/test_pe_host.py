@@ -87,3 +87,26 @@ def test_isize_add_pairs_bins_like_isize_bin_and_wraps():
         nabwa.isize_add_pairs(recs, n, got)
     assert (got == want).all()
     assert int(got[350]) == (4 * ((n + 2) // 3)) % 65536 and 4 * ((n + 2) // 3) > 65535
+
+
+def test_isize_add_pairs_same_on_one_thread(monkeypatch):
+    """above 65536 pairs the bins are taken on several host threads: the histogram does not depend on how many"""
+    rng = np.random.default_rng(5)
+    n = 70000
+    recs = (nabwa.PeRec * (2 * n))()
+    for i in range(n):
+        a, b = recs[2 * i].se, recs[2 * i + 1].se
+        a.mapQ, b.mapQ = int(rng.integers(10, 40)), int(rng.integers(10, 40))
+        a.len, b.len = 100, int(rng.integers(30, 101))
+        a.pos = int(rng.integers(0, 1 << 16))
+        b.pos = a.pos + int(rng.integers(0, 1000))
+    got = []
+    for threads in ("1", None):
+        if threads:
+            monkeypatch.setenv("NABWA_HOST_THREADS", threads)
+        else:
+            monkeypatch.delenv("NABWA_HOST_THREADS")
+        h = np.zeros(100000, np.uint16)
+        nabwa.isize_add_pairs(recs, n, h)
+        got.append(h)
+    assert got[0].sum() > 0 and (got[0] == got[1]).all()

@@ -61,7 +61,8 @@ int nabwa_cal_maxdiff(int len, double err, double thres);
 
 /* Replaces init_genome_index (bam2bam.c:844-858): reads <prefix>.bwt/.rbwt (and .sa/.rsa when
  * with_sa, .pac when with_pac) in the reference's on-disk format (bwtio.c:161-204), uploads them
- * to `device` and re-packs the Occ arrays into 64-byte buckets there. */
+ * to `device` and re-packs the Occ arrays into 64-byte buckets there.  NABWA_EINVAL for a seq_len above 0xffffffdf, or with SA samples
+ * a seq_len + sa_intv above 0xffffffff: the reference's loader wraps its SA count there (bwtio.c:175). */
 int nabwa_index_load(const char *prefix, int device, int with_sa, int with_pac, nabwa_index_t **out);
 
 /* Same, from arrays already in memory (is_device != 0: device pointers on `device`).
@@ -476,7 +477,8 @@ int nabwa_occ4(nabwa_index_t *ix, int which, int n, const uint32_t *k, uint32_t 
  *                        FASTQ, plain or gzip, in; <prefix>.pac, .ann, .amb and .rpac out, byte for byte the reference's (ambiguous
  *                        bases drawn from lrand48 after srand48(11), holes, the stale-comment quirk of kseq).  Host only, no GPU.
  *                        Returns l_pac, or a negative NABWA_E*: NABWA_EINVAL for an input without bases or over 4 Gbp (nothing is
- *                        written then), NABWA_EIO for a file that cannot be read or written.  prefix NULL: read and check the
+ *                        written then; "over 4 Gbp" means over 4 294 967 168 bases, 0xffffff80, where the reference's own Occ count
+ *                        wraps, bwtmisc.c:131), NABWA_EIO for a file that cannot be read or written.  prefix NULL: read and check the
  *                        input only, write nothing.
  * nabwa_index_fa2cspac = the same for `bwa index -c` (bwtindex.c:84-98, bwa_pac2cspac, bwtmisc.c:210-254): <prefix>.nt.pac/.ann/.amb
  *                        of the bases, then the colour text as <prefix>.pac/.ann/.amb/.rpac.  Host only.
@@ -484,7 +486,9 @@ int nabwa_occ4(nabwa_index_t *ix, int which, int n, const uint32_t *k, uint32_t 
  *                        reversed text), .sa and .rsa (every sa_intv-th row; the reference uses 32) out, the words the reference writes
  *                        whichever of -a is / bwtsw it runs.  The worst-case device memory (nabwa_index_build_estimate, about
  *                        41 bytes per base) is checked against the device's free memory and against NABWA_INDEX_MAX_BYTES when that
- *                        is set: NABWA_ENOMEM before any allocation if it does not fit.  Texts up to 4 294 967 279 bases.
+ *                        is set: NABWA_ENOMEM before any allocation if it does not fit.  Texts up to 4 294 967 168 bases
+ *                        (0xffffff80, as nabwa_index_fa2pac); a longer .pac is NABWA_EINVAL before its bases are read, and so is
+ *                        an sa_intv with l_pac + sa_intv > 0xffffffff (the reference's loader would wrap n_sa, bwtio.c:175).
  *                        verbose != 0: stage times and peak device memory on stderr. */
 int64_t nabwa_index_fa2pac(const char *fasta, const char *prefix);
 int64_t nabwa_index_fa2cspac(const char *fasta, const char *prefix);

@@ -29,7 +29,8 @@
  * base-4 digits, first one most significant; l = DEEP_KEYL | its length t) instead of the string's rows.  Its four possible extensions are
  * 32 consecutive bytes of level t + 1 of the table: one load instead of the rank query's two buckets, and no counting.  Rows are taken from
  * the table where the reference's results show them: a hit, level T, an exact tail (one jump down to level T), the occurrence test of a
- * deletion's extension.  An index of 0xffffff00 rows or more is searched without it (the host sets key_T = 0), so l tells the forms apart. */
+ * deletion's extension.  An index of 0xffffff00 rows or more is searched without it (the host sets key_T = 0): there a row-form l may reach
+ * the marker, so every test of the form checks key_T != 0 as well as l >= DEEP_KEYL. */
 #define DEEP_KEYL 0xffffff00u
 #define DEEP_LVO(t_) ((0x55555555u & ((1u << (2u * (t_) - 2u)) - 1u)) << 2)      /* entries in front of level t of the table, 1 <= t <= 16: (4^t - 4) / 3 */
 #define DEEP_LDS_WORDS(ns_, rd_) (2u * (((ns_) + 1u) & ~1u) + DEEP_NEWP + 256u + DEEP_BC_WORDS + ((rd_) + 3u) / 4u)

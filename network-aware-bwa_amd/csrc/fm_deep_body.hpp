@@ -361,7 +361,7 @@ DEEP_FN void deep_wave_body(const DeepParams &P_, uint32_t *lds, uint32_t wave
 							{
 								// ---- expansion (bwtgap.c:201-260)
 								const int i = E.i - 1;
-								const bool kf = E.l >= DEEP_KEYL;                                // key form: the four extensions come out of the table
+								const bool kf = KT && E.l >= DEEP_KEYL;                          // key form: the four extensions come out of the table
 								const uint32_t kt = E.l & 0xffu;
 								uint32_t occ;
 								uint32_t nk0, nl0, nk1, nl1, nk2, nl2, nk3, nl3;
@@ -516,7 +516,7 @@ DEEP_FN void deep_wave_body(const DeepParams &P_, uint32_t *lds, uint32_t wave
 				// (an entry in key form first takes its rows from the table: a tail jumps as far down as the table goes -- min(T - t, i) symbols
 				// for one load --, a hit takes the rows of its own string)
 				LANES {
-					const bool kf = L(e).l >= DEEP_KEYL;
+					const bool kf = KT && L(e).l >= DEEP_KEYL;
 					L(ts) = L(flag) == DF_TAIL ? (kf ? 5 : ((text_ok && L(e).k == L(e).l) ? 1 : 0)) : (L(flag) == DF_HIT && kf ? 6 : (L(flag) == DF_COOP && kf ? 10 : (L(flag) == DF_RUN || L(flag) == DF_COOP ? 7 : -1)));
 				}
 				while (WBALLOT(L(ts) >= 0 && L(ts) != 10) != 0ull) {
@@ -647,7 +647,7 @@ DEEP_FN void deep_wave_body(const DeepParams &P_, uint32_t *lds, uint32_t wave
 							LANES { L(tu) = L(e).l; } const uint32_t cl0 = WUNI(WBCAST(tu, j));
 							// the chain stands on one row (its levels come out of the text) or in key form (out of the interval table: level d's string is the
 							// entry's and the read's next d symbols, its four possible extensions 32 bytes of the next table level -- down to the table's depth)
-							const bool ckf = cl0 >= DEEP_KEYL;
+							const bool ckf = KT && cl0 >= DEEP_KEYL;
 							const uint32_t kt0 = cl0 & 0xffu;
 							const uint32_t zlast = ckf ? (KT - 1u - kt0 < 63u ? KT - 1u - kt0 : 63u) : 63u;
 							LANES { L(tu) = (uint32_t)L(e).i; } const int ci = (int)WUNI(WBCAST(tu, j));
@@ -792,7 +792,7 @@ DEEP_FN void deep_wave_body(const DeepParams &P_, uint32_t *lds, uint32_t wave
 						}
 					}
 				}
-				if (WBALLOT(L(act) || L(flag) == DF_TAIL || (L(flag) == DF_HIT && L(e).l >= DEEP_KEYL)) == 0ull) break;      // (a hit found here in key form still takes its rows from the table: the tails' loop once more)
+				if (WBALLOT(L(act) || L(flag) == DF_TAIL || (L(flag) == DF_HIT && KT && L(e).l >= DEEP_KEYL)) == 0ull) break;      // (a hit found here in key form still takes its rows from the table: the tails' loop once more)
 				if (prof) { pc1 = DEEP_CLOCK(); ph_tail += pc1 - pc2; }
 				}
 
@@ -876,7 +876,7 @@ DEEP_FN void deep_wave_body(const DeepParams &P_, uint32_t *lds, uint32_t wave
 						// the children of a parent in key form stay in it while the table has a level below theirs (a deletion or a mismatch over x: the
 						// parent's string and x); the insertion child has its parent's string
 						const uint32_t kt1 = (r2.y & 0xffu) + 1u;
-						const bool kfc = r2.y >= DEEP_KEYL && kt1 < KT;
+						const bool kfc = KT && r2.y >= DEEP_KEYL && kt1 < KT;
 						const uint32_t ckey = r2.x << 2, clen = DEEP_KEYL | kt1;
 						if (grp) {                                    // the gap group: [the insertion,] [the deletions over the symbols that occur]
 							const uint32_t gT = gcn == 0u ? cT0 : (gcn == 1u ? cT1 : cT2), gO = gcn == 0u ? ot0 : (gcn == 1u ? ot1 : ot2);

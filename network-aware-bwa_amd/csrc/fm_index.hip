@@ -33,10 +33,10 @@ __global__ __launch_bounds__(256) void repack_kernel(const uint32_t *__restrict_
 	for (uint32_t g = 0; g < 3; ++g) {
 		// 64 rows = 4 reference words, each 16 bases
 		for (uint32_t q = 0; q < 4; ++q) {
-			const uint32_t j = j0 + g * 64u + q * 16u;
+			const uint64_t j = (uint64_t)j0 + g * 64u + q * 16u;      // 64 bits: the last bucket's rows reach past 2^32 - 1 when seq_len > 2^32 - 177
 			if (j >= seq_len) break;
 			const uint32_t x = w[(size_t)(j >> 7) * 12 + 4 + ((j & 127u) >> 4)];
-			const uint32_t nb = seq_len - j < 16u ? seq_len - j : 16u;
+			const uint32_t nb = seq_len - j < 16u ? (uint32_t)(seq_len - j) : 16u;
 			for (uint32_t t = 0; t < nb; ++t) {
 				const uint32_t c = x >> ((15u - t) << 1) & 3u;
 				lo[g] |= (uint64_t)(c & 1u) << (q * 16u + t);

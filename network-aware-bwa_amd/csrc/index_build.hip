@@ -35,7 +35,7 @@
 #define IX_GRID(n) dim3((unsigned)(((n) + 255) / 256 < 65536 * 16 ? ((n) + 255) / 256 : 65536 * 16)), dim3(256)
 #define IX_FOR_ALL(i, n) for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < (n); i += (size_t)gridDim.x * 256)
 #define KCH 29                               // bases in the first sort key: 58 bits + 5 bits of "valid" count
-#define IX_MAX_N 0xFFFFFFEFull               // longest text the u32 rows can hold (n + 1 rows, row values up to n)
+#define IX_MAX_N 0xFFFFFF80ull               // longest text the reference indexes: above it n_occ = (n + 127)/128 + 1 wraps in 32 bits (bwtmisc.c:131)
 
 static int ix_fail(int code, const std::string &m) { return nabwa_fail(code, "%s", m.c_str()); }
 static int ix_hip(hipError_t e, const char *what, int line)
@@ -384,6 +384,16 @@ extern "C" int nabwa_index_build(const char *prefix, int device, int sa_intv, in
 		if (!fp) return ix_fail(NABWA_EIO, "cannot open '" + pre + ".pac'");
 		fseek(fp, 0, SEEK_END);
 		const long sz = ftell(fp);
+		// the length from the file's size and last byte first: a text too long is refused before its bases are read
+		int last = -1;
+		if (sz >= 2 && fseek(fp, sz - 1, SEEK_SET) == 0) last = fgetc(fp);
+		if (last >= 0 && last <= 3 && (uint64_t)(sz - 2) * 4 + (uint64_t)last > IX_MAX_N) {
+			fclose(fp);
+			char b[200];
+			snprintf(b, sizeof b, "a text of %lld bases is too long: the reference's 32-bit Occ count (bwtmisc.c:131) holds at most %llu bases",
+					 (long long)((int64_t)(sz - 2) * 4 + last), (unsigned long long)IX_MAX_N);
+			return ix_fail(NABWA_EINVAL, b);
+		}
 		fseek(fp, 0, SEEK_SET);
 		if (sz > 0) pac.resize((size_t)sz);
 		const bool ok = sz > 0 && fread(pac.data(), 1, (size_t)sz, fp) == (size_t)sz;
@@ -395,8 +405,14 @@ extern "C" int nabwa_index_build(const char *prefix, int device, int sa_intv, in
 		return ix_fail(NABWA_EIO, "'" + pre + ".pac' is malformed (its last byte does not match its size)");
 	if ((uint64_t)l_pac > IX_MAX_N) {
 		char b[200];
-		snprintf(b, sizeof b, "a text of %lld bases is too long for the GPU builder: its 32-bit suffix array holds at most %llu bases",
+		snprintf(b, sizeof b, "a text of %lld bases is too long: the reference's 32-bit Occ count (bwtmisc.c:131) holds at most %llu bases",
 				 (long long)l_pac, (unsigned long long)IX_MAX_N);
+		return ix_fail(NABWA_EINVAL, b);
+	}
+	if ((uint64_t)l_pac + (uint64_t)sa_intv > 0xffffffffull) {      // the reference's loader would wrap n_sa (bwtio.c:175): no files it can read
+		char b[200];
+		snprintf(b, sizeof b, "a text of %lld bases with sa_intv %d: the reference's 32-bit SA count (bwtio.c:175) wraps above 0xffffffff",
+				 (long long)l_pac, sa_intv);
 		return ix_fail(NABWA_EINVAL, b);
 	}
 	const size_t n = (size_t)l_pac;

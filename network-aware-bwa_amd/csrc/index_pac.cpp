@@ -178,6 +178,10 @@ static int read_fasta(const char *fasta, Packed &P)
 	if (P.l_pac == 0) return fail_msg(NABWA_EINVAL, std::string("'") + fasta + "' holds no bases (the reference aborts: zero length sequence)");
 	if (P.l_pac > 0xffffffffLL)
 		return fail_msg(NABWA_EINVAL, "the reference is longer than 4 Gbp in total; BWA only works with reference sequences shorter than 4GB (bwtindex.c:103)");
+	/* the reference's own builder wraps above this: n_occ = (seq_len + 127)/128 + 1 in 32 bits (bwtmisc.c:131), so there are no
+	 * reference files to be identical to (and its SA loader, bwtio.c:175, wraps above 0xffffffdf) */
+	if (P.l_pac > 0xffffff80LL)
+		return fail_msg(NABWA_EINVAL, "the reference is longer than 4 294 967 168 bases; BWA's Occ count wraps above that (bwtmisc.c:131)");
 	pac_tail(P.pac, P.l_pac);
 	return 0;
 }

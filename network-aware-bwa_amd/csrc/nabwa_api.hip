@@ -106,6 +106,8 @@ static int build_one(nabwa_index *ix, int t_, const uint32_t *words, uint64_t n_
 	DevBwt &B = ix->bwt[t_];
 	memset(&B, 0, sizeof(B));
 	B.primary = hdr[0]; B.L2[0] = 0; B.L2[1] = hdr[1]; B.L2[2] = hdr[2]; B.L2[3] = hdr[3]; B.seq_len = hdr[4];
+	/* the reference's loader computes n_sa = (seq_len + sa_intv) / sa_intv in 32 bits (bwtio.c:175, bwt.c:56): above this it wraps */
+	if (B.seq_len > 0xffffffdfu) return fail(NABWA_EINVAL, "seq_len above 0xffffffdf: the reference's SA count wraps (bwtio.c:175)");
 	/* (seq_len+15)/16 BWT words plus (seq_len+127)/128+1 checkpoints of 4 words (bwtmisc.c:130-131) */
 	const uint64_t expect = ((uint64_t)B.seq_len + 15) / 16 + (((uint64_t)B.seq_len + 127) / 128 + 1) * 4;
 	if (n_words - 5 < expect) return fail(NABWA_EIO, "bwt array shorter than its seq_len implies");
@@ -170,6 +172,10 @@ static int build_one(nabwa_index *ix, int t_, const uint32_t *words, uint64_t n_
 		if (on_device) HIP_CHECK(hipMemcpy(sh, sa_words, 28, hipMemcpyDeviceToHost)); else memcpy(sh, sa_words, 28);
 		if (sh[0] != B.primary || sh[6] != B.seq_len) return fail(NABWA_EIO, "SA-BWT inconsistency");   /* bwtio.c:169,173 */
 		B.sa_intv = sh[5];
+		/* n_sa = (seq_len + sa_intv) / sa_intv is 32-bit in the reference's loader (bwtio.c:175): 0xffffffdf above holds for its interval of
+		 * 32, a larger interval wraps sooner */
+		if (B.sa_intv < 1 || (uint64_t)B.seq_len + B.sa_intv > 0xffffffffull)
+			return fail(NABWA_EINVAL, "seq_len + sa_intv above 0xffffffff: the reference's SA count wraps (bwtio.c:175)");
 		B.n_sa = (uint32_t)(((uint64_t)B.seq_len + B.sa_intv) / B.sa_intv);
 		if (n_sa_words - 7 < (uint64_t)B.n_sa - 1) return fail(NABWA_EIO, "sa array shorter than n_sa");
 		HIP_CHECK(hipMalloc(&ix->sa[t_], (size_t)B.n_sa * 4));

@@ -34,7 +34,7 @@ void build(EmuBwt &X, const uint32_t *words)
 		uint64_t lo[3] = { 0, 0, 0 }, hi[3] = { 0, 0, 0 };
 		const uint32_t c0[4] = { cnt[0], cnt[1], cnt[2], cnt[3] };
 		for (uint32_t r = 0; r < NABWA_INTV; ++r) {
-			const uint32_t j = b * NABWA_INTV + r;
+			const uint64_t j = (uint64_t)b * NABWA_INTV + r;      // 64 bits, as repack_kernel: the last bucket's rows pass 2^32 - 1 when n > 2^32 - 193
 			if (j >= n) break;
 			const uint32_t c = ref_base(w, j);
 			++cnt[c];

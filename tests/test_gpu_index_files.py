@@ -12,20 +12,12 @@ import shutil
 import numpy as np
 import pytest
 
+import bigindex as BI
 import nabwa_testlib as T
 
 nabwa = importlib.import_module("network-aware-bwa_amd")
 synth = importlib.import_module("network-aware-bwa_amd.synth")
 pytestmark = pytest.mark.gpu
-
-
-def pack_pac(d_text, n):
-    t = d_text.to_host(np.uint8)[:n]
-    pad = (-n) % 4
-    if pad:
-        t = np.concatenate([t, np.zeros(pad, np.uint8)])
-    t = t.reshape(-1, 4)
-    return np.ascontiguousarray((t[:, 0] << 6) | (t[:, 1] << 4) | (t[:, 2] << 2) | t[:, 3]).astype(np.uint8)
 
 
 def test_genome_sized_index_from_reference_format_files(tmp_path_factory):
@@ -56,37 +48,13 @@ def run(n, prefix):
     want_sum = b.checksum()
     b.close(); ix.close()
     # ---- the same arrays as files of the reference's formats
-    for t, (bw, nbw, sa, nsa) in enumerate(parts):
-        bw.to_host(np.uint32, nbw).tofile(prefix + (".rbwt" if t else ".bwt"))        # primary, L2[1..4], then the Occ-interleaved BWT words (bwtio.c:184-204)
-        sa.to_host(np.uint32, nsa).tofile(prefix + (".rsa" if t else ".sa"))          # primary, 4 skipped words, sa_intv, seq_len, then the samples (bwtio.c:161-182)
-        bw.free(); sa.free()
-    pac = pack_pac(d_text, n)
+    BI.write_index_words(prefix, parts)
+    pac = BI.pack_pac(d_text, n)
     d_text.free()
-    with open(prefix + ".pac", "wb") as f:                                            # bntseq.c:240-250: the packed bases, a zero byte when they end on a byte border, the count of bases in the last byte
-        f.write(pac.tobytes())
-        if n % 4 == 0:
-            f.write(b"\0")
-        f.write(bytes([n % 4]))
+    BI.write_pac(prefix, pac, n)
     rng = np.random.default_rng(8)
     n_ctg = 240
-    cuts = np.sort(rng.choice(np.arange(1000, n - 1000), n_ctg - 1, replace=False))
-    offs = np.concatenate([[0], cuts]).astype(np.int64)
-    lens = np.diff(np.concatenate([offs, [n]])).astype(np.int64)
-    assert lens.max() < 2**31
-    names = ["ctg%03d" % i for i in range(n_ctg)]
-    hole_off = np.sort(rng.choice(np.arange(5000, n - 5000), 3000, replace=False)).astype(np.int64)
-    hole_len = rng.integers(1, 2000, 3000).astype(np.int64)
-    hole_len = np.minimum(hole_len, np.diff(np.concatenate([hole_off, [n]])) - 1)    # holes do not overlap
-    ctg_of_hole = np.searchsorted(offs, hole_off, side="right") - 1
-    with open(prefix + ".ann", "w") as f:                                             # bns_dump (bntseq.c:63-75)
-        f.write("%d %d %u\n" % (n, n_ctg, 11))
-        for i in range(n_ctg):
-            f.write("%d %s a synthetic contig\n" % (i, names[i]) if i % 3 else "%d %s\n" % (i, names[i]))
-            f.write("%d %d %d\n" % (offs[i], lens[i], int((ctg_of_hole == i).sum())))
-    with open(prefix + ".amb", "w") as f:
-        f.write("%d %d %d\n" % (n, n_ctg, 3000))
-        for o, l in zip(hole_off, hole_len):
-            f.write("%d %d N\n" % (o, l))
+    names, offs, lens, hole_off, hole_len, cuts = BI.write_ann_amb(prefix, n, rng, n_ctg, 3000)
     # ---- loaded from the files
     ix = nabwa.Index.load(prefix, 0, True, True)
     L = nabwa.lib()
@@ -131,39 +99,10 @@ def run(n, prefix):
     s_seq = np.concatenate([r[::-1] for r in reads]).astype(np.uint8)              # bwa_seq_t.seq: the read reversed; rseq: its complement
     s_rseq = (3 - s_seq).astype(np.uint8)
     s_off = np.arange(len(reads) + 1, dtype=np.int64) * 100
-    hits, _ = ix.cal_sa_reg_gap(opt, s_seq, s_rseq, s_off, per_read=True)
-    full = np.full(len(reads), 100, np.int32)
-    recs, _ = ix.se_finish(opt, s_seq, s_rseq, s_off, full, hits, 3, nabwa.srand48_state(11))
     ref.ref_index_load.restype = C.c_void_p
     ref.ref_index_load.argtypes = [C.c_char_p, C.c_int]
     rix = C.c_void_p(ref.ref_index_load(prefix.encode(), 1))
-    P = C.c_void_p
-    ref.ref_se_chain_mt.argtypes = [P, P, C.c_int, C.c_int, P, P, P, P, P, C.c_int, P, P, P, C.c_int, P]
-    ref.ref_pac2real.argtypes = [P, C.c_int64, C.c_int, P, P]
-    copt = T.GapOpt(); C.memmove(C.byref(copt), C.byref(opt), 64)
-    na = np.array([len(h) for h in hits], np.int32)
-    rows = np.ascontiguousarray(np.concatenate([np.asarray(h, nabwa.ALN_DT) for h in hits] + [np.zeros(0, nabwa.ALN_DT)]))
-    f = np.zeros((len(reads), 16), np.int64); cg = np.zeros((len(reads), 64), np.uint16); md = np.zeros((len(reads), 256), np.uint8)
-    secs = (C.c_double * 2)()
-    ref.ref_seed48(11)
-    ref.ref_se_chain_mt(rix, C.byref(copt), 3, len(reads), T.ptr(s_off), T.ptr(s_seq), T.ptr(s_rseq), T.ptr(na), T.ptr(rows), 4, T.ptr(f), T.ptr(cg), T.ptr(md), 256, secs)
-    n_map = n_hole = n_bridge = 0
-    for i in range(len(reads)):
-        s, w = recs[i], f[i]
-        assert s.type == w[0], i
-        if s.type == 0:
-            continue
-        n_map += 1
-        bridging = bool(s.flag & 4)
-        n_bridge += bridging
-        assert [s.strand, s.n_mm, s.n_gapo, s.n_gape, s.score, s.sa, s.c1, s.c2, s.pos] == [int(x) for x in w[1:10]], i
-        assert bridging or s.mapQ == w[10], i
-        assert s.n_cigar == w[12] and list(s.cigar[:s.n_cigar]) == list(cg[i, :s.n_cigar]) and s.nm == w[13], i
-        assert s.md == bytes(md[i]).split(b"\0", 1)[0], i           # N's of the holes restored in MD (bwase.c:243-268)
-        sid, o = C.c_int32(), C.c_int64()
-        ln = 100 if s.n_cigar == 0 else sum((c & 0x3fff) for c in s.cigar[:s.n_cigar] if (c >> 14) in (0, 2))
-        nn = ref.ref_pac2real(rix, int(s.pos), ln, C.byref(sid), C.byref(o))
-        assert (s.seqid, s.rpos, s.nn) == (sid.value, int(s.pos) - o.value + 1, nn), (i, s.seqid, s.rpos, s.nn, sid.value, o.value, nn)
-        n_hole += nn > 0
+    n_map, n_hole, n_bridge, _ = BI.se_chain_vs_reference(ix, ref, rix, opt, s_seq, s_rseq, s_off)
+    ref.ref_index_free(rix)
     assert n_map > 0.9 * len(reads) and n_hole >= 100 and n_bridge >= 20
     ix.close()

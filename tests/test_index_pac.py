@@ -124,3 +124,36 @@ def test_no_gpu_writes_nothing(tmp_path):
         r = subprocess.run([TOOL] + extra + ["-p", str(tmp_path / "toy"), os.path.join(T.GOLDEN, "toy.fa")], capture_output=True, timeout=120)
         assert r.returncode == 2 and b"no usable GPU" in r.stderr, r.stderr
         assert os.listdir(tmp_path) == []
+
+
+def poly_a_fasta_gz(path, rec_lens):
+    """a gzip FASTA of all-A records of the given lengths, written as one gzip member per MiB of bases (zlib reads them as one stream)"""
+    line = b"A" * 1023 + b"\n"
+    mib = gzip.compress(line * 1024, 1)                    # 1 MiB of bases in 1023-base lines (plus a short line per MiB)
+    with open(path, "wb") as f:
+        for i, n in enumerate(rec_lens):
+            f.write(gzip.compress(b">r%d\n" % i))
+            full, rest = divmod(n, 1023 * 1024)
+            for _ in range(full):
+                f.write(mib)
+            f.write(gzip.compress(b"A" * rest + b"\n", 1))
+
+
+def test_text_longer_than_the_reference_indexes_is_refused(tmp_path):
+    """above 0xffffff80 bases the reference's Occ count wraps (bwtmisc.c:131): fa2pac, fa2cspac and the command line refuse the text
+    before writing anything; 0xffffff80 itself is accepted (checked without writing: prefix NULL)"""
+    L = nabwa.lib()
+    big = str(tmp_path / "over.fa.gz")
+    poly_a_fasta_gz(big, [2**31 - 1, 0xffffff81 - (2**31 - 1)])           # records under 2^31 bases each (bntann1_t.len is an int)
+    for colour in (False, True):
+        with pytest.raises(nabwa.NabwaError) as e:
+            nabwa.index_fa2pac(big, str(tmp_path / "lib"), colour=colour)
+        assert e.value.code == nabwa.EINVAL and "bwtmisc.c:131" in str(e.value), str(e.value)
+    r = subprocess.run([TOOL, "-p", str(tmp_path / "cli"), big], capture_output=True, timeout=600)
+    assert r.returncode == 1 and b"bwtmisc.c:131" in r.stderr, r.stderr
+    assert os.listdir(tmp_path) == ["over.fa.gz"]
+    os.remove(big)
+    edge = str(tmp_path / "edge.fa.gz")
+    poly_a_fasta_gz(edge, [2**31 - 1, 0xffffff80 - (2**31 - 1)])
+    assert L.nabwa_index_fa2pac(edge.encode(), None) == 0xffffff80
+    assert os.listdir(tmp_path) == ["edge.fa.gz"]

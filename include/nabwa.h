@@ -199,7 +199,8 @@ void nabwa_dp_scratch_release(int device);
 
 /* tests, diagnostics: launches of the alignment kernels by form since the library was loaded, each picked per launch from the
  * batch's largest task: [0] global, one wavefront per task; [1] global, lanes with rows in LDS; [2] global, lanes with rows in
- * HBM; [3] local, rows in LDS; [4] local, rows in HBM.  Writes min(n, 5) counts. */
+ * HBM; [3] local, rows in LDS; [4] local, rows in HBM; [5] extension, rows in LDS; [6] extension, rows in HBM.  Writes min(n, 7)
+ * counts. */
 void nabwa_dp_form_counts(uint64_t *out, int n);
 
 /* Batch form of aln_extend_core (stdaln.c:862-1007): left-anchored extension seeded with G0[i], then the

@@ -213,9 +213,10 @@ def extend_align(ref, ref_off, qry, qry_off, gap_open, gap_ext, matrix25, band, 
 
 def dp_form_counts():
     """launches of the alignment kernels by form since the library was loaded (nabwa_dp_form_counts):
-    global wave / global LDS lanes / global HBM lanes / local rows in LDS / local rows in HBM"""
-    out = (C.c_uint64 * 5)()
-    lib().nabwa_dp_form_counts(out, 5)
+    global wave / global LDS lanes / global HBM lanes / local rows in LDS / local rows in HBM / extension rows in LDS /
+    extension rows in HBM"""
+    out = (C.c_uint64 * 7)()
+    lib().nabwa_dp_form_counts(out, 7)
     return list(out)
 
 

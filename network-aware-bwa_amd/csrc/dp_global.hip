@@ -75,7 +75,7 @@ __global__ __launch_bounds__(LDSV ? DP_SMALL_LANES : 256) void dp_global_kernel(
 		const int left = j > b2 ? j - b2 : 0, right = j + b1 - 1 < l1 ? j + b1 - 1 : l1;
 		const int *mat = P.matrix + s2[j - 1] * 5;
 		const int mt0 = mat[0], mt1 = mat[1], mt2 = mat[2], mt3 = mat[3], mt4 = mat[4];      // this row's scores against A, C, G, T, N
-		const int dpen = j == l2 ? end_pen : gap_ext;
+		const int dpen = j == l2 && !(b2 == 1 && l2 > 1) ? end_pen : gap_ext;       // b2 == 1: the last row is a middle row (stdaln.c:443)
 		int cm_l = NINF, cd_l = NINF;          // M and D of the cell to the left in this row
 		ROW(0, cur, left) = NINF; ROW(1, cur, left) = NINF; ROW(2, cur, left) = NINF; TBC(j, left) = 0;
 		if (left == 0) {                       // column 0: end-gap insertion chain
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(64) void dp_global_wave_kernel(const DpParams P)
 		const int left = j > b2 ? j - b2 : 0, right = j + b1 - 1 < l1 ? j + b1 - 1 : l1;
 		const int *const mat = P.matrix + w2[j - 1] * 5;
 		const int mt0 = mat[0], mt1 = mat[1], mt2 = mat[2], mt3 = mat[3], mt4 = mat[4];
-		const int dpen = j == l2 ? end_pen : gap_ext;
+		const int dpen = j == l2 && !(b2 == 1 && l2 > 1) ? end_pen : gap_ext;       // b2 == 1: the last row is a middle row (stdaln.c:443)
 		uint8_t *const tbr = tb + (size_t)j * WH;
 		if (lane == 0) {
 			RW(0, cur, left) = NINF; RW(1, cur, left) = NINF; RW(2, cur, left) = NINF; tbl[j] = 0;
@@ -333,11 +333,11 @@ __global__ __launch_bounds__(64) void dp_global_wave_kernel(const DpParams P)
 #undef TBW
 }
 
-/* launches by form (nabwa_dp_form_counts): [0..2] here, [3..4] in dp_wave.hip */
-std::atomic<uint64_t> g_dp_form_count[5];
+/* launches by form (nabwa_dp_form_counts): [0..2] here, [3..6] in dp_wave.hip */
+std::atomic<uint64_t> g_dp_form_count[7];
 extern "C" void nabwa_dp_form_counts(uint64_t *out, int n)
 {
-	for (int i = 0; i < n && i < 5; ++i) out[i] = g_dp_form_count[i].load();
+	for (int i = 0; i < n && i < 7; ++i) out[i] = g_dp_form_count[i].load();
 }
 
 extern "C" void nabwa_launch_dp_global(const DpParams *P, hipStream_t s)

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(64) void dp_local_wave_kernel(const LocParams P)
 	if (lane == 0) { out[1] = score_r + base - qr; out[2] = start_i; out[3] = start_j; }
 }
 
-extern std::atomic<uint64_t> g_dp_form_count[5];      /* launches by form (dp_global.hip) */
+extern std::atomic<uint64_t> g_dp_form_count[7];      /* launches by form (dp_global.hip) */
 extern "C" size_t nabwa_dp_local_rows_bytes(int W) { return (size_t)W * 8; }      // HBM form: per task
 extern "C" int nabwa_dp_local_fits_lds(int W)
 {
@@ -316,6 +316,6 @@ __global__ __launch_bounds__(64) void dp_extend_wave_kernel(const ExtParams P)
 extern "C" void nabwa_launch_dp_extend_fwd(const ExtParams *P, hipStream_t s)
 {
 	if (P->n <= 0) return;
-	if (nabwa_dp_local_fits_lds(P->W)) hipLaunchKernelGGL(dp_extend_wave_kernel<false>, dim3(P->n), dim3(64), (size_t)P->W * 9 + 16, s, *P);
-	else hipLaunchKernelGGL(dp_extend_wave_kernel<true>, dim3(P->n), dim3(64), 0, s, *P);
+	if (nabwa_dp_local_fits_lds(P->W)) { hipLaunchKernelGGL(dp_extend_wave_kernel<false>, dim3(P->n), dim3(64), (size_t)P->W * 9 + 16, s, *P); ++g_dp_form_count[5]; }
+	else { hipLaunchKernelGGL(dp_extend_wave_kernel<true>, dim3(P->n), dim3(64), 0, s, *P); ++g_dp_form_count[6]; }
 }

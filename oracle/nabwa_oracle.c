@@ -626,7 +626,7 @@ int orc_global(const uint8_t *s1, int l1, const uint8_t *s2, int l2, int gap_ope
 		int *cm = M[j&1], *ci = I[j&1], *cd = D[j&1], *pm = M[(j-1)&1], *pi = I[(j-1)&1], *pd = D[(j-1)&1];
 		int left = j > b2 ? j - b2 : 0, right = j + b1 - 1 < l1 ? j + b1 - 1 : l1;
 		const int *mat = matrix + s2[j-1] * row;
-		const int dpen = (j == l2) ? end_pen : gap_ext;
+		const int dpen = (j == l2 && !(b2 == 1 && l2 > 1)) ? end_pen : gap_ext;   /* b2 == 1: part 2 takes the last row, set_D (stdaln.c:443) */
 		uint8_t *t = tb + (size_t)j * W;
 		cm[left] = ci[left] = cd[left] = NINF;
 		if (left == 0) {   /* column 0: end-gap insertion chain */

@@ -8,10 +8,14 @@ index resident in HBM.  With --gpus N every rank holds a replica of the index an
 (no collective on the data path; weak scaling).  `python bench.py --gpus N` without a launcher around it starts
 its N ranks itself (a torch.distributed.run child, before anything touches a GPU) and relays rank 0's line.
 
-Prints ONE JSON line on rank 0 with `roofline` (algorithmic Occ-bucket bytes / HIP-event kernel time
-vs. the 8 TB/s HBM peak), `cpu_baseline` (the reference's own compiled code, oracle/_ref, on the
-host cores of this box, on a bounded sample of the same reads), `e2e` (BAM records in -> BAM records out) and, at full
-size, `workloads`: BASELINE configs 5 (--adna) and 3 (--pe) and the repeat-family genome (--repeats) after the headline
+A plain run does what the headline figure needs and nothing else: it builds the index and the reads, warms up, times the
+steps, writes --dump-outputs, compares the GPU rows of a fixed sample of the reads bit for bit with the reference's own compiled
+code (oracle/_ref; what the metric's "bit-exact vs CPU" says) and prints ONE JSON line on rank 0 (the kernels' HIP-event times in
+`roofline`, the counter pass of profiles/ under `roofline.traffic`).  With --full the same line also carries what takes runs of
+its own: the PCIe-inclusive rates, `roofline` achieved / frac (algorithmic Occ-bucket bytes of an untimed instrumented run /
+HIP-event kernel time vs. the 8 TB/s HBM peak), `cpu_baseline` (that code's rate on the host cores, on a sample of the same reads
+sized by --cpu-seconds, which is then the one compared), `e2e` (BAM records in -> BAM records out), the streamed PE steps and, at
+full size, `workloads`: BASELINE configs 5 (--adna) and 3 (--pe) and the repeat-family genome (--repeats) after the headline
 steps, each with its own value / roofline / cpu_baseline / bit-exact sample.
 """
 import argparse
@@ -46,8 +50,11 @@ def parse_args():
     ap.add_argument("--read-len", type=int, default=100)
     ap.add_argument("--sub-ppm", type=int, default=2000)
     ap.add_argument("--indel-ppm", type=int, default=0, help="per-base indel rate of the synthetic reads (not part of the headline workload)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need (see the options below that "
+                    "say --full): PCIe-inclusive rates, CPU baselines (their sample is then the one compared bit for bit), the instrumented run behind the roofline figures, "
+                    "the e2e leg, the streamed PE steps and the other workloads")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: time budget of the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="no CPU baseline and no bit-exact sample check")
     ap.add_argument("--adna", action="store_true", help="SURVEY 8d config C5 instead of the headline workload: reads of 50-76 bases with "
                     "terminal deamination (5' C>T, 3' G>A, 30 %% decaying by 0.7 per base) + 1 %% substitutions, searched with -n 0.01 -o 2 -l 16500")
     ap.add_argument("--repeats", action="store_true", help="the genome with GRCh38-like repeat families (LINE-like, Alu-like with a young subfamily, tandem repeats; "
@@ -55,11 +62,11 @@ def parse_args():
     ap.add_argument("--pe", action="store_true", help="BASELINE config 3 instead of the headline workload: 2 x 150 bp pairs at 2 %% substitutions, 10 %% of the reads with "
                     "a 1-base indel, inserts ~ N(400, 40): FM search of both ends + posn_pair + insert-size estimate + finish_pair; value = pairs/s")
     ap.add_argument("--pairs", type=int, default=int(os.environ.get("NABWA_BENCH_PAIRS", 1_000_000)))
-    ap.add_argument("--no-e2e", action="store_true", help="skip the BAM-records-in -> BAM-records-out leg of the headline run")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the BAM-records-in -> BAM-records-out leg of the headline run")
     ap.add_argument("--e2e-reads", type=int, default=1_000_000)
     ap.add_argument("--pipeline", action="store_true", help="steps alternate between two device-resident batches on two streams (not the headline mode)")
-    ap.add_argument("--extras", choices=["auto", "on", "off"], default="auto", help="after the headline steps also run configs 5 (--adna), 3 (--pe) and the repeat-family "
-                    "genome and attach them under `workloads` (auto: at the full genome size only)")
+    ap.add_argument("--extras", choices=["auto", "on", "off"], default="auto", help="--full: after the headline steps also run configs 5 (--adna), 3 (--pe) and the "
+                    "repeat-family genome and attach them under `workloads` (auto: at the full genome size only)")
     ap.add_argument("--extra-steps", type=int, default=2, help="timed steps of each extra workload (one warm-up step before them)")
     ap.add_argument("--extra-adna-reads", type=int, default=6_250_000, help="config 5's share of one GPU: 50 M reads over 8 GPUs")
     ap.add_argument("--extra-repeat-reads", type=int, default=10_000_000)
@@ -69,6 +76,8 @@ def parse_args():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.extras == "on" and not args.full:
+        ap.error("--extras on needs --full")
     return args
 
 
@@ -128,13 +137,14 @@ def main():
     import nabwa_testlib as T
     ctx.T = T
     ctx.want_cpu = rank == 0 and not args.no_cpu
-    # a CPU leg is taken on rank 0 at N = 1 only (at N > 1 the host cores are the ranks'); the bit-exact sample check stays on at any N
+    # a CPU leg is taken on rank 0 at N = 1 only (at N > 1 the host cores are the ranks'); the bit-exact sample check stays on at any N.
+    # Without --full the leg is that check alone, on a fixed sample of CHECK_READS reads (CHECK_PAIRS pairs), and reports no CPU rate.
     t_start = time.time()
 
     single = args.pe or args.adna or args.repeats
-    extras = [] if (single or args.pipeline or quick_env() or args.extras == "off" or (args.extras == "auto" and args.genome_len != GRCH38_LEN)) \
+    extras = [] if (not args.full or single or args.pipeline or quick_env() or args.extras == "off" or (args.extras == "auto" and args.genome_len != GRCH38_LEN)) \
         else ["adna", "pe", "repeats"]
-    want_e2e = not args.no_e2e and not args.adna and not args.pe and not quick_env()
+    want_e2e = args.full and not args.no_e2e and not args.adna and not args.pe and not quick_env()
     need_ref = args.pe or want_e2e or "pe" in extras
     G = build_genome(ctx, args.genome_len, args.repeats, need_ref)
     if args.pe:
@@ -242,7 +252,9 @@ def se_workload(ctx, G, kind, n_reads, steps, warmup, primary, cpu_seconds, want
     t_pcie = t_pcie_first = None
     n_pc = 0
     if primary:
-        # one end-to-end pass over host buffers (upload + both kernels + compacted download): the PCIe-inclusive rate
+        # one end-to-end pass over host buffers (upload + both kernels + compacted download): the PCIe-inclusive rate.  A plain run makes the
+        # first call as well, untimed: it loads the kernels' code objects and leaves its working buffers in the index's pool, where the batch
+        # below and kernel D's pages come from, so no step waits for a hipMalloc (--warmup 0 included)
         ix.cal_sa_reg_gap_flat(opt, seq[:off[1000]], rseq[:off[1000]], off[:1001], per_read=True)   # (loads the kernels' code objects once)
         torch.cuda.synchronize()
         n_pc = 1000 if quick else n_reads
@@ -251,13 +263,14 @@ def se_workload(ctx, G, kind, n_reads, steps, warmup, primary, cpu_seconds, want
         _na, _rows, _maxe = ix.cal_sa_reg_gap_flat(opt, seq_pc, rseq_pc, off_pc, per_read=True)      # the C one-shot entry on host buffers
         t_pcie_first = time.time() - t_pcie_first           # first call: the working buffers come from hipMalloc
         del _na, _rows, _maxe
-        t_pcie = time.time()
-        _na, _rows, _maxe = ix.cal_sa_reg_gap_flat(opt, seq_pc, rseq_pc, off_pc, per_read=True)      # what a streaming caller sees: buffers from the index's pool
-        t_pcie = time.time() - t_pcie
-        if rank == 0 and os.environ.get("NABWA_BENCH_MAXE"):          # how large the searches' stacks get (bwa_seq_t.max_entries)
-            log("max_entries: percentiles 50/90/99/99.9/100 = %s; reads over 1024/4096/16384/65536/262144: %s"
-                % (np.percentile(_maxe, [50, 90, 99, 99.9, 100]).tolist(), [int((_maxe > c).sum()) for c in (1024, 4096, 16384, 65536, 262144)]))
-        del _na, _rows, _maxe
+        if args.full:
+            t_pcie = time.time()
+            _na, _rows, _maxe = ix.cal_sa_reg_gap_flat(opt, seq_pc, rseq_pc, off_pc, per_read=True)      # what a streaming caller sees: buffers from the index's pool
+            t_pcie = time.time() - t_pcie
+            if rank == 0 and os.environ.get("NABWA_BENCH_MAXE"):          # how large the searches' stacks get (bwa_seq_t.max_entries)
+                log("max_entries: percentiles 50/90/99/99.9/100 = %s; reads over 1024/4096/16384/65536/262144: %s"
+                    % (np.percentile(_maxe, [50, 90, 99, 99.9, 100]).tolist(), [int((_maxe > c).sum()) for c in (1024, 4096, 16384, 65536, 262144)]))
+            del _na, _rows, _maxe
     batch = nabwa.Batch(ix, opt, seq, rseq, off, per_read=True)
 
     # Optional double buffering, as a streaming worker does: a second device-resident copy of the batch on its own stream.  Steps
@@ -306,9 +319,10 @@ def se_workload(ctx, G, kind, n_reads, steps, warmup, primary, cpu_seconds, want
         e2e = e2e_leg(ctx, G, opt, seq, rseq, off, read_len)
     out = None
     if rank == 0:
-        # ---- roofline of the dominant kernel (fm_search, first pass): algorithmic bytes / event time
-        t_search, t_width = (0, 0) if quick else batch.count_touches()
-        instrumented_same = True if quick else batch.checksum() == (checksum, n_rows)      # the untimed touch-counting run (tables and text mode off) must give the same rows
+        # ---- roofline of the dominant kernel (fm_search, first pass): algorithmic bytes (--full) / event time
+        counted = args.full and not quick
+        t_search, t_width = batch.count_touches() if counted else (0, 0)
+        instrumented_same = batch.checksum() == (checksum, n_rows) if counted else True      # the untimed touch-counting run (tables and text mode off) must give the same rows
         if not instrumented_same:
             log("ERROR: the instrumented run's rows differ from the timed run's (checksum %016x / %d rows vs %016x / %d): no roofline figure is reported"
                 % (batch.checksum() + (checksum, n_rows)))
@@ -322,30 +336,35 @@ def se_workload(ctx, G, kind, n_reads, steps, warmup, primary, cpu_seconds, want
         bytes_alg = 48 * t_search + half_reads + 16 * n_rows
         bytes_w = 48 * t_width + half_reads
         achieved = bytes_alg / (k_ms * 1e-3) / 1e9
-        full = n == GRCH38_LEN and read_len == (76 if adna else 100) and sub_ppm == (10000 if adna else 2000) and indel_ppm == 0
-        traffic = pmc_traffic(kind, n_reads) if full else None
-        roofline = {"bound": "hbm", "achieved": round(achieved, 2) if instrumented_same else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 5) if instrumented_same else None,
+
+        def fig(x, nd, ok=True):                # figures from the instrumented run's touch counts: --full only
+            return round(x, nd) if args.full and ok else None
+        full_size = n == GRCH38_LEN and read_len == (76 if adna else 100) and sub_ppm == (10000 if adna else 2000) and indel_ppm == 0
+        traffic = pmc_traffic(kind, n_reads) if full_size else None
+        roofline = {"bound": "hbm", "achieved": fig(achieved, 2, instrumented_same), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": fig(achieved / HBM_PEAK_GBS, 5, instrumented_same),
                     "traffic": traffic,
                     "kernel": ("fm_deep_kernel (one search per wavefront) + fm_search_kernel<false,false> before it" if deep else
                                "fm_search_kernel<false,false> (one read per lane) + fm_deep_kernel for the searches it hands on"),
                     "kernel_ms": round(k_ms, 3), "search_kernel_ms": round(s_ms, 3), "deep_kernel_ms": round(d_ms, 3),
                     "note": "achieved = the REFERENCE algorithm's bucket bytes / kernel time (an effective rate: the interval tables and text mode skip most of those touches); "
-                            "traffic = HBM bytes per launch the counters saw in the committed pass of this kernel version (profiles/), null where none was taken",
-                    "bytes_per_read": round(bytes_alg / n_reads, 1),
-                    "bucket_touches_per_read": round(t_search / n_reads, 1),
+                            "traffic = HBM bytes per launch the counters saw in the committed pass of this kernel version (profiles/), null where none was taken; "
+                            "the byte and touch figures count the touches in an untimed instrumented run, null without --full",
+                    "bytes_per_read": fig(bytes_alg / n_reads, 1),
+                    "bucket_touches_per_read": fig(t_search / n_reads, 1),
                     "width_kernel": {"kernel": "fm_width_kernel<false>", "kernel_ms": round(w_ms, 3),
-                                     "achieved": round(bytes_w / (w_ms * 1e-3) / 1e9, 2),
-                                     "frac": round(bytes_w / (w_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                                     "bucket_touches_per_read": round(t_width / n_reads, 1)},
+                                     "achieved": fig(bytes_w / (w_ms * 1e-3) / 1e9, 2),
+                                     "frac": fig(bytes_w / (w_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                     "bucket_touches_per_read": fig(t_width / n_reads, 1)},
                     "both_kernels": {"ms": round(k_ms + w_ms, 3),
-                                     "achieved": round((bytes_alg + bytes_w) / ((k_ms + w_ms) * 1e-3) / 1e9, 2),
-                                     "frac": round((bytes_alg + bytes_w) / ((k_ms + w_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}}
+                                     "achieved": fig((bytes_alg + bytes_w) / ((k_ms + w_ms) * 1e-3) / 1e9, 2),
+                                     "frac": fig((bytes_alg + bytes_w) / ((k_ms + w_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}}
         cpu = None
         bit_exact = None
         if ctx.want_cpu:
-            cpu, bit_exact = cpu_baseline(T, G.host_bwt, opt, seq, rseq, off, timed_rows, cpu_seconds if world == 1 else min(cpu_seconds, 3.0))
-            if world > 1:
+            cpu, bit_exact = cpu_baseline(T, G.host_bwt, opt, seq, rseq, off, timed_rows,
+                                          (cpu_seconds if world == 1 else min(cpu_seconds, 3.0)) if args.full else 0.0)
+            if world > 1 or not args.full:
                 cpu = None          # reported at N = 1 only: at N > 1 the host cores belong to the ranks (the sample check above stays)
         reads_per_s = n_reads * world * steps / elapsed
         what = "50-76 bp damaged SE, ancient-DNA options" if adna else "%d bp SE" % read_len
@@ -370,8 +389,9 @@ def se_workload(ctx, G, kind, n_reads, steps, warmup, primary, cpu_seconds, want
                           "bit_exact_vs_cpu_sample": bit_exact, "instrumented_run_same_rows": instrumented_same},
                "roofline": roofline, "cpu_baseline": cpu}
         if primary:
-            out["config"]["pcie_inclusive_reads_per_s"] = round(n_pc / t_pcie, 1)
-            out["config"]["pcie_inclusive_first_call_reads_per_s"] = round(n_pc / t_pcie_first, 1)
+            if args.full:
+                out["config"]["pcie_inclusive_reads_per_s"] = round(n_pc / t_pcie, 1)
+                out["config"]["pcie_inclusive_first_call_reads_per_s"] = round(n_pc / t_pcie_first, 1)
             out["e2e"] = e2e
     for b in batches:
         b.close()
@@ -758,7 +778,7 @@ def pe_workload(ctx, G, N, steps, warmup, cpu_seconds):
     # the same steps as a stream: the next batch's search runs on the GPU (nabwa_batch_run returns at once) while the host finishes this one -- two
     # batch objects over the same resident reads, taken in turn; the results of every step are the sequential step's
     streamed = None
-    if not quick_env() or os.environ.get("NABWA_BENCH_STREAM"):
+    if ctx.args.full and (not quick_env() or os.environ.get("NABWA_BENCH_STREAM")):
         batch2 = nabwa.Batch(ix, opt, seq, rseq, off, per_read=True)
         rec_buf2 = (nabwa.PeRec * (2 * N))()
         pair = [(batch, rec_buf, {}), (batch2, rec_buf2, {})]
@@ -811,22 +831,26 @@ def pe_workload(ctx, G, N, steps, warmup, cpu_seconds):
         return None
     sp = np.mean(splits, axis=0) * 1e3
     checksum, n_rows = batch.checksum()
-    t_search, t_width = (0, 0) if quick_env() else batch.count_touches()
-    instrumented_same = True if quick_env() else batch.checksum() == (checksum, n_rows)
+    full = ctx.args.full
+    counted = full and not quick_env()
+    t_search, t_width = batch.count_touches() if counted else (0, 0)
+    instrumented_same = batch.checksum() == (checksum, n_rows) if counted else True
     s_ms, w_ms, d_ms = [float(x) for x in np.mean(kms, axis=0)]
     bytes_alg = 48 * t_search + N * L + 16 * n_rows
     k_ms = s_ms + d_ms
-    roofline = {"bound": "hbm", "achieved": round(bytes_alg / (k_ms * 1e-3) / 1e9, 2) if instrumented_same else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(bytes_alg / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if instrumented_same else None,
+    have = full and instrumented_same                   # the byte and touch figures: --full only
+    roofline = {"bound": "hbm", "achieved": round(bytes_alg / (k_ms * 1e-3) / 1e9, 2) if have else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(bytes_alg / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if have else None,
                 "traffic": pmc_traffic("pe", N) if n == GRCH38_LEN else None,
                 "kernel": "fm_search_kernel<false,false> + fm_deep_kernel (bwt_match_gap of both ends)", "kernel_ms": round(k_ms, 3),
                 "search_kernel_ms": round(s_ms, 3), "deep_kernel_ms": round(d_ms, 3), "width_kernel_ms": round(w_ms, 3),
-                "bytes_per_read": round(bytes_alg / (2 * N), 1), "bucket_touches_per_read": round(t_search / (2 * N), 1),
-                "note": "the FM search is the dominant GPU kernel of the step; the finishing chain is host-bound (stage_ms)"}
+                "bytes_per_read": round(bytes_alg / (2 * N), 1) if full else None, "bucket_touches_per_read": round(t_search / (2 * N), 1) if full else None,
+                "note": "the FM search is the dominant GPU kernel of the step; the finishing chain is host-bound (stage_ms); "
+                        "the byte and touch figures count the touches in an untimed instrumented run, null without --full"}
     cpu, exact = None, None
     if ctx.want_cpu:
-        cpu, exact = pe_cpu_baseline(N, cpu_seconds if world == 1 else min(cpu_seconds, 3.0), nabwa, T, G.host_bwt, G.host_sa, G.pac, n, opt, seq, rseq, off, hits, recs, ii, L)
-        if world > 1:
+        cpu, exact = pe_cpu_baseline(N, (cpu_seconds if world == 1 else min(cpu_seconds, 3.0)) if ctx.args.full else 0.0, nabwa, T, G.host_bwt, G.host_sa, G.pac, n, opt, seq, rseq, off, hits, recs, ii, L)
+        if world > 1 or not ctx.args.full:
             cpu = None
     tp = np.frombuffer(recs, np.uint8).reshape(2 * N, C.sizeof(nabwa.PeRec))[:, nabwa.PeRec.se.offset + nabwa.SeRec.type.offset]
     out = {"metric": "aligned pairs/s to GRCh38 (2 x 150 bp PE at 2%% error), search + posn_pair + insert-size estimate + finish_pair%s%s"
@@ -853,7 +877,7 @@ def pe_workload(ctx, G, N, steps, warmup, cpu_seconds):
 def pe_cpu_baseline(n_pairs, cpu_seconds, nabwa, T, host_bwt, host_sa, pac, n, opt, seq, rseq, off, hits, recs, ii, L):
     """the reference's own functions on a bounded sample of the same pairs: bwa_cal_sa_reg_gap of both ends on all host threads
     (ref_cal_sa_reg_gap_mt), then posn_pair serially and finish_pair on all threads (ref_pe_chain_mt); the GPU records of the
-    sample are compared field for field"""
+    sample are compared field for field.  cpu_seconds 0: the check alone, on the first CHECK_PAIRS pairs"""
     cores = cpu_threads()
     ref, rix = ref_full_index(T, host_bwt, host_sa, pac, n)
     if ref is None:
@@ -879,9 +903,12 @@ def pe_cpu_baseline(n_pairs, cpu_seconds, nabwa, T, host_bwt, host_sa, pac, n, o
         assert tot >= 0
         return time.time() - t, na, rows[:tot]
 
-    pilot = 64 * cores
-    dt, _, _ = search(pilot)
-    n_s = int(min(n_pairs, max(pilot, pilot / max(dt, 1e-3) * cpu_seconds * 0.7)))
+    if cpu_seconds > 0:
+        pilot = 64 * cores
+        dt, _, _ = search(pilot)
+        n_s = int(min(n_pairs, max(pilot, pilot / max(dt, 1e-3) * cpu_seconds * 0.7)))
+    else:
+        n_s = min(n_pairs, CHECK_PAIRS)                # the sample check alone: a fixed sample
     t_search, na, rows = search(n_s)
     g_na, g_rows = hits
     b0 = np.concatenate([[0], np.cumsum(na)])
@@ -909,7 +936,8 @@ def pe_cpu_baseline(n_pairs, cpu_seconds, nabwa, T, host_bwt, host_sa, pac, n, o
         exact = exact and bool(same)
     ref.ref_pe_free(b)
     t_all = t_search + secs[0] + secs[1]
-    log("cpu baseline (reference): %d pairs on %d threads: search %.2f s, posn_pair %.2f s (serial, as in the reference), finish_pair %.2f s" % (n_s, cores, t_search, secs[0], secs[1]))
+    log("cpu %s (reference): %d pairs on %d threads: search %.2f s, posn_pair %.2f s (serial, as in the reference), finish_pair %.2f s"
+        % ("baseline" if cpu_seconds > 0 else "sample check", n_s, cores, t_search, secs[0], secs[1]))
     return {"value": round(n_s / t_all, 1), "unit": "pairs/s", "cores": cores, "kind": "reference",
             "sample": "first %d pairs of the same batch: bwa_cal_sa_reg_gap of both ends on %d threads (%.1f s), posn_pair serial (%.1f s), finish_pair on %d threads (%.1f s)"
                       % (n_s, cores, t_search, secs[0], cores, secs[1])}, exact
@@ -971,10 +999,15 @@ def pmc_traffic(kind, units):
 PMC_FILES = {"headline": ("r03_pmc.json", "r02_pmc.json"), "adna": ("r03_pmc_adna.json",), "pe": ("r03_pmc_pe.json",), "repeats": ("r03_pmc_repeats.json",)}
 
 
+CHECK_READS = 1 << 16          # without --full: reads (pairs) of the bit-exact sample check, which then takes no CPU rate
+CHECK_PAIRS = 1 << 12
+
+
 def cpu_baseline(T, host_bwt, opt, seq, rseq, off, timed_rows, cpu_seconds):
     """The reference's own bwa_cal_sa_reg_gap (oracle/_ref, compiled from /root/reference) on all host
     cores over a bounded sample of the same reads; falls back to the CPU restatement ("port") when the
-    compiled reference did not travel.  Also checks the GPU rows of the sample bit-for-bit."""
+    compiled reference did not travel.  Also checks the GPU rows of the sample bit-for-bit.  cpu_seconds 0: the check alone, on the
+    first CHECK_READS reads."""
     cores = cpu_threads()
     ref = T.load_ref()
     n_all = len(off) - 1
@@ -1011,11 +1044,14 @@ def cpu_baseline(T, host_bwt, opt, seq, rseq, off, timed_rows, cpu_seconds):
         olib = T.load_oracle()
         oix = C.c_void_p(olib.orc_index_wrap(T.ptr(host_bwt[0]), len(host_bwt[0]), T.ptr(host_bwt[1]), len(host_bwt[1])))
         kind = "port"
-    pilot = min(n_all, 256 * cores)
-    dt, _, _ = run(pilot, cores)
-    n_s = int(min(n_all, max(pilot, pilot / max(dt, 1e-3) * cpu_seconds)))
+    if cpu_seconds > 0:
+        pilot = min(n_all, 256 * cores)
+        dt, _, _ = run(pilot, cores)
+        n_s = int(min(n_all, max(pilot, pilot / max(dt, 1e-3) * cpu_seconds)))
+    else:
+        n_s = min(n_all, CHECK_READS)                  # the sample check alone: a fixed sample
     dt, n_aln, rows = run(n_s, cores)
-    log("cpu baseline (%s): %d reads on %d threads in %.2f s" % (kind, n_s, cores, dt))
+    log("cpu %s (%s): %d reads on %d threads in %.2f s" % ("baseline" if cpu_seconds > 0 else "sample check", kind, n_s, cores, dt))
     # parity of the GPU rows (of the timed run) for the sample
     g_na, g_rows, _ = timed_rows
     gb = int(np.sum(g_na[:n_s]))

@@ -1,5 +1,5 @@
 """Which feature known BEFORE kernel D runs predicts how long a search will take there?  (The launch ends with its longest search;
-the work order decides when that one starts.)   NABWA_DEEP_DUMP=<file> python3 bench.py --adna ... ; python3 deep_order_probe.py <file>
+the work order decides when that one starts.)   NABWA_DEEP_DUMP=<file> python3 bench.py --full --adna ... ; python3 deep_order_probe.py <file>
 Simulates list scheduling on W waves with the rounds a search took as its cost, for several orders."""
 import heapq
 import sys

@@ -1,8 +1,8 @@
-cd "$GRAFT_REPO_ROOT" && mkdir -p gpurun_out/ho
-NABWA_DEEP_DUMP=$PWD/gpurun_out/ho/pe.bin NABWA_BENCH_QUICK=1 timeout -k 10 300 python3 bench.py --pe --pairs 1000000 --steps 1 --warmup 0 --no-cpu > gpurun_out/ho/pe.json 2> gpurun_out/ho/pe.err || { tail -3 gpurun_out/ho/pe.err; exit 1; }
+cd "$(dirname "$0")/../.." && mkdir -p bench_out/ho
+NABWA_DEEP_DUMP=$PWD/bench_out/ho/pe.bin NABWA_BENCH_QUICK=1 timeout -k 10 300 python3 bench.py --full --pe --pairs 1000000 --steps 1 --warmup 0 --no-cpu > bench_out/ho/pe.json 2> bench_out/ho/pe.err || { tail -3 bench_out/ho/pe.err; exit 1; }
 python3 - <<'PY'
 import numpy as np
-a=np.fromfile('gpurun_out/ho/pe.bin.all',np.uint8).reshape(-1,4)
+a=np.fromfile('bench_out/ho/pe.bin.all',np.uint8).reshape(-1,4)
 mn=np.minimum(a[:,0],a[:,1]); mx=np.maximum(a[:,0],a[:,1])
 print("reads", len(a), "handed on", int(a[:,2].sum()))
 for c in range(5):

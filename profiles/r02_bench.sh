@@ -1,8 +1,8 @@
 #!/bin/bash
 # The round's bench lines WITHOUT a profiler attached (rocprofv3's tracing slows the host-side legs; kernel statistics come from
-# profiles/r02_collect.sh): bash profiles/r02_bench.sh  -> gpurun_out/r02b/*.json
-cd "$GRAFT_REPO_ROOT" && mkdir -p gpurun_out/r02b && O=gpurun_out/r02b
-run() { name=$1; shift; timeout -k 10 600 python3 bench.py "$@" > $O/$name.json 2> $O/$name.log; echo "$name rc=$?"; }
+# profiles/r02_collect.sh): bash profiles/r02_bench.sh  -> bench_out/r02b/*.json
+cd "$(dirname "$0")/.." && mkdir -p bench_out/r02b && O=bench_out/r02b
+run() { name=$1; shift; timeout -k 10 600 python3 bench.py --full "$@" > $O/$name.json 2> $O/$name.log; echo "$name rc=$?"; }
 run headline --steps 5 --warmup 1 || exit 1
 run repeats --repeats --steps 3 --warmup 1 || exit 1
 run adna --adna --reads 1000000 --steps 3 --warmup 1 || exit 1

@@ -4,13 +4,13 @@
 #          process; per-kernel averages would mix them), at the sizes the driver's line uses
 #   pmc  : HBM traffic (FETCH_SIZE, WRITE_SIZE; separate passes, no tracing flags alongside) of the dominant kernel of each workload,
 #          and the SQ / request counters of kernel D on the ancient-DNA workload
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 WHAT=${1:-all}
-O=gpurun_out/r03
+O=bench_out/r03
 mkdir -p $O
 run() {   # name, bench args
   local name=$1; shift
-  timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $O/prof_$name -o run --output-format csv -- python3 bench.py --extras off "$@" > $O/${name}_bench.json 2> $O/${name}_bench.log
+  timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $O/prof_$name -o run --output-format csv -- python3 bench.py --full --extras off "$@" > $O/${name}_bench.json 2> $O/${name}_bench.log
   echo "$name rc=$?"
   f=$(find $O/prof_$name -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/${name}_kernel_stats.csv
   rm -rf $O/prof_$name
@@ -22,7 +22,7 @@ pmc() {   # name, counter groups..., then -- bench args
   local i=0
   for g in "${groups[@]}"; do
     d=$O/pmc_$name/g$i; i=$((i+1)); mkdir -p $O/pmc_$name
-    NABWA_BENCH_QUICK=1 timeout -k 10 600 rocprofv3 --pmc $g -d "$d" -o run --output-format csv -- python3 bench.py --extras off --no-cpu --no-e2e --steps 1 --warmup 0 "$@" > "$d.json" 2> "$d.err" || echo "group '$g' of $name failed (see $d.err)"
+    NABWA_BENCH_QUICK=1 timeout -k 10 600 rocprofv3 --pmc $g -d "$d" -o run --output-format csv -- python3 bench.py --full --extras off --no-cpu --no-e2e --steps 1 --warmup 0 "$@" > "$d.json" 2> "$d.err" || echo "group '$g' of $name failed (see $d.err)"
   done
   python3 profiles/summarize_pmc.py $O/pmc_$name > $O/pmc_$name.json
   # the launch size the pass was taken at and its dominant kernel: bench.py quotes a pass only for the same size (tests/test_profiles.py)

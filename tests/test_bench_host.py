@@ -49,7 +49,7 @@ def test_adna_profile_keeps_the_encoding_and_damages_only_the_ends():
 def test_bench_command_line_parses_without_a_gpu():
     r = subprocess.run([sys.executable, os.path.join(T.ROOT, "bench.py"), "--help"], capture_output=True, text=True)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--adna", "--pipeline"):
+    for flag in ("--gpus", "--steps", "--warmup", "--adna", "--pipeline", "--full"):
         assert flag in r.stdout
 
 
@@ -76,3 +76,13 @@ def test_gpus_without_a_launcher_starts_the_ranks_as_a_child(monkeypatch):
     i = c.index(os.path.join(T.ROOT, "bench.py"))
     assert c[i + 1:] == ["--gpus", "4", "--steps", "5", "--warmup", "2"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0" and seen["env"]["MASTER_ADDR"] == "127.0.0.1"
+
+
+def test_plain_run_is_the_default_and_the_extra_workloads_need_full(monkeypatch):
+    b = load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert b.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--extras", "on"])
+    assert b.parse_args().full is True
+    r = subprocess.run([sys.executable, os.path.join(T.ROOT, "bench.py"), "--extras", "on"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--extras on needs --full" in r.stderr

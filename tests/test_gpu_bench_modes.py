@@ -22,7 +22,7 @@ def run_bench(*args):
 
 def test_bench_adna_small():
     """BASELINE config 5 (-n 0.01 -o 2 -l 16500, 30-70 bp damaged reads) through kernel D, 20 k reads on a 64 Mbp text"""
-    r = run_bench("--adna", "--reads", "20000", "--genome-len", "64000000", "--steps", "1", "--warmup", "0", "--cpu-seconds", "5", "--no-e2e")
+    r = run_bench("--full", "--adna", "--reads", "20000", "--genome-len", "64000000", "--steps", "1", "--warmup", "0", "--cpu-seconds", "5", "--no-e2e")
     assert r["unit"] == "reads/s" and r["value"] > 0
     assert r["config"]["bit_exact_vs_cpu_sample"] is True, r["config"]
     assert r["cpu_baseline"]["kind"] in ("reference", "port") and r["cpu_baseline"]["value"] > 0
@@ -32,12 +32,23 @@ def test_bench_adna_small():
 
 def test_bench_pe_small():
     """BASELINE config 3 (2 x 150 bp pairs): search of both ends + posn_pair + finish_pair, a sample against the reference chain"""
-    r = run_bench("--pe", "--pairs", "20000", "--genome-len", "64000000", "--steps", "1", "--warmup", "0")
+    r = run_bench("--full", "--pe", "--pairs", "20000", "--genome-len", "64000000", "--steps", "1", "--warmup", "0")
     assert r["unit"] == "pairs/s" and r["value"] > 0
     assert r["config"]["bit_exact_vs_cpu_sample"] is True, r["config"]
 
 
 def test_bench_repeats_small():
     """the repeat-family text (LINE / Alu / tandem families): the branchy reads reach kernel D; rows are the CPU leg's"""
-    r = run_bench("--repeats", "--reads", "50000", "--genome-len", "256000000", "--steps", "1", "--warmup", "0", "--cpu-seconds", "5", "--no-e2e")
+    r = run_bench("--full", "--repeats", "--reads", "50000", "--genome-len", "256000000", "--steps", "1", "--warmup", "0", "--cpu-seconds", "5", "--no-e2e")
     assert r["config"]["bit_exact_vs_cpu_sample"] is True, r["config"]
+
+
+@pytest.mark.parametrize("mode", [["--adna", "--reads", "20000"], ["--pe", "--pairs", "20000"]], ids=["adna", "pe"])
+def test_bench_mode_plain_line(mode):
+    """the same modes without --full: the steps' line with the bit-exact check on a fixed sample, no CPU rate, no instrumented run,
+    no streamed PE steps"""
+    r = run_bench(*mode, "--genome-len", "64000000", "--steps", "1", "--warmup", "0")
+    assert r["value"] > 0 and r["steps"] == 1 and r["warmup"] == 0 and r["unit"] == ("pairs/s" if "--pe" in mode else "reads/s")
+    assert r["config"]["bit_exact_vs_cpu_sample"] is True and r["metric"].endswith(", bit-exact vs CPU") and r["cpu_baseline"] is None
+    assert r["roofline"]["kernel_ms"] > 0 and r["roofline"]["achieved"] is None and r["roofline"]["bytes_per_read"] is None
+    assert r["config"].get("streamed") is None

@@ -59,7 +59,7 @@ def test_two_ranks_shard_the_reads_on_the_gpu():
 
 
 def test_bench_two_rank_rehearsal():
-    r = launch(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--genome-len", "30000000", "--reads", "300000", "--cpu-seconds", "3", "--no-e2e"],
+    r = launch(["bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--genome-len", "30000000", "--reads", "300000", "--cpu-seconds", "3", "--no-e2e"],
                dict(NABWA_BENCH_BACKEND="gloo", NABWA_BENCH_SINGLE_DEVICE="1"))
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -78,7 +78,7 @@ def test_bench_starts_its_own_ranks():
     e = dict(os.environ, NABWA_BENCH_BACKEND="gloo", NABWA_BENCH_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         e.pop(k, None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--genome-len", "30000000", "--reads", "300000",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--genome-len", "30000000", "--reads", "300000",
                         "--cpu-seconds", "3", "--e2e-reads", "50000"], env=e, capture_output=True, text=True, timeout=900, cwd=T.ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -521,6 +521,44 @@ int nabwa_pe_finish_sampe(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 						  uint64_t n_mapped[2]);
 int nabwa_index_pac2real(const nabwa_index_t *ix, int64_t pos, int len, int *seqid);
 
+/* ---- colour space (SOLiD): `bwa samse` / `bwa sampe` on a .sai whose gap_opt_t.mode lacks BWA_MODE_COMPREAD ---------------------------
+ * The reference refines the colour hits on the colour pac, turns every mapped colour read into a nucleotide read with nucleotide
+ * qualities (bwa_cs2nt_core, cs2nt.c:112-191), refines every CIGAR again on the nucleotide pac and takes MD / NM from there
+ * (bwa_refine_gapped with ntbns, bwase.c:356-423; no bwa_correct_trimmed).  The decoding is a per-read dynamic programme and runs on
+ * the GPU, one read per lane.
+ * nabwa_cs2nt                    = cs2nt_DP + cs2nt_nt_qual (cs2nt.c:36-109) for n cases: case i has size = off[i + 1] - off[i] colours
+ *                                  (1 .. NABWA_CS2NT_MAX; off[0] = 0), cs_read[off[i] ..) = colour << 6 | quality (63: an N colour),
+ *                                  nt_ref[off[i] + i ..) = size + 1 codes 0-4, and gets out[off[i] - i ..) = size - 1 bytes base << 6 | quality
+ *                                  (0 where a neighbouring colour was N), the reference's returned array.
+ * nabwa_index_attach_nt_reference = bwa_open_nt + bwt_restore_pac (bwase.c:595-603): <prefix>.nt.ann, .nt.amb and .nt.pac of an index built
+ *                                  with `-c`; the 2-bit bases go to HBM.  After nabwa_index_attach_reference: coordinates, contig names
+ *                                  and ambiguity holes stay those of the colour annotations, as in the reference.
+ * nabwa_se_finish_cs             = nabwa_se_finish for colour reads.  qual: the reads' qualities as in the FASTQ (+33), read order, read i
+ *                                  at off[i] (its first len characters).  Out, caller-owned and off[n] bytes each, read i at off[i]: nt_seq
+ *                                  (the decoded read reversed, as bwa_seq_t.seq is held here), nt_rseq (its reverse complement), nt_qual
+ *                                  (qualities + 33, read order); valid for mapped records, whose len and full_len become the decoded
+ *                                  length (one less than the colours the alignment consumes); the other bytes come back 0.  Unmapped records keep the colour read.
+ * nabwa_pe_finish_sampe_cs       = nabwa_pe_finish_sampe for colour pairs, the same side arrays (index 2 * pair + end).  popt->type must be 2
+ *                                  (BWA_PET_SOLID: both ends on the fragment's strand, end 0 upstream, bwape.c:234-247), and popt->is_sw
+ *                                  0 or ii->avg < 0: the reference's mate rescue dereferences a null pac in colour space (bwape.c:651,
+ *                                  692-701), so there is nothing to reproduce.
+ * Both return NABWA_EINVAL when opt->mode has COMPREAD set or the index has no nucleotide reference attached.
+ * times (both chains, may be NULL): [0] += wall seconds of the decode stage (records, copies, kernels), [1] += HIP-event milliseconds
+ *                                  of its kernels; added to, so that a caller sums over its chunks.
+ * nabwa_pairing_typed            = nabwa_pairing with pe_opt_t.type (1 or 2). */
+#define NABWA_CS2NT_MAX 1024
+int nabwa_cs2nt(int device, int n, const int64_t *off, const uint8_t *nt_ref, const uint8_t *cs_read, uint8_t *out);
+int nabwa_index_attach_nt_reference(nabwa_index_t *ix, const char *prefix);
+int nabwa_se_finish_cs(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, const int64_t *off, const uint8_t *seq, const uint8_t *rseq,
+					   const uint8_t *qual, const int32_t *full_len, const int32_t *n_aln, const nabwa_aln1_t *aln, int n_occ,
+					   uint64_t *rng48, nabwa_se_t *out, uint8_t *nt_seq, uint8_t *nt_rseq, uint8_t *nt_qual, double *times);
+int nabwa_pe_finish_sampe_cs(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const nabwa_pe_opt_t *popt, const nabwa_isize_t *ii,
+							 int n_pairs, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, const uint8_t *qual,
+							 const int32_t *n_aln, const nabwa_aln1_t *aln, nabwa_pe_t *inout, nabwa_poscache_t *cache, int *cnt_chg,
+							 uint8_t *nt_seq, uint8_t *nt_rseq, uint8_t *nt_qual, double *times);
+int nabwa_pairing_typed(nabwa_pe_end_t p[2], int n_hits, uint64_t *hits, const nabwa_aln1_t *rows0, const nabwa_aln1_t *rows1,
+						int max_isize, int s_mm, const nabwa_isize_t *ii, int type);
+
 #ifdef __cplusplus
 }
 #endif

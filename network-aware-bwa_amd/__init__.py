@@ -135,6 +135,34 @@ def pairing(ends, hits, rows0, rows1, max_isize, s_mm, ii):
     return lib().nabwa_pairing(ends, len(hits), _ptr(hits), _ptr(r0), _ptr(r1), int(max_isize), int(s_mm), C.byref(ii))
 
 
+def pairing_typed(ends, hits, rows0, rows1, max_isize, s_mm, ii, pe_type):
+    """pairing with pe_opt_t.type: 1 BWA_PET_STD, 2 BWA_PET_SOLID (colour space, reference bwape.c:234-247)"""
+    hits = np.ascontiguousarray(hits, np.uint64)
+    r0 = np.ascontiguousarray(rows0, ALN_DT)
+    r1 = np.ascontiguousarray(rows1, ALN_DT)
+    rc = lib().nabwa_pairing_typed(ends, len(hits), _ptr(hits), _ptr(r0), _ptr(r1), int(max_isize), int(s_mm), C.byref(ii), int(pe_type))
+    if rc < 0:
+        raise NabwaError(int(rc), lib().nabwa_last_error().decode())
+    return rc
+
+
+CS2NT_MAX = 1024
+
+
+def cs2nt(off, nt_ref, cs_read, device=0):
+    """cs2nt_DP + cs2nt_nt_qual (reference cs2nt.c:36-109) for a batch on the GPU.  Case i has size = off[i + 1] - off[i] colours:
+    cs_read[off[i]:off[i + 1]] = colour << 6 | quality (63: N), nt_ref[off[i] + i:off[i + 1] + i + 1] = size + 1 codes 0-4.  Returns the
+    uint8 array whose [off[i] - i:off[i + 1] - i - 1] are the size - 1 bytes base << 6 | quality of case i."""
+    off = np.ascontiguousarray(off, np.int64)
+    n = len(off) - 1
+    ref = np.ascontiguousarray(nt_ref, np.uint8)
+    cs = np.ascontiguousarray(cs_read, np.uint8)
+    assert n >= 0 and cs.size == int(off[-1]) and ref.size == cs.size + n
+    out = np.zeros(max(cs.size - n, 1), np.uint8)
+    _chk(lib().nabwa_cs2nt(int(device), n, _ptr(off), _ptr(ref), _ptr(cs), _ptr(out)))
+    return out[:max(cs.size - n, 0)]
+
+
 class BwaSeq(C.Structure):
     """bwa_seq_t (reference bwtaln.h:64-90), 200 bytes, as nabwa_bwa_seq_t declares it"""
     _fields_ = [("name", C.c_void_p), ("seq", C.c_void_p), ("rseq", C.c_void_p), ("qual", C.c_void_p),
@@ -304,6 +332,11 @@ def lib():
     L.nabwa_index_fa2cspac.argtypes = [C.c_char_p, C.c_char_p]
     L.nabwa_index_build.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int]
     L.nabwa_index_build_estimate.argtypes = [C.c_uint64, _P]
+    L.nabwa_cs2nt.argtypes = [C.c_int, C.c_int, _P, _P, _P, _P]
+    L.nabwa_index_attach_nt_reference.argtypes = [_P, C.c_char_p]
+    L.nabwa_se_finish_cs.argtypes = [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]
+    L.nabwa_pe_finish_sampe_cs.argtypes = [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]
+    L.nabwa_pairing_typed.argtypes = [_P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int]
     _lib = L
     return L
 
@@ -418,6 +451,40 @@ class Index:
     def attach_reference(self, prefix):
         """.ann/.amb/.pac of the index (reference bns_restore + bwt_restore_pac)"""
         _chk(lib().nabwa_index_attach_reference(self._h, prefix.encode()))
+
+    def attach_nt_reference(self, prefix):
+        """.nt.ann/.nt.amb/.nt.pac of a colour index (reference bwa_open_nt + bwt_restore_pac); the bases go to HBM"""
+        _chk(lib().nabwa_index_attach_nt_reference(self._h, prefix.encode()))
+
+    def se_finish_cs(self, opt, seq, rseq, qual, off, full_len, hits, n_occ, rng_state):
+        """se_finish for colour reads (nabwa_se_finish_cs); qual: the reads' qualities (+33, read order) at off[].
+        Returns (array of SeRec, new rng state, nt_seq, nt_rseq, nt_qual): the decoded read of a mapped record i is the first
+        recs[i].len bytes at off[i] -- reversed, its reverse complement, its qualities + 33 in read order."""
+        n = len(off) - 1
+        n_aln = np.array([len(h) for h in hits], np.int32)
+        rows = np.ascontiguousarray(np.concatenate([np.asarray(h, ALN_DT) for h in hits] + [np.zeros(0, ALN_DT)]))
+        out = (SeRec * max(n, 1))()
+        st = C.c_uint64(rng_state)
+        off = np.ascontiguousarray(off, np.int64)
+        side = [np.zeros(max(int(off[-1]), 1), np.uint8) for _ in range(3)]
+        _chk(lib().nabwa_se_finish_cs(self._h, C.byref(opt), n, _ptr(off), _ptr(np.ascontiguousarray(seq, np.uint8)),
+                                      _ptr(np.ascontiguousarray(rseq, np.uint8)), _ptr(np.ascontiguousarray(qual, np.uint8)),
+                                      _ptr(np.ascontiguousarray(full_len, np.int32)), _ptr(n_aln), _ptr(rows), int(n_occ), C.byref(st), out,
+                                      _ptr(side[0]), _ptr(side[1]), _ptr(side[2]), None))
+        return (out, st.value) + tuple(side)
+
+    def pe_finish_sampe_cs(self, opt, popt, ii, seq, rseq, qual, off, n_aln, rows, recs, cache=None):
+        """nabwa_pe_finish_sampe_cs on flat arrays; recs (from pe_posn_flat) are updated in place.
+        Returns (cnt_chg, nt_seq, nt_rseq, nt_qual) as se_finish_cs, index 2 * pair + end."""
+        off = np.ascontiguousarray(off, np.int64)
+        n = len(off) - 1
+        side = [np.zeros(max(int(off[-1]), 1), np.uint8) for _ in range(3)]
+        chg = C.c_int()
+        _chk(lib().nabwa_pe_finish_sampe_cs(self._h, C.byref(opt), C.byref(popt), C.byref(ii), n // 2, _ptr(off),
+                                            _ptr(np.ascontiguousarray(seq, np.uint8)), _ptr(np.ascontiguousarray(rseq, np.uint8)),
+                                            _ptr(np.ascontiguousarray(qual, np.uint8)), _ptr(np.ascontiguousarray(n_aln, np.int32)),
+                                            _ptr(np.ascontiguousarray(rows)), recs, cache, C.byref(chg), _ptr(side[0]), _ptr(side[1]), _ptr(side[2]), None))
+        return (chg.value,) + tuple(side)
 
     def set_reference(self, l_pac, seed, pac, n_contigs=16, name="synth"):
         """nabwa_index_set_reference: n_contigs equal contigs "synth1".. over the reference (a contig's length is an int32 in the

@@ -224,15 +224,30 @@ static inline int64_t rec_pos_end(const nabwa_se_t &s)
 	return x;
 }
 
+/* the flag / contig / XT fields bwa_update_bam1 derives for a mapped single-end record (bam2bam.c:430-525) */
+static inline void se_flags(const nabwa_reference *R, nabwa_se_t &s)
+{
+	const int reflen = (int)(rec_pos_end(s) - s.pos);
+	s.nn = pac2real(R, s.pos, reflen, &s.seqid);
+	s.flag = 0;
+	if ((int64_t)s.pos + reflen - R->anns[s.seqid].offset > R->anns[s.seqid].len) { s.flag |= 4; s.mapQ = 0; }   /* bridges two contigs */
+	if (s.strand) s.flag |= 16;
+	s.rpos = (int64_t)s.pos - R->anns[s.seqid].offset + 1;
+	s.xt = s.nn > 10 ? 'N' : "NURM"[s.type];
+}
+
 /* Gap refinement of every gapped hit of the batch (main hits and multi hits) as ONE batch of banded global
  * alignments on the GPU (refine_gapped_core, bwase.c:189-237; driver bwase.c:366-381: mate-rescued and
  * unmapped records are skipped).  The host work around the kernel -- finding the jobs, cutting their reference windows out
  * of the packed text, laying the reads out in alignment orientation, turning the paths into CIGARs -- runs on slices of the
- * records / jobs in threads. */
+ * records / jobs in threads.
+ * nt_ref (colour space, bwase.c:383-402): the second pass on the nucleotide pac with the decoded reads -- every hit that has a CIGAR
+ * and every gapped multi hit again, with is_end_correct = 0: the window starts at pos on both strands and pos is not shifted. */
 static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int n, const int64_t *off, const uint8_t *seq,
-							   const uint8_t *rseq, size_t *n_jobs)
+							   const uint8_t *rseq, size_t *n_jobs, const nabwa_reference *nt_ref = nullptr)
 {
-	const nabwa_reference *R = ix->ref;
+	const nabwa_reference *R = nt_ref ? nt_ref : ix->ref;
+	const bool end_correct = nt_ref == nullptr;
 	const bool timing = getenv("NABWA_TIMING") != 0;
 	const double tr0 = now_s();
 	const int nt = host_threads((size_t)n, 4096);
@@ -243,7 +258,7 @@ static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int
 			const nabwa_se_t &s = *rec_at(base, stride, (int)i);
 			for (int j = 0; j < s.n_multi; ++j)
 				if (s.multi[j].gap) v.push_back({ (int)i, j, s.multi[j].strand, (s.multi[j].strand ? 1 : -1) * s.multi[j].gap, s.len, s.multi[j].pos, 0, 0 });
-			if (s.type != 0 && s.type != 3 && s.n_gapo) v.push_back({ (int)i, -1, s.strand, (s.strand ? 1 : -1) * (s.n_gapo + s.n_gape), s.len, s.pos, 0, 0 });
+			if (nt_ref ? (s.type != 0 && s.n_cigar) : (s.type != 0 && s.type != 3 && s.n_gapo)) v.push_back({ (int)i, -1, s.strand, (s.strand ? 1 : -1) * (s.n_gapo + s.n_gape), s.len, s.pos, 0, 0 });
 		}
 	});
 	std::vector<RefineJob> jobs;
@@ -261,7 +276,7 @@ static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int
 		J.pos = p;
 		int64_t lo, hi;
 		if (J.ext > 0) { lo = std::max<int64_t>(p, 0); hi = std::min<int64_t>(p + ref_len, R->l_pac); }
-		else { const int64_t x = p + J.len; lo = x - ref_len > 0 ? x - ref_len : 0; hi = std::min<int64_t>(x, R->l_pac); }
+		else { const int64_t x = p + (end_correct ? J.len : ref_len); lo = x - ref_len > 0 ? x - ref_len : 0; hi = std::min<int64_t>(x, R->l_pac); }
 		J.win_lo = lo; J.win_n = hi > lo ? (int)(hi - lo) : 0;
 		ro[t + 1] = ro[t] + J.win_n; qo[t + 1] = qo[t] + J.len;
 	}
@@ -306,7 +321,7 @@ static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int
 			if (nc[t] > MAXC || nc[t] < 1) { bad[(size_t)slice] = 1; continue; }
 			uint16_t cg[NABWA_MAX_CIGAR]; int m = nc[t]; int64_t p = J.pos;
 			for (int k = 0; k < m; ++k) cg[k] = CMAKE(c32[t * MAXC + k] & 0xf, c32[t * MAXC + k] >> 4);
-			if (J.ext < 0) {                       /* forward strand: the end was anchored, shift the start by the net indel */
+			if (J.ext < 0 && end_correct) {        /* forward strand: the end was anchored, shift the start by the net indel */
 				int d = 0;
 				for (int k = 0; k < m; ++k) { if (COP(cg[k]) == 2) d -= CLEN(cg[k]); else if (COP(cg[k]) == 1) d += CLEN(cg[k]); }
 				p += d;

@@ -385,6 +385,8 @@ extern "C" void nabwa_index_destroy(nabwa_index_t *ix)
 		}
 		delete ix->pool;
 	}
+	if (ix->d_ntpac) (void)hipFree(ix->d_ntpac);
+	delete ix->ref_nt;
 	delete ix->ref;
 	delete ix;
 }

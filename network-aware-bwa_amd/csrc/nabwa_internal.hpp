@@ -27,6 +27,9 @@ struct nabwa_index {
 	uint64_t bytes;
 	int kmer_T_pick = -1;           // depth of the interval tables, decided when the first direction is built
 	nabwa_reference *ref;
+	nabwa_reference *ref_nt = nullptr;   // colour index: the annotations of `ref` over the bases of <prefix>.nt.pac (cs2nt.hip)
+	uint8_t *d_ntpac = nullptr;          // ... and those bases in HBM, with their size in bytes
+	uint64_t ntpac_bytes = 0;
 	struct nabwa_dev_pool *pool;   // released working buffers of earlier batches, kept for the next one (nabwa_api.hip)
 };
 
@@ -45,6 +48,13 @@ static inline int nabwa_hip_fail(hipError_t e, const char *expr, const char *fil
 int nabwa_se_posn_strided(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, const int64_t *off, const int32_t *full_len,
 						  const int32_t *n_aln, const nabwa_aln1_t *aln, const uint8_t *n_occ_v, uint64_t *rng48, void *out_base, size_t stride);
 int nabwa_se_refine_strided(nabwa_index_t *ix, int n, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, void *out_base, size_t stride);
+/* <prefix>.ann, .amb and .pac into a new nabwa_reference (se_finish.hip) */
+int nabwa_reference_read(const char *prefix, nabwa_reference **out);
+/* colour space (cs2nt.hip): bwa_cs2nt_core for every mapped record on the GPU -- the decoded reads go to nt_seq (the read reversed, as
+ * bwa_seq_t.seq is held here), nt_rseq (its reverse complement) and nt_qual (qualities + 33, read order) from off[i] on, and len =
+ * full_len = the decoded length in the records.  times (may be null): [0] += seconds of this stage, [1] += milliseconds of its kernels */
+int nabwa_cs2nt_records(nabwa_index_t *ix, void *base, size_t stride, int n, const int64_t *off, const uint8_t *seq, const uint8_t *rseq,
+						const uint8_t *qual, uint8_t *nt_seq, uint8_t *nt_rseq, uint8_t *nt_qual, double *times);
 /* the wide rows of a batch's pairs into finish_pair's position cache, in record order (pe_finish.hip) */
 void nabwa_poscache_register(nabwa_poscache_t *cache, int max_occ, int n, const int *first, const int32_t *n_aln, const int64_t *row0,
 							 const nabwa_aln1_t *rows, const nabwa_pe_t *res);

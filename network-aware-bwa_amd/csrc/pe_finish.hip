@@ -95,6 +95,9 @@ void nabwa_poscache_register(nabwa_poscache_t *cache, int max_occ, int n, const 
 	}
 }
 
+/* colour space (nabwa_pe_finish_sampe_cs): the reads' qualities in, the decoded reads out (nabwa_cs2nt_records) */
+struct PeColour { const uint8_t *qual; uint8_t *nt_seq, *nt_rseq, *nt_qual; double *times; };
+
 /* one mate-rescue attempt: align end `k` of pair `pair` inside [beg, beg+reglen) next to its mate (bwape.c:562-583) */
 struct SwJob { int pair, k; int64_t beg; int ref_n; bool fwd; };
 
@@ -108,7 +111,7 @@ extern "C" int nabwa_pe_finish(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, co
 static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const nabwa_pe_opt_t *popt, const nabwa_isize_t *ii,
 						  int n_pairs, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, const int32_t *n_aln,
 						  const nabwa_aln1_t *aln, nabwa_pe_t *out, uint64_t n_tot[2], uint64_t n_mapped[2], nabwa_poscache_t *cache,
-						  bool sampe, int *cnt_chg);
+						  bool sampe, int *cnt_chg, const PeColour *cs = nullptr);
 
 extern "C" int nabwa_pe_finish_cached(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const nabwa_pe_opt_t *popt, const nabwa_isize_t *ii,
 									  int n_pairs, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, const int32_t *n_aln,
@@ -129,13 +132,21 @@ extern "C" int nabwa_pe_finish_sampe(nabwa_index_t *ix, const nabwa_gap_opt_t *o
 static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const nabwa_pe_opt_t *popt, const nabwa_isize_t *ii,
 						  int n_pairs, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, const int32_t *n_aln,
 						  const nabwa_aln1_t *aln, nabwa_pe_t *out, uint64_t n_tot[2], uint64_t n_mapped[2], nabwa_poscache_t *cache,
-						  bool sampe, int *cnt_chg)
+						  bool sampe, int *cnt_chg, const PeColour *cs)
 {
 	if (cnt_chg) *cnt_chg = 0;
 	std::atomic<int> chg(0);
 	if (!ix || !opt || !popt || !ii || n_pairs < 0 || (n_pairs && (!off || !seq || !rseq || !n_aln || !out))) return nabwa_fail(NABWA_EINVAL, "null argument");
 	if (!ix->ref) return nabwa_fail(NABWA_EINVAL, "index has no reference attached (nabwa_index_attach_reference)");
-	if (popt->type != 1) return nabwa_fail(NABWA_EINVAL, "only BWA_PET_STD pairs are supported (no colour space)");
+	if (!cs && popt->type != 1) return nabwa_fail(NABWA_EINVAL, "only BWA_PET_STD pairs are supported (no colour space)");
+	if (cs) {
+		if (opt->mode & NABWA_MODE_COMPREAD) return nabwa_fail(NABWA_EINVAL, "the option block is a nucleotide one (BWA_MODE_COMPREAD): use nabwa_pe_finish_sampe");
+		if (!ix->ref_nt) return nabwa_fail(NABWA_EINVAL, "index has no nucleotide reference attached (nabwa_index_attach_nt_reference)");
+		if (popt->type != 2) return nabwa_fail(NABWA_EINVAL, "colour-space pairs need pe_opt_t.type == 2 (BWA_PET_SOLID)");
+		/* the reference hands bwa_paired_sw1 a null pac in colour space (bwape.c:651,692-701) and crashes: there is nothing to be equal to */
+		if (popt->is_sw && ii->avg >= 0.0) return nabwa_fail(NABWA_EINVAL, "no mate rescue in colour space: is_sw must be 0 or the estimate's avg below 0");
+		if (!cs->qual || !cs->nt_seq || !cs->nt_rseq || !cs->nt_qual) return nabwa_fail(NABWA_EINVAL, "null argument");
+	}
 	if (popt->n_multi < 0 || popt->N_multi < 0 || popt->n_multi > NABWA_MAX_MULTI || popt->N_multi > NABWA_MAX_MULTI)
 		return nabwa_fail(NABWA_EINVAL, "n_multi / N_multi outside 0..16");
 	const nabwa_reference *R = ix->ref;
@@ -244,7 +255,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 				const nabwa_pe_t &r = PE(out, pr, j); const nabwa_se_t &s = r.se;
 				e[j] = { s.pos, s.strand, s.mapQ, s.seQ, s.len, s.full_len, s.n_mm, s.n_gapo, s.n_gape, s.score, r.extra_flag };
 			}
-			chg += nabwa_pairing(e, (int)hits.size(), hits.data(), aln + a_off[2 * (size_t)pr], aln + a_off[2 * (size_t)pr + 1], popt->max_isize, opt->s_mm, ii);
+			chg += nabwa_pairing_typed(e, (int)hits.size(), hits.data(), aln + a_off[2 * (size_t)pr], aln + a_off[2 * (size_t)pr + 1], popt->max_isize, opt->s_mm, ii, popt->type);
 			for (int j = 0; j < 2; ++j) {
 				nabwa_pe_t &r = PE(out, pr, j); nabwa_se_t &s = r.se;
 				s.pos = e[j].pos; s.strand = e[j].strand; s.mapQ = e[j].mapQ; s.seQ = e[j].seQ; s.n_mm = e[j].n_mm; s.n_gapo = e[j].n_gapo;
@@ -453,6 +464,18 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 		int r = refine_batch(ix, out, sizeof(nabwa_pe_t), n, off, seq, rseq, &n_refine);
 		if (r != NABWA_OK) return r;
 	}
+	double t_dec = 0, t_ref2 = 0; size_t n_refine2 = 0;
+	const nabwa_reference *Rmd = R;                       /* where MD / NM read their bases */
+	if (cs) {	/* colour space (bwase.c:383-402): every mapped end decoded on the GPU, then the CIGARs again on the nucleotide pac */
+		const double td0 = now_s();
+		int r = nabwa_cs2nt_records(ix, out, sizeof(nabwa_pe_t), n, off, seq, rseq, cs->qual, cs->nt_seq, cs->nt_rseq, cs->nt_qual, cs->times);
+		if (r != NABWA_OK) return r;
+		const double td1 = now_s();
+		r = refine_batch(ix, out, sizeof(nabwa_pe_t), n, off, cs->nt_seq, cs->nt_rseq, &n_refine2, ix->ref_nt);
+		if (r != NABWA_OK) return r;
+		t_dec = td1 - td0; t_ref2 = now_s() - td1;
+		seq = cs->nt_seq; rseq = cs->nt_rseq; Rmd = ix->ref_nt;
+	}
 	t4 = now_s();
 
 	/* ---- E. MD / NM / trimmed tail per end, then the flag and mate fields (bwase.c:399-419, bam2bam.c:430-525) */
@@ -466,7 +489,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 			if (pr + 4 < hi) for (int j = 0; j < 2; ++j) { const nabwa_se_t &f = PE(out, pr + 4, j).se; if (f.type) { const uint8_t *const w = R->pac.data() + (f.pos >> 2); __builtin_prefetch(w); __builtin_prefetch(w + 32); } }
 			for (int j = 0; j < 2; ++j) {
 				nabwa_se_t &s = PE(out, pr, j).se;
-				if (s.type != 0 && !md_and_trim(R, s, seq + off[2 * pr + j], rseq + off[2 * pr + j], fwd)) md_over = 1;
+				if (s.type != 0 && !md_and_trim(Rmd, s, seq + off[2 * pr + j], rseq + off[2 * pr + j], fwd)) md_over = 1;
 			}
 			for (int j = 0; j < 2; ++j) {                              /* end 0 first, as bam2bam.c:804-805 */
 				nabwa_pe_t &r = PE(out, pr, j); nabwa_se_t &p = r.se;
@@ -506,6 +529,17 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 						ta[0], ta[1], ta[2], tc[0], tc[1] - tc[0], n_cand, tc[2] - tc[1], (t3 - t2) - tc[2]);
 	if (timing) fprintf(stderr, "[nabwa] pe_finish %d pairs: pairing (%zu hit rows) %.3f s, multi %.3f s, mate rescue (%zu alignments) %.3f s, "
 						"refinement (%zu jobs) %.3f s, md/flags %.3f s\n", n_pairs, n_hit_rows, t1 - t0, t2 - t1, n_sw, t3 - t2, n_refine, t4 - t3, now_s() - t4);
+	if (timing && cs) fprintf(stderr, "[nabwa] pe_finish colour space: decode %.3f s, nucleotide refinement (%zu jobs) %.3f s\n", t_dec, n_refine2, t_ref2);
 	if (cnt_chg) *cnt_chg = chg.load();
 	return NABWA_OK;
+}
+
+/* nabwa_pe_finish_sampe for colour-space pairs: see nabwa.h */
+extern "C" int nabwa_pe_finish_sampe_cs(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const nabwa_pe_opt_t *popt, const nabwa_isize_t *ii,
+										int n_pairs, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, const uint8_t *qual,
+										const int32_t *n_aln, const nabwa_aln1_t *aln, nabwa_pe_t *inout, nabwa_poscache_t *cache, int *cnt_chg,
+										uint8_t *nt_seq, uint8_t *nt_rseq, uint8_t *nt_qual, double *times)
+{
+	const PeColour cs = { qual, nt_seq, nt_rseq, nt_qual, times };
+	return pe_finish_impl(ix, opt, popt, ii, n_pairs, off, seq, rseq, n_aln, aln, inout, 0, 0, cache, true, cnt_chg, &cs);
 }

@@ -177,6 +177,15 @@ struct PairSweep {
 extern "C" int nabwa_pairing(nabwa_pe_end_t p[2], int n_hits, uint64_t *hits, const nabwa_aln1_t *rows0, const nabwa_aln1_t *rows1,
 							 int max_isize, int s_mm, const nabwa_isize_t *ii)
 {
+	return nabwa_pairing_typed(p, n_hits, hits, rows0, rows1, max_isize, s_mm, ii, 1);
+}
+
+/* type: pe_opt_t.type -- 1 BWA_PET_STD (the sweep above), 2 BWA_PET_SOLID (bwape.c:234-247): both ends lie on the fragment's strand, end 0
+ * upstream of end 1, so a hit closes a pair when its strand bit differs from its end bit and opens one otherwise */
+extern "C" int nabwa_pairing_typed(nabwa_pe_end_t p[2], int n_hits, uint64_t *hits, const nabwa_aln1_t *rows0, const nabwa_aln1_t *rows1,
+								   int max_isize, int s_mm, const nabwa_isize_t *ii, int type)
+{
+	if (type != 1 && type != 2) return nabwa_fail(NABWA_EINVAL, "pairing: pe_opt_t.type must be 1 (BWA_PET_STD) or 2 (BWA_PET_SOLID)");
 	const nabwa_aln1_t *rows[2] = { rows0, rows1 };
 	PairSweep sw;
 	sw.end = p; sw.rows = rows; sw.ii = ii; sw.max_isize = max_isize;
@@ -186,7 +195,8 @@ extern "C" int nabwa_pairing(nabwa_pe_end_t p[2], int n_hits, uint64_t *hits, co
 	sw.n_best = sw.n_worse = 0;
 	std::sort(hits, hits + n_hits);
 	for (int i = 0; i < n_hits; ++i) {
-		if (sw.reverse(hits[i])) sw.reverse_seen(hits[i]);
+		const bool closes = type == 2 ? (((unsigned)sw.reverse(hits[i]) ^ (unsigned)hits[i]) & 1) != 0 : sw.reverse(hits[i]);
+		if (closes) sw.reverse_seen(hits[i]);
 		else sw.forward_seen(hits[i]);
 	}
 	if (sw.best.none) return 0;

@@ -12,6 +12,13 @@
 // rescue alignment on the GPU (nabwa_se_finish, nabwa_pe_posn, nabwa_pe_finish_sampe); parsing and SAM text (bwa_print_sam1,
 // bwase.c:458-592) on host threads here.  Chunk k+1 is parsed and chunk k-1 formatted and written while the GPU works on chunk k;
 // the output order is the input order.
+//
+// Colour space (a .sai whose option block lacks BWA_MODE_COMPREAD, from `nabwa_aln -c` on an index built with `nabwa_index -c`): the chains
+// are nabwa_se_finish_cs / nabwa_pe_finish_sampe_cs, which also decode every mapped colour read into nucleotides on the GPU; SEQ / QUAL of
+// a mapped record are the decoded read, those of an unmapped one the colour letters.  Refused with exit status 1, each because the
+// reference crashes or reads outside its arrays there:
+//   * nabwa_sampe without -s or -A: bwa_paired_sw hands bwa_paired_sw1 a null pac (bwape.c:651,692-701);
+//   * reads without qualities (FASTA input): bwa_cs2nt_core reads p->qual[...] of a null pointer (cs2nt.c:129).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -134,6 +141,7 @@ struct Chunk {
 	std::vector<int64_t> off{0};
 	std::vector<uint8_t> seq, rseq;
 	std::vector<int32_t> full_len;
+	std::vector<uint8_t> qual, nt_seq, nt_rseq, nt_qual; /* colour space: the qualities in, the decoded reads out (nabwa_se_finish_cs), all at off[] */
 	std::vector<nabwa_se_t> se;
 	std::vector<nabwa_pe_t> pe;
 	std::string log;                                    /* stderr lines of the GPU step, printed in order */
@@ -148,6 +156,10 @@ static void encode(Chunk &c, const Reads &r, int i, bool comp)          /* bwa_s
 	for (int k = 0; k < len; ++k) { const uint8_t x = f[len - 1 - k]; c.seq.push_back(x < 4 ? x : 4); c.rseq.push_back(x < 4 ? x ^ flip : 4); }   /* '-' (5) as N, as nabwa_aln searched it */
 	c.off.push_back((int64_t)c.seq.size());
 	c.full_len.push_back(r.full_len[i]);
+	if (!comp) {                                                         /* colour space: the qualities bwa_cs2nt_core reads (cs2nt.c:129) */
+		if (!r.has_qual[i]) fail("colour-space read " + r.name[i] + " has no qualities: the conversion to nucleotides needs them (the reference reads a null pointer there, cs2nt.c:129)");
+		c.qual.insert(c.qual.end(), r.qual[i].begin(), r.qual[i].begin() + len);
+	}
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -157,6 +169,7 @@ struct Printer {
 	std::vector<std::string> names; std::vector<int64_t> offs; std::vector<int32_t> lens;
 	int mode = 0, max_top2 = 0;
 	std::string rg_id;
+	bool colour() const { return !(mode & NABWA_MODE_COMPREAD); }
 
 	int pac2real(int64_t pos, int len, int *seqid) const { return nabwa_index_pac2real(ix, pos, len, seqid); }
 	static int64_t pos_end(const nabwa_se_t &p, int64_t pos)
@@ -175,13 +188,16 @@ struct Printer {
 		if (strand) std::reverse(o.begin() + (long)at, o.begin() + (long)at + std::min<long>(len, (long)rd.qual[i].size()));   /* seq_reverse(p->len, p->qual, 0) */
 	}
 	/* p: the record; mapQ: its mapping quality; extra_flag: bwa_seq_t.extra_flag; mate: NULL for single-end; bc: the barcode printed */
-	void print1(std::string &o, const nabwa_se_t &p, int mapQ, int extra_flag, const nabwa_se_t *mate, const Reads &rd, int i, const std::string &bc) const
+	/* nt_seq / nt_qual (colour space): the decoded read of a mapped record -- reversed, as the chain leaves it -- and its qualities */
+	void print1(std::string &o, const nabwa_se_t &p, int mapQ, int extra_flag, const nabwa_se_t *mate, const Reads &rd, int i, const std::string &bc,
+				const uint8_t *nt_seq = nullptr, const uint8_t *nt_qual = nullptr) const
 	{
 		char b[256];
 		const uint8_t *fwd = rd.fwd.data() + rd.foff[i];
 		/* bwa_correct_trimmed (bwase.c:320-354) runs on every read, unmapped ones too, while their strand is still 0: a trimmed unmapped
 		 * read gets len M + the clip as S, and len = full_len from there on */
-		const bool trim0 = p.type == 0 && p.len < rd.full_len[i];
+		const bool trim0 = p.type == 0 && p.len < rd.full_len[i] && !colour();          /* (not applied in colour space, bwase.c:418-419) */
+		const int tag_full = p.type != 0 && colour() ? p.full_len : rd.full_len[i];      /* bwa_seq_t.full_len: the decoded length once a colour read is decoded */
 		const int plen = trim0 ? rd.full_len[i] : p.len;
 		if (p.type != 0 || (mate && mate->type != 0)) {
 			int seqid, m_seqid = -1, am = 0, flag = extra_flag, j;
@@ -223,15 +239,25 @@ struct Printer {
 				snprintf(b, sizeof b, "%d\t%lld\t", (int)(mate->pos - offs[m_seqid] + 1), isize); o += b;
 			} else if (mate) { snprintf(b, sizeof b, "\t=\t%d\t0\t", (int)(pos - offs[seqid] + 1)); o += b; }
 			else o += "\t*\t0\t0\t";
-			const int fl = rd.full_len[i];
-			const size_t at = o.size();
-			o.resize(at + (size_t)fl);
-			/* codes 0-5: "ACGTN"[5] is the literal's terminating NUL, the byte the reference's putchar writes for a '-' */
-			if (strand == 0) for (int k = 0; k < fl; ++k) o[at + k] = "ACGTN"[fwd[k]];
-			else for (int k = 0; k < fl; ++k) o[at + k] = "TGCAN"[fwd[fl - 1 - k]];
-			o += '\t';
-			put_qual(o, rd, i, strand, plen);
-			tags_head(o, p, rd, i, bc);
+			if (p.type != 0 && colour()) {                               /* the decoded read, in the alignment's orientation */
+				const int fl = p.full_len;
+				const size_t at = o.size();
+				o.resize(at + 2 * (size_t)fl + 1);
+				if (strand == 0) for (int k = 0; k < fl; ++k) { o[at + k] = "ACGT"[nt_seq[fl - 1 - k] & 3]; o[at + fl + 1 + k] = (char)nt_qual[k]; }
+				else for (int k = 0; k < fl; ++k) { o[at + k] = "TGCA"[nt_seq[k] & 3]; o[at + fl + 1 + k] = (char)nt_qual[fl - 1 - k]; }
+				o[at + fl] = '\t';
+			} else {
+				/* (an unmapped colour read beside its mapped mate: bwa_seq_t.full_len is still the untrimmed length; strand and pos are the mate's) */
+				const int fl = rd.full_len[i];
+				const size_t at = o.size();
+				o.resize(at + (size_t)fl);
+				/* codes 0-5: "ACGTN"[5] is the literal's terminating NUL, the byte the reference's putchar writes for a '-' */
+				if (strand == 0) for (int k = 0; k < fl; ++k) o[at + k] = "ACGTN"[fwd[k]];
+				else for (int k = 0; k < fl; ++k) o[at + k] = "TGCAN"[fwd[fl - 1 - k]];
+				o += '\t';
+				put_qual(o, rd, i, strand, plen);
+			}
+			tags_head(o, p, bc, tag_full);
 			if (p.type != 0) {
 				char XT = "NURM"[p.type];
 				if (nn > 10) XT = 'N';
@@ -273,7 +299,7 @@ struct Printer {
 			else for (int k = 0; k < plen; ++k) { const uint8_t c = fwd[plen - 1 - k]; o[at + k] = "ACGTN"[c < 4 ? 3 - c : c]; }
 			o += '\t';
 			put_qual(o, rd, i, p.strand, plen);
-			tags_head(o, p, rd, i, bc);
+			tags_head(o, p, bc, tag_full);
 			if (mate && mate->type != 0) {                               /* the mate's XN (bwase.c:586-590) */
 				int m_seqid;
 				const int nn = pac2real(mate->pos, mate->len, &m_seqid);
@@ -282,12 +308,12 @@ struct Printer {
 			o += '\n';
 		}
 	}
-	void tags_head(std::string &o, const nabwa_se_t &p, const Reads &rd, int i, const std::string &bc) const
+	void tags_head(std::string &o, const nabwa_se_t &p, const std::string &bc, int full_len) const
 	{
 		char b[64];
 		if (!rg_id.empty()) { o += "\tRG:Z:"; o += rg_id; }
 		if (!bc.empty()) { o += "\tBC:Z:"; o += bc; }
-		if (p.clip_len < rd.full_len[i]) { snprintf(b, sizeof b, "\tXC:i:%d", p.clip_len); o += b; }
+		if (p.clip_len < full_len) { snprintf(b, sizeof b, "\tXC:i:%d", p.clip_len); o += b; }
 	}
 };
 
@@ -339,9 +365,14 @@ static int usage()
 			"         -P       accepted for compatibility; the index is always resident on the GPU\n"
 			"         -s       disable Smith-Waterman for the unmapped mate\n"
 			"         -A       disable insert size estimate (force -s)\n\n"
+			"Colour space (.sai files from `nabwa_aln -c`): needs <prefix>.nt.ann, .nt.amb and .nt.pac, FASTQ reads (the conversion to\n"
+			"nucleotides reads the qualities; the reference reads a null pointer without them, cs2nt.c:129), R3 reads first and -s or -A\n"
+			"(the reference's mate rescue crashes in colour space, bwape.c:651).  Anything else is refused with exit status 1.\n\n"
 			"Environment: NABWA_DEVICE picks the GPU [0].  Exit status 1: bad input, 2: no usable GPU.\n\n");
 #else
 	fprintf(stderr, "Usage: " TOOL " [-n max_occ] [-f out.sam] [-r RG_line] <prefix> <in.sai> <in.fq>\n"
+			"Colour space (a .sai from `nabwa_aln -c`): needs <prefix>.nt.ann, .nt.amb and .nt.pac, and FASTQ reads (the conversion to\n"
+			"nucleotides reads the qualities; the reference reads a null pointer without them, cs2nt.c:129); else exit status 1.\n"
 			"Environment: NABWA_DEVICE picks the GPU [0].  Exit status 1: bad input, 2: no usable GPU.\n");
 #endif
 	return 1;
@@ -406,10 +437,22 @@ static int run(int argc, char *argv[])
 	for (int f = 0; f < n_files; ++f) {
 		if (!sai[f].open(fn_sai[f])) fail(std::string("cannot open ") + fn_sai[f]);
 		if (!sai[f].header(&gopt[f])) fail(std::string(fn_sai[f]) + " is too short for a .sai header");
-		if (!(gopt[f].mode & NABWA_MODE_COMPREAD)) fail(std::string(fn_sai[f]) + " is a colour-space .sai; colour space is not supported");
 	}
 	/* sampe reads file 1 with the first .sai's mode and trimming, file 2 with the second's, and prints both with the second's option block (bwape.c:687-690) */
 	const nabwa_gap_opt_t &opt = gopt[n_files - 1];
+	const bool colour = !(opt.mode & NABWA_MODE_COMPREAD);              /* bwase.c:680, bwape.c:690-692 */
+	if (colour) {
+		for (const char *ext : { ".nt.ann", ".nt.amb", ".nt.pac" }) {
+			const std::string p = std::string(prefix) + ext;
+			if (access(p.c_str(), R_OK) != 0) fail(std::string(fn_sai[n_files - 1]) + " is a colour-space .sai and " + p + " cannot be read (an index built with `nabwa_index -c` has it)");
+		}
+#if SAI2SAM_PE
+		if (popt.is_sw && !popt.force_isize)
+			fail(std::string(fn_sai[1]) + " is a colour-space .sai: give -s or -A (there is no mate rescue in colour space; the reference's crashes there, bwape.c:651)");
+		popt.type = 2;                                                   /* BWA_PET_SOLID */
+		popt.is_sw = 0;
+#endif
+	}
 	Input in[2];
 	for (int f = 0; f < n_files; ++f) {
 		if ((unsigned)gopt[f].mode >> 24 > MAX_BCLEN) fail("the maximum barcode length is 63");
@@ -429,6 +472,7 @@ static int run(int argc, char *argv[])
 	nabwa_index_t *ix = nullptr;
 	int rc = nabwa_index_load(prefix, device, 1, 0, &ix);
 	if (rc == NABWA_OK) rc = nabwa_index_attach_reference(ix, prefix);
+	if (rc == NABWA_OK && colour) rc = nabwa_index_attach_nt_reference(ix, prefix);
 	if (rc != NABWA_OK) {
 		fprintf(stderr, "[" TOOL "] loading the index failed: %s\n", nabwa_last_error());
 		return rc == NABWA_ENODEV || rc == NABWA_ENOMEM ? 2 : 1;
@@ -490,6 +534,7 @@ static int run(int argc, char *argv[])
 
 	/* ---- GPU: the finishing chain of one chunk */
 	long long tot = 0;
+	double t_decode[2] = { 0, 0 };                                      /* colour space: seconds of the decode stage, milliseconds of its kernels */
 	auto gpu_chunk = [&](Chunk &k) {
 		const double ts = now();
 		fputs(k.log.c_str(), stderr);
@@ -510,6 +555,11 @@ static int run(int argc, char *argv[])
 			ii.low = ii.high = 0; ii.avg = ii.std = -1.0;
 		}
 		int cnt_chg = 0;
+		if (colour) {
+			k.nt_seq.assign(k.seq.size(), 0); k.nt_rseq.assign(k.seq.size(), 0); k.nt_qual.assign(k.seq.size(), 0);
+			r = nabwa_pe_finish_sampe_cs(ix, &opt, &popt, &ii, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.qual.data(), k.n_aln.data(), k.aln.data(),
+										 k.pe.data(), cache, &cnt_chg, k.nt_seq.data(), k.nt_rseq.data(), k.nt_qual.data(), t_decode);
+		} else
 		r = nabwa_pe_finish_sampe(ix, &opt, &popt, &ii, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.n_aln.data(), k.aln.data(), k.pe.data(),
 								  cache, &cnt_chg, nullptr, nullptr);
 		if (r != NABWA_OK) {
@@ -520,6 +570,11 @@ static int run(int argc, char *argv[])
 		last_ii = ii;
 #else
 		k.se.resize((size_t)k.n);
+		if (colour) {
+			k.nt_seq.assign(k.seq.size(), 0); k.nt_rseq.assign(k.seq.size(), 0); k.nt_qual.assign(k.seq.size(), 0);
+			r = nabwa_se_finish_cs(ix, &opt, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.qual.data(), k.full_len.data(), k.n_aln.data(), k.aln.data(),
+								   n_occ, &rng48, k.se.data(), k.nt_seq.data(), k.nt_rseq.data(), k.nt_qual.data(), t_decode);
+		} else
 		r = nabwa_se_finish(ix, &opt, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.full_len.data(), k.n_aln.data(), k.aln.data(),
 							n_occ, &rng48, k.se.data());
 		if (r != NABWA_OK) {
@@ -545,11 +600,14 @@ static int run(int argc, char *argv[])
 #if SAI2SAM_PE
 				const nabwa_pe_t &a = k.pe[2 * (size_t)i], &b = k.pe[2 * (size_t)i + 1];
 				const std::string bc = (k.r[0].bc[i].empty() && k.r[1].bc[i].empty()) ? std::string() : k.r[0].bc[i] + k.r[1].bc[i];   /* bwape.c:734-737 */
-				pr.print1(o, a.se, a.mapQ_paired, a.extra_flag & (F_PD | F_PP | F_R1 | F_R2), &b.se, k.r[0], i, bc);
-				pr.print1(o, b.se, b.mapQ_paired, b.extra_flag & (F_PD | F_PP | F_R1 | F_R2), &a.se, k.r[1], i, bc);
+				const uint8_t *ns = colour ? k.nt_seq.data() : nullptr, *nq = colour ? k.nt_qual.data() : nullptr;
+				const int64_t oa = k.off[2 * (size_t)i], ob = k.off[2 * (size_t)i + 1];
+				pr.print1(o, a.se, a.mapQ_paired, a.extra_flag & (F_PD | F_PP | F_R1 | F_R2), &b.se, k.r[0], i, bc, ns ? ns + oa : ns, nq ? nq + oa : nq);
+				pr.print1(o, b.se, b.mapQ_paired, b.extra_flag & (F_PD | F_PP | F_R1 | F_R2), &a.se, k.r[1], i, bc, ns ? ns + ob : ns, nq ? nq + ob : nq);
 #else
 				const nabwa_se_t &s = k.se[(size_t)i];
-				pr.print1(o, s, s.mapQ, 0, nullptr, k.r[0], i, k.r[0].bc[i]);
+				pr.print1(o, s, s.mapQ, 0, nullptr, k.r[0], i, k.r[0].bc[i], colour ? k.nt_seq.data() + k.off[(size_t)i] : nullptr,
+						  colour ? k.nt_qual.data() + k.off[(size_t)i] : nullptr);
 #endif
 			}
 		};
@@ -606,5 +664,9 @@ static int run(int argc, char *argv[])
 	fprintf(stderr, "[" TOOL "] main thread: first chunk parsed %.2f sec (fill), GPU chain %.2f sec, waited for the parser %.2f sec and for "
 			"the writer %.2f sec, last chunk's text and write %.2f sec (drain), other %.2f sec\n", t_first_parse, t_gpu, t_wait_parse, t_wait_write, t_drain,
 			t_run - (t_first_parse + t_gpu + t_wait_parse + t_wait_write + t_drain));
+	if (colour) {
+		const double dec_s = t_decode[0], dec_ms = t_decode[1];
+		fprintf(stderr, "[" TOOL "] colour space: decoding the mapped reads took %.3f sec of the GPU chain (records, copies and kernels; the kernels alone %.2f ms)\n", dec_s, dec_ms);
+	}
 	return 0;
 }

@@ -22,9 +22,8 @@
 
 /* ------------------------------------------------------------------ reference annotations */
 
-extern "C" int nabwa_index_attach_reference(nabwa_index_t *ix, const char *prefix)
+int nabwa_reference_read(const char *prefix, nabwa_reference **out)
 {
-	if (!ix || !prefix) return nabwa_fail(NABWA_EINVAL, "null argument");
 	nabwa_reference *R = new nabwa_reference();
 	std::string p(prefix);
 	FILE *f = fopen((p + ".ann").c_str(), "r");                       /* format: bns_dump / bns_restore_core, bntseq.c:63-117 */
@@ -56,6 +55,15 @@ extern "C" int nabwa_index_attach_reference(nabwa_index_t *ix, const char *prefi
 	R->pac.resize(sz + 8);
 	if (fread(R->pac.data(), 1, sz, f) != (size_t)sz || sz < R->l_pac / 4) { fclose(f); delete R; return nabwa_fail(NABWA_EIO, "short %s.pac", prefix); }
 	fclose(f);
+	*out = R;
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_index_attach_reference(nabwa_index_t *ix, const char *prefix)
+{
+	if (!ix || !prefix) return nabwa_fail(NABWA_EINVAL, "null argument");
+	nabwa_reference *R = nullptr;
+	if (const int r = nabwa_reference_read(prefix, &R)) return r;
 	delete ix->ref;
 	ix->ref = R;
 	return NABWA_OK;
@@ -264,16 +272,7 @@ int nabwa_se_refine_strided(nabwa_index_t *ix, int n, const int64_t *off, const 
 			nabwa_se_t &s = *rec_at(out_base, stride, i);
 			if (s.type == 0) { s.flag = 4; continue; }
 			if (!md_and_trim(R, s, seq + off[i], rseq + off[i], fwd)) md_over = 1;
-			int64_t end = s.pos;
-			if (s.n_cigar) { for (int k = 0; k < s.n_cigar; ++k) { const int op = COP(s.cigar[k]); if (op == 0 || op == 2) end += CLEN(s.cigar[k]); } }
-			else end += s.len;
-			const int reflen = (int)(end - s.pos);
-			s.nn = pac2real(R, s.pos, reflen, &s.seqid);
-			s.flag = 0;
-			if ((int64_t)s.pos + reflen - R->anns[s.seqid].offset > R->anns[s.seqid].len) { s.flag |= 4; s.mapQ = 0; }   /* bridges two contigs */
-			if (s.strand) s.flag |= 16;
-			s.rpos = (int64_t)s.pos - R->anns[s.seqid].offset + 1;
-			s.xt = s.nn > 10 ? 'N' : "NURM"[s.type];
+			se_flags(R, s);
 		}
 	};
 	host_parallel(host_threads((size_t)n, 4096), (size_t)n, [&](int, size_t lo, size_t hi) { phase4((int)lo, (int)hi); });

@@ -17,6 +17,7 @@
 #include <vector>
 #include "../../include/nabwa.h"
 #include "nabwa_internal.hpp"
+#include "dev_pool.hpp"
 #include "finish_common.hpp"
 
 #define CS_COLOR_MM 19          /* cs2nt.c:24-25 */
@@ -167,17 +168,6 @@ __global__ __launch_bounds__(256) void cs2nt_finish_kernel(int nm, const CsRec *
 	}
 }
 
-struct DevBuf {
-	void *p = nullptr;
-	~DevBuf() { if (p) (void)hipFree(p); }
-	int get(size_t bytes) { HIP_CHECK(hipMalloc(&p, bytes ? bytes : 1)); return NABWA_OK; }
-	template <class T> T *as() const { return (T*)p; }
-};
-struct DevEvents {
-	hipEvent_t a = nullptr, b = nullptr;
-	~DevEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 }
 
 /* ------------------------------------------------------------------ the flat entry */
@@ -287,11 +277,11 @@ int nabwa_cs2nt_records(nabwa_index_t *ix, void *base, size_t stride, int n, con
 	HIP_CHECK(hipMemset(d_oseq.p, 0, tot));
 	HIP_CHECK(hipMemset(d_orseq.p, 0, tot));
 	HIP_CHECK(hipMemset(d_oqual.p, 0, tot));
-	DevEvents ev;
-	HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+	DevEvent ev_a, ev_b;
+	HIP_CHECK(hipEventCreate(&ev_a.e)); HIP_CHECK(hipEventCreate(&ev_b.e));
 	const dim3 grid((nm + 255) / 256), block(256);
 	const double t1 = now_s();
-	HIP_CHECK(hipEventRecord(ev.a, 0));
+	HIP_CHECK(hipEventRecord(ev_a, 0));
 	hipLaunchKernelGGL(cs2nt_prep_kernel, grid, block, 0, 0, nm, cap, d_rec.as<CsRec>(), d_cig.as<uint16_t>(), d_seq.as<uint8_t>(), d_rseq.as<uint8_t>(),
 					   d_qual.as<uint8_t>(), ix->d_ntpac, (int64_t)ix->ref_nt->l_pac, d_ref.as<uint8_t>(), d_cs.as<uint8_t>(), d_size.as<int32_t>());
 	hipLaunchKernelGGL(cs2nt_core_kernel<1>, grid, block, 0, 0, nm, (const int64_t*)nullptr, d_size.as<int32_t>(), d_ref.as<uint8_t>(), d_cs.as<uint8_t>(),
@@ -299,9 +289,9 @@ int nabwa_cs2nt_records(nabwa_index_t *ix, void *base, size_t stride, int n, con
 	hipLaunchKernelGGL(cs2nt_finish_kernel, grid, block, 0, 0, nm, d_rec.as<CsRec>(), d_size.as<int32_t>(), d_dec.as<uint8_t>(), d_oseq.as<uint8_t>(),
 					   d_orseq.as<uint8_t>(), d_oqual.as<uint8_t>());
 	HIP_CHECK(hipGetLastError());
-	HIP_CHECK(hipEventRecord(ev.b, 0));
-	HIP_CHECK(hipEventSynchronize(ev.b));
-	float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b));
+	HIP_CHECK(hipEventRecord(ev_b, 0));
+	HIP_CHECK(hipEventSynchronize(ev_b));
+	float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ev_a, ev_b));
 	const double t2 = now_s();
 	std::vector<int32_t> size((size_t)nm);
 	HIP_CHECK(hipMemcpy(size.data(), d_size.p, (size_t)nm * 4, hipMemcpyDeviceToHost));

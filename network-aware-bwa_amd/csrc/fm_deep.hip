@@ -3,6 +3,7 @@
 // Block = ONE wave (64 threads): everything the wave shares (per-score counts and top pages) is its block's LDS, and
 // __syncthreads() is the wave's own memory fence.  Persistent grid: n_waves blocks draw reads from a counter.
 #include "fm_deep_body.hpp"
+#include "launchers.hpp"
 
 #ifndef NABWA_DEEP_WAVES
 #define NABWA_DEEP_WAVES 4    // waves per SIMD the register budget is bounded for: 128 VGPRs (22 spilled dwords), 16 searches per CU.  The trade-off was

@@ -6,6 +6,7 @@
 //  * sa_lookup_kernel : bwt_sa / bwt_invPsi (bwt.c:72-81, bwt.h:71-75), one row per lane.
 //  * occ4_kernel : bwt_occ4 for tests.
 #include "nabwa_dev.hpp"
+#include "launchers.hpp"
 
 // base j of B0 in the reference word stream
 __device__ __forceinline__ uint32_t ref_base(const uint32_t *w, uint32_t j)

@@ -37,6 +37,7 @@
 // are flagged and searched from the start by kernel D (fm_deep.hip: one search per wavefront, paged arenas) -- never on the CPU.
 #include "nabwa_dev.hpp"
 #include "fm_search.hpp"
+#include "launchers.hpp"
 
 #define ST_IDLE   0
 #define ST_WIDTH  1
@@ -411,7 +412,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 	};
 	auto push_mem = [&](int score, uint4 e) {
 		if (ovf || never_popped(score)) return;
-		if ((uint32_t)score >= P.NS) { ovf = true; return; }       // cannot happen (nabwa_api.hip sizes NS); the second pass would take over
+		if ((uint32_t)score >= P.NS) { ovf = true; return; }       // cannot happen (nabwa_batch.hip sizes NS); the second pass would take over
 		if (bump >= P.cap) { ovf = true; return; }
 		const uint32_t s = bump++;
 		const uint32_t prev = mask_has(score) ? head_get(score) : NIL;

@@ -1,4 +1,4 @@
-// host_util.hpp -- the library's host plumbing: the NABWA_TIMING clock and slices of independent records on host threads.
+// host_util.hpp -- the library's host plumbing: the NABWA_TIMING clock, integer switches of the environment and slices of independent records on host threads.
 #pragma once
 #include <stdlib.h>
 #include <chrono>
@@ -7,6 +7,13 @@
 
 /* wall clock of the NABWA_TIMING lines, in seconds */
 static inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+/* an integer switch of the environment; unset or empty: dflt */
+static inline int env_int(const char *name, int dflt)
+{
+	const char *s = getenv(name);
+	return s && *s ? atoi(s) : dflt;
+}
 
 /* threads for n independent records: the cores, at most 16, or NABWA_HOST_THREADS (a value below 1 counts as 1); one thread
  * when n < min_n.  min_n is 4096 in the SE / PE finishing chains and refine_batch, 8192 in the BAM front-end, 65536 in

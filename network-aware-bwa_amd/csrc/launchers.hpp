@@ -1,0 +1,46 @@
+// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip and fm_deep.hip, declared once.
+// The defining files and every host unit that calls one include this header, so a parameter list that differs between the two sides
+// is a compile error (C linkage carries no types).  Host side only: the kernel headers (nabwa_dev.hpp, fm_search.hpp, fm_deep.hpp,
+// fm_deep_body.hpp) do not include it -- the CPU emulation of the tests compiles those without HIP.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "fm_deep.hpp"
+
+extern "C" {
+/* fm_index.hip */
+void nabwa_launch_repack(const uint32_t *w, uint32_t seq_len, uint32_t n_buckets, uint4 *out, hipStream_t s);
+void nabwa_launch_kmer_level(const DevBwt *B, const uint2 *prev, uint2 *cur, uint64_t n_cur, hipStream_t s);
+void nabwa_launch_sa_fill(const DevBwt *B, uint32_t *sa_full, uint32_t *isa, uint8_t *text_bytes, hipStream_t s);
+void nabwa_launch_text_pack(const uint8_t *bytes, uint32_t n, uint32_t n_words, uint32_t *out, hipStream_t s);
+void nabwa_launch_sa_lookup(const DevBwt *B, int n, const uint8_t *which, const uint32_t *k, uint32_t *out, hipStream_t s);
+void nabwa_launch_occ4(const DevBwt *B, int n, const uint32_t *k, uint32_t *out, hipStream_t s);
+/* fm_search.hip */
+void nabwa_launch_fm_search(const SearchParams *P, int n_blocks, hipStream_t s);
+void nabwa_launch_fm_width(const SearchParams *P, int n_blocks, hipStream_t s);
+int nabwa_width_occupancy(void);
+int nabwa_search_occupancy(int ns);
+void nabwa_launch_checksum(int n, const int32_t *n_aln, const uint4 *aln, int aln_cap, const uint8_t *status,
+						   const int32_t *wide_idx, const uint4 *aln2, int aln_cap2, const uint4 *const *grown,
+						   unsigned long long *sum, unsigned long long *rows, hipStream_t s);
+void nabwa_launch_collect(int n, const uint8_t *status, int32_t *ids, unsigned int *count, int which, hipStream_t s);
+void nabwa_launch_collect_keyed(int n, const uint8_t *status, int32_t *ids, unsigned int *count, int which,
+								const uint8_t *cls, const uint8_t *md, int max_key, const int32_t *n_aln, int aln_cap, hipStream_t s);
+void nabwa_launch_assign_slots(int n2, const int32_t *ids, int32_t *wide_idx, hipStream_t s);
+void nabwa_launch_scatter_grown(int n2, const int32_t *ids, const int32_t *n_aln3, const int32_t *max_ent3, const uint8_t *status3,
+								 int32_t *n_aln, int32_t *max_ent, uint8_t *status, int32_t *wide_idx, const uint4 *block, size_t cap3,
+								 const uint4 **grown, int slot0, hipStream_t s);
+void nabwa_launch_scatter_wide(int n2, const int32_t *ids, const int32_t *n_aln2, const int32_t *max_ent2,
+							   const uint8_t *status2, int32_t *n_aln, int32_t *max_ent, uint8_t *status,
+							   int32_t *wide_idx, hipStream_t s);
+void nabwa_launch_gather(int n, const int32_t *n_aln, const uint32_t *row_off, const uint4 *aln, int aln_cap,
+						 const uint8_t *status, const int32_t *wide_idx, const uint4 *aln2, int aln_cap2,
+						 const uint4 *const *grown, uint4 *out, hipStream_t s);
+void nabwa_launch_partition(int n, const uint8_t *cls, int32_t *ids, unsigned int *cnt, hipStream_t s);
+void nabwa_launch_padded_len(int n, const int64_t *off, int64_t *plen, hipStream_t s);
+void nabwa_launch_pad_reads(int n, const uint8_t *seq, const uint8_t *rseq, const int64_t *off, const int64_t *poff,
+							uint8_t *pseq, uint8_t *prseq, int32_t *rd_len, uint32_t *rd_key, int T, int seed_len, uint32_t *rd_pack, int pack_stride,
+							const uint8_t *md_tab, const uint8_t *mg_tab, uint8_t *rd_md, uint8_t *rd_mg, hipStream_t s);
+/* fm_deep.hip */
+void nabwa_launch_fm_deep(const DeepParams *P, int n_waves, hipStream_t s);
+int nabwa_deep_occupancy(int ns, int lds_rd);
+}

@@ -1,0 +1,519 @@
+// nabwa_batch.hip -- one batch of reads through the search: upload and re-layout, kernels W and S, the hand-over of the searches
+// kernel S flags to kernel D (nabwa_batch_deep.hip), and the read-back of the hits.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <memory>
+#include <vector>
+#include "../../include/nabwa.h"
+#include "nabwa_batch.hpp"
+#include "host_util.hpp"
+
+static void layout(SearchParams &P, uint32_t cap, int max_len, int seed_len, uint32_t NS)
+{
+	// per-read width record
+	P.WL = align_up((uint32_t)max_len + 1, 16);
+	P.WLB = P.WL + 16;
+	P.SLB = align_up((uint32_t)(max_len > seed_len ? seed_len : 0) + 1, 16) + 16;      /* seed bounds exist only for reads longer than the seed (bwtaln.c:126-130) */
+	P.woff_bid = 2 * P.WL * 4;
+	P.woff_sbid = P.woff_bid + 2 * P.WLB;
+	P.wstride = align_up(P.woff_sbid + 2 * P.SLB, 64);
+	// per-lane search scratch
+	P.cap = cap; P.NS = NS;
+	P.lane_stride = align_up((size_t)cap * 16, 64);
+}
+
+extern "C" void nabwa_batch_destroy(nabwa_batch_t *b)
+{
+	if (!b) return;
+	(void)hipSetDevice(b->ix->device);
+	if (b->stream) (void)hipStreamSynchronize(b->stream);      /* the buffers go back to the pool, not to the driver: nothing may still use them */
+	delete b;
+}
+
+namespace {
+/* what nabwa_batch_create derives on the host from the option block and the read lengths */
+struct BatchShape {
+	int max_len = 0, min_len = 65535; int64_t padded_total = 0;
+	std::vector<uint8_t> md_tab, mg_tab;     /* by read length: what the search of such a read runs with */
+	uint32_t NS = 1, NS1 = 1;                /* score levels: the reference's formula; those the first pass can address */
+	bool deep_only = false;
+};
+}
+
+// ---- step 1 of nabwa_batch_create: per-read option derivation, on the host in double (bwtaln.c:102-106,125), and its refusals
+static int derive_options(const nabwa_gap_opt_t *opt, int n, const int64_t *off, int per_read, BatchShape &s)
+{
+	// One threaded pass over the read boundaries: validity, the lengths that occur, the padded size.  Everything per read
+	// that follows from its length alone (max_diff, max_gapo) is a table over lengths, applied on the device.
+	bool bad_len = false;
+	std::vector<uint8_t> seen(65536, 0);
+	{
+		const int NT = n >= (1 << 20) ? 4 : 1;
+		struct Part { int mx = 0, mn = 65535; int64_t padded = 0; bool bad = false; std::vector<uint8_t> seen; };
+		std::vector<Part> part(NT);
+		for (Part &q : part) q.seen.assign(65536, 0);
+		host_parallel(NT, (size_t)n, [&](int t, size_t i0, size_t i1) {
+			Part &q = part[t];
+			for (size_t i = i0; i < i1; ++i) {
+				const int64_t L = off[i + 1] - off[i];
+				if (L < 0 || L > 65535) { q.bad = true; continue; }
+				q.seen[L] = 1; q.padded += (L + 15) / 16 * 16;
+				if (L > q.mx) q.mx = (int)L;
+				if (L < q.mn) q.mn = (int)L;
+			}
+		});
+		for (auto &q : part) {
+			bad_len |= q.bad; s.padded_total += q.padded;
+			if (q.mx > s.max_len) s.max_len = q.mx;
+			if (q.mn < s.min_len) s.min_len = q.mn;
+			for (int L = 0; L < 65536; ++L) seen[L] |= q.seen[L];
+		}
+	}
+	if (bad_len) return nabwa_fail(NABWA_EINVAL, "read length outside 0..65535");
+	std::vector<int> md_of(s.max_len + 1, opt->max_diff);
+	if (opt->fnr > 0.0f) for (int L = 0; L <= s.max_len; ++L) md_of[L] = nabwa_cal_maxdiff(L, 0.02, opt->fnr);
+	s.md_tab.assign(s.max_len + 1, 0); s.mg_tab.assign(s.max_len + 1, 0);
+	int mdx = 0, mgx = 0;
+	for (int L = 0; L <= s.max_len; ++L) {
+		if (!seen[L]) continue;
+		const int md_sizing = md_of[per_read ? L : s.max_len];
+		int g = opt->max_gapo; if (md_sizing < g) g = md_sizing;
+		const int d = md_of[L];
+		/* kernel D's entries keep n_mm / n_gapo / n_gape in 8 bits each, the bound bytes of kernel W hold min(bid, 127) */
+		if (d < 0 || d > 126 || g < 0 || g > 255) return nabwa_fail(NABWA_EINVAL, "max_diff > 126 or max_gapo > 255 (unsupported)");
+		s.md_tab[L] = (uint8_t)d; s.mg_tab[L] = (uint8_t)g;
+		if (d > mdx) mdx = d;
+		if (g > mgx) mgx = g;
+		const long ns = (long)(md_sizing + 1) * opt->s_mm + (long)(g + 1) * opt->s_gapo + (long)(opt->max_gape + 1) * opt->s_gape;
+		if (ns > (long)s.NS) s.NS = (uint32_t)ns;
+	}
+	/* First pass: score levels that can actually hold an entry.  A child is only made of a parent that passed the
+	 * m >= 0 test (bwtgap.c:152-154), so it has at most max_diff + 1 counted differences, at most max_gapo opens and
+	 * max_gape extensions; its score is the largest index the per-score lists are addressed with.  (The formula above
+	 * is the reference's initial best_score, a value that is compared, never an index; the second pass still sizes by it.) */
+	{
+		const bool gape_counts = opt->mode & NABWA_MODE_GAPE;
+		for (int a = 0; a <= mdx + 1; ++a)
+			for (int g = 0; g <= mgx; ++g)
+				for (int e = 0; e <= (g ? opt->max_gape : 0); ++e) {
+					if (a + g + (gape_counts ? e : 0) > mdx + 1) continue;
+					const long sc = (long)a * opt->s_mm + (long)g * opt->s_gapo + (long)e * opt->s_gape;
+					if (sc + 1 > (long)s.NS1) s.NS1 = (uint32_t)(sc + 1);
+				}
+		if (s.NS1 > s.NS) s.NS1 = s.NS;
+	}
+	/* the reference packs the score into 11 bits (bwtgap.c:58) */
+	if (s.NS > 2048 || opt->s_mm < 0 || opt->s_gapo < 0 || opt->s_gape < 0 || opt->max_gape < 0 || opt->max_gape > 255)
+		return nabwa_fail(NABWA_EINVAL, "option block needs more than 2048 score levels (the reference's own limit)");
+	/* first-pass (kernel S) arena entries keep n_mm / n_gapo in 4 bits and n_gape in 5, and it tracks 64 score levels:
+	 * option blocks beyond that go to kernel D whole */
+	s.deep_only = mdx > 14 || mgx > 15 || opt->max_gape > 31 || s.NS1 > 64;
+	if (opt->seed_len < 0) return nabwa_fail(NABWA_EINVAL, "negative seed_len");
+	/* refused before any work, not when the first read reaches kernel D in the middle of a file: there a chain's matching child must be
+	 * the only child of its own score (fm_deep_body.hpp), so every penalty has to be positive (-M / -O / -E 0 have no use in practice) */
+	if (opt->s_mm < 1 || opt->s_gapo < 1 || opt->s_gape < 1) return nabwa_fail(NABWA_EINVAL, "s_mm, s_gapo and s_gape must be >= 1 (-M / -O / -E 0 are not supported)");
+	return NABWA_OK;
+}
+
+// ---- step 2: the reads, uploaded as given, then re-laid out on the device with 16-byte aligned starts
+static int upload_reads(nabwa_batch *b, const BatchShape &s, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, bool timing, double tc0)
+{
+	nabwa_index *ix = b->ix;
+	const int n = b->n, max_len = s.max_len;
+	const size_t nb = (size_t)off[n] > 0 ? (size_t)off[n] : 1, pnb = (size_t)s.padded_total + 64;
+	if ((uint64_t)pnb >= (1ull << 32)) return nabwa_fail(NABWA_EINVAL, "batch holds 4 Gi padded bases or more: split it (lane state keeps a 32-bit read offset)");
+	HIP_CHECK(b->d_seq.get(ix, pnb)); HIP_CHECK(b->d_rseq.get(ix, pnb));
+	HIP_CHECK(b->d_poff.get(ix, (size_t)(n + 1) * 8)); HIP_CHECK(b->d_len.get(ix, (size_t)(n ? n : 1) * 4));
+	HIP_CHECK(b->d_md.get(ix, n ? n : 1)); HIP_CHECK(b->d_mg.get(ix, n ? n : 1)); HIP_CHECK(b->d_key.get(ix, (size_t)(n ? n : 1) * 24));
+	b->pack_stride = 2 * ((max_len + 15) / 16 + 2);
+	HIP_CHECK(b->d_pack.get(ix, (size_t)(n ? n : 1) * b->pack_stride * 4));
+	HIP_CHECK(b->d_cls.get(ix, (size_t)(n ? n : 1) * 2)); HIP_CHECK(b->d_perm.get(ix, (size_t)(n ? n : 1) * 4)); HIP_CHECK(b->d_ncls.get(ix, 64));
+	if (n == 0) { HIP_CHECK(hipMemset(b->d_poff, 0, 8)); return NABWA_OK; }
+	PoolBuf<uint8_t> raw_s, raw_r, d_tab; PoolBuf<int64_t> raw_off, plen; PoolBuf<void> d_tmp; size_t tmp_bytes = 0;
+	StreamDrain drain{ b->stream };
+	HIP_CHECK(raw_s.get(ix, nb)); HIP_CHECK(raw_r.get(ix, nb)); HIP_CHECK(raw_off.get(ix, (size_t)(n + 1) * 8));
+	const UploadJob jobs[3] = { { raw_s, seq, (size_t)off[n] }, { raw_r, rseq, (size_t)off[n] }, { raw_off, off, (size_t)(n + 1) * 8 } };
+	const double tu0 = now_s();
+	HIP_CHECK(staged_upload(ix, jobs, 3));
+	if (timing) fprintf(stderr, "[nabwa] upload of %.2f GB: %.3f s (%.3f s into batch_create)\n", 2e-9 * (double)off[n], now_s() - tu0, tu0 - tc0);
+	// padded starts: exclusive scan of the padded lengths, on the device
+	HIP_CHECK(plen.get(ix, (size_t)(n + 1) * 8));
+	nabwa_launch_padded_len(n, raw_off, plen, b->stream);
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, plen.p, b->d_poff.p, n + 1, b->stream));
+	HIP_CHECK(d_tmp.get(ix, tmp_bytes ? tmp_bytes : 16));
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, plen.p, b->d_poff.p, n + 1, b->stream));
+	HIP_CHECK(d_tab.get(ix, 2 * (size_t)(max_len + 1)));
+	HIP_CHECK(hipMemcpyAsync(d_tab, s.md_tab.data(), max_len + 1, hipMemcpyHostToDevice, b->stream));
+	HIP_CHECK(hipMemcpyAsync(d_tab + max_len + 1, s.mg_tab.data(), max_len + 1, hipMemcpyHostToDevice, b->stream));
+	nabwa_launch_pad_reads(n, raw_s, raw_r, raw_off, b->d_poff, b->d_seq, b->d_rseq, b->d_len, b->d_key,
+						   ix->bwt[0].kmer_T == ix->bwt[1].kmer_T ? (int)ix->bwt[0].kmer_T : 0, b->opt.seed_len, b->d_pack, b->pack_stride,
+						   d_tab, d_tab + max_len + 1, b->d_md, b->d_mg, b->stream);
+	HIP_CHECK(hipStreamSynchronize(b->stream));
+	if (timing) fprintf(stderr, "[nabwa] re-layout kernel done %.3f s into batch_create\n", now_s() - tc0);
+	HIP_CHECK(raw_s.release()); HIP_CHECK(raw_r.release()); HIP_CHECK(raw_off.release());
+	HIP_CHECK(plen.release()); HIP_CHECK(d_tmp.release()); HIP_CHECK(d_tab.release());
+	return NABWA_OK;
+}
+
+// ---- step 3: the search parameters, the launch shape and the working buffers
+static int working_buffers(nabwa_batch *b, const BatchShape &s)
+{
+	nabwa_index *ix = b->ix;
+	const nabwa_gap_opt_t *opt = &b->opt;
+	const int n = b->n, max_len = s.max_len;
+	SearchParams &P = b->P;
+	memset(&P, 0, sizeof(P));
+	P.bwt[0] = ix->bwt[0]; P.bwt[1] = ix->bwt[1];
+	{	/* the per-index constants the search kernels pick per lane, as a table for their LDS (fm_search.hpp) */
+		uint32_t tab[NABWA_IXTAB_WORDS];
+		nabwa_ixtab_fill(tab, ix->bwt);
+		HIP_CHECK(b->d_ixtab.get(ix, sizeof tab));
+		HIP_CHECK(hipMemcpy(b->d_ixtab, tab, sizeof tab, hipMemcpyHostToDevice));
+		P.ixtab = b->d_ixtab;
+	}
+	P.seq = b->d_seq; P.rseq = b->d_rseq; P.poff = b->d_poff; P.rd_len = b->d_len; P.rd_maxdiff = b->d_md; P.rd_maxgapo = b->d_mg; P.rd_key = b->d_key; P.rd_pack = b->d_pack; P.pack_stride = b->pack_stride;
+	P.text_mode = env_int("NABWA_TEXT_KERNELS", 7);      /* bit 0: text mode in the width kernel, bit 1: in the search kernel, bit 2: key form in the search kernel */
+	if (ix->bwt[0].kmer_T != ix->bwt[1].kmer_T) P.bwt[0].kmer_T = P.bwt[1].kmer_T = 0;
+	P.ids = 0; P.n = n;
+	P.s_mm = opt->s_mm; P.s_gapo = opt->s_gapo; P.s_gape = opt->s_gape; P.mode = opt->mode;
+	P.indel_end_skip = opt->indel_end_skip; P.max_del_occ = opt->max_del_occ; P.max_entries = opt->max_entries;
+	P.max_gape = opt->max_gape; P.max_seed_diff = opt->max_seed_diff; P.seed_len = opt->seed_len; P.max_top2 = opt->max_top2;
+	int cap1 = env_int("NABWA_CAP1", 4096);
+	if (cap1 < 16) cap1 = 16;
+	if (cap1 > 65534) cap1 = 65534;
+	layout(P, (uint32_t)cap1, max_len, opt->seed_len, s.deep_only ? 1u : s.NS1);
+	P.aln_cap = env_int("NABWA_ALNCAP1", 16);
+	P.sync_refill = env_int("NABWA_SYNC_REFILL", 0);
+	/* trips after which kernel S hands a search on to kernel D (0: never).  Seeded searches (the default options): measured 10 M x 100 bp,
+	 * 0 -> 123.6 ms per pass, 2000 -> 108.9 (1111 reads handed on, kernel D 2 ms), 1000 -> 116.2, 500 -> 189.6; 2 x 150 bp pairs: 2000 is the
+	 * optimum too.  Without a seed (reads no longer than seed_len: the ancient-DNA options) the searches that do not end early are deep, and
+	 * every trip kernel S spends on them is spent again by kernel D: 6.25 M reads, 300 / 1000 / 2000 / 5000 -> 2.29 / 2.20 / 2.20 / 2.04 M reads/s */
+	P.trip_budget = (uint32_t)env_int("NABWA_TRIP_BUDGET", max_len > opt->seed_len ? 2000 : 300);
+	P.trip_budget_hard = (uint32_t)env_int("NABWA_TRIP_BUDGET_HARD", max_len > opt->seed_len ? 200 : (int)P.trip_budget);      /* (a batch of reads that mostly occur on neither strand: fm_search.hip) */
+	if (getenv("NABWA_TRIP_BUDGET") && !getenv("NABWA_TRIP_BUDGET_HARD")) P.trip_budget_hard = P.trip_budget;                       /* (a sweep of the one knob means the one budget) */
+	b->class_sort = env_int("NABWA_CLASS_SORT", 1);
+	{
+		P.w_sync = (n > 0 && s.min_len == max_len) ? env_int("NABWA_W_SYNC", 1) : 0;
+	}
+	if (P.aln_cap < 1) P.aln_cap = 1;
+
+	hipDeviceProp_t prop;
+	HIP_CHECK(hipGetDeviceProperties(&prop, ix->device));
+	int occ = nabwa_search_occupancy(s.deep_only ? 1 : (int)s.NS1);
+	if (occ < 1) occ = 1;
+	const int occ_env = env_int("NABWA_BLOCKS_PER_CU", 0);
+	if (occ_env > 0) occ = occ_env;
+	long blocks = (long)prop.multiProcessorCount * occ;
+	const long need = ((long)n + NABWA_SEARCH_BLOCK - 1) / NABWA_SEARCH_BLOCK;
+	if (blocks > need) blocks = need;
+	if (blocks < 1) blocks = 1;
+	b->n_blocks = (int)blocks;
+	if (getenv("NABWA_TIMING")) fprintf(stderr, "[nabwa] search kernel: %u score levels, %d blocks per CU (LDS %zu B per block), %ld blocks\n", s.NS1, occ,
+										(size_t)s.NS1 * NABWA_SEARCH_BLOCK * 2 + NABWA_SEARCH_BLOCK * 80, blocks);
+	HIP_CHECK(b->d_scratch.get(ix, (size_t)blocks * NABWA_SEARCH_BLOCK * P.lane_stride));
+	int occw = nabwa_width_occupancy(); if (occw < 1) occw = 1;
+	long blocks_w = (long)prop.multiProcessorCount * occw;
+	if (blocks_w > 2 * need) blocks_w = 2 * need;        /* kernel W: one lane per strand of a read */
+	if (blocks_w < 1) blocks_w = 1;
+	b->n_blocks_w = (int)blocks_w;
+	HIP_CHECK(b->d_wdata.get(ix, (size_t)(n ? n : 1) * P.wstride));
+	HIP_CHECK(b->d_nN.get(ix, n ? n : 1));
+	P.wdata = b->d_wdata; P.rd_nN = b->d_nN;
+	const size_t n1 = n ? n : 1;
+	HIP_CHECK(b->d_naln.get(ix, n1 * 4)); HIP_CHECK(b->d_maxent.get(ix, n1 * 4)); HIP_CHECK(b->d_wide_idx.get(ix, n1 * 4));
+	HIP_CHECK(b->d_status.get(ix, n1)); HIP_CHECK(b->d_aln.get(ix, n1 * (size_t)P.aln_cap * 16));
+	HIP_CHECK(b->d_counter.get(ix, 16)); HIP_CHECK(b->d_novf.get(ix, 4)); HIP_CHECK(b->d_ovf_ids.get(ix, n1 * 4));
+	HIP_CHECK(b->d_sum.get(ix, 256));
+	P.scratch = b->d_scratch; P.n_aln = b->d_naln; P.max_ent = b->d_maxent; P.status = b->d_status; P.aln = b->d_aln;
+	P.work_counter = b->d_counter;
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, const int64_t *off,
+								  const uint8_t *seq, const uint8_t *rseq, int per_read, nabwa_batch_t **out)
+{
+	if (!ix || !opt || !off || !out || n < 0 || (n && (!seq || !rseq))) return nabwa_fail(NABWA_EINVAL, "null argument");
+	HIP_CHECK(hipSetDevice(ix->device));
+	const bool timing = getenv("NABWA_TIMING") != 0;
+	const double tc0 = now_s();
+	BatchShape s;
+	if (int r = derive_options(opt, n, off, per_read, s)) return r;
+
+	const double tc1 = now_s();
+	std::unique_ptr<nabwa_batch, void (*)(nabwa_batch*)> b(new nabwa_batch(), nabwa_batch_destroy);      /* a half-built batch goes the way of a whole one */
+	b->ix = ix; b->opt = *opt; b->n = n; b->deep_only = s.deep_only ? 1 : 0;
+	b->max_len = s.max_len; b->min_len = n ? s.min_len : 0; b->NS1 = s.NS1; b->NS_wide = s.NS; b->deep_coop = -1;
+	/* a stream that does not synchronise with the legacy default stream: the finishing chains of another batch (bwt_sa batches, the
+	 * alignment kernels: default stream, synchronous copies) run from another thread while this batch's search kernels do; everything in
+	 * this file orders its own work on b->stream explicitly.  NABWA_STREAM_BLOCKING=1: the old kind, for comparison. */
+	if (env_int("NABWA_STREAM_BLOCKING", 0)) HIP_CHECK(hipStreamCreate(&b->stream.s));
+	else HIP_CHECK(hipStreamCreateWithFlags(&b->stream.s, hipStreamNonBlocking));
+	for (DevEvent *e : { &b->ev0, &b->ev1, &b->evw, &b->evd0, &b->evd1 }) HIP_CHECK(hipEventCreate(&e->e));
+	if (int r = upload_reads(b.get(), s, off, seq, rseq, timing, tc0)) return r;
+
+	const double tc2 = now_s();
+	if (int r = working_buffers(b.get(), s)) return r;
+	*out = b.release();
+	if (timing) fprintf(stderr, "[nabwa] batch_create %d reads: host option derivation %.3f s, read upload + device layout %.3f s, working buffers %.3f s\n", n, tc1 - tc0, tc2 - tc1, now_s() - tc2);
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_batch_run(nabwa_batch_t *b)
+{
+	if (!b) return nabwa_fail(NABWA_EINVAL, "null batch");
+	HIP_CHECK(hipSetDevice(b->ix->device));
+	b->unresolved = 0;
+	if (b->n == 0) return NABWA_OK;
+	if (b->n_grown) {          /* row blocks of the previous run's longest hit lists: that run's results are gone with this one */
+		HIP_CHECK(hipStreamSynchronize(b->stream));
+		for (int t = 0; t < b->n_grown; ++t) HIP_CHECK(b->grown[t].release());
+		b->n_grown = 0; b->grown_used = 0;
+	}
+	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
+	HIP_CHECK(hipMemsetAsync(b->d_novf, 0, 4, b->stream));
+	HIP_CHECK(hipEventRecord(b->evw, b->stream));
+	SearchParams PW = b->P; PW.ids = 0; PW.rd_cls = b->class_sort ? b->d_cls : 0;
+	nabwa_launch_fm_width(&PW, b->n_blocks_w, b->stream);
+	if (b->class_sort) {      /* work order of the search: reads with an exact occurrence first, in lockstep waves */
+		HIP_CHECK(hipMemsetAsync(b->d_ncls, 0, 64, b->stream));
+		nabwa_launch_partition(b->n, b->d_cls, b->d_perm, b->d_ncls, b->stream);
+	}
+	HIP_CHECK(hipEventRecord(b->ev0, b->stream));
+	SearchParams PS = b->P; PS.ids = b->class_sort ? b->d_perm : 0; PS.n_sync = b->class_sort ? b->d_ncls + 10 : 0;
+	if (!b->deep_only) nabwa_launch_fm_search(&PS, b->n_blocks, b->stream);
+	else {      /* option blocks the first-pass kernel's compact entries cannot hold: every read goes to kernel D */
+		HIP_CHECK(hipMemsetAsync(b->d_status, NABWA_ST_OVERFLOW, b->n, b->stream));
+		HIP_CHECK(hipMemsetAsync(b->d_naln, 0, (size_t)b->n * 4, b->stream));
+	}
+	HIP_CHECK(hipEventRecord(b->ev1, b->stream));
+	/* the reads the first pass hands on, in the order kernel D should start them (largest-looking searches first) */
+	if (b->class_sort && env_int("NABWA_DEEP_ORDER", 1)) nabwa_launch_collect_keyed(b->n, b->d_status, b->d_ovf_ids, b->d_novf, NABWA_ST_OVERFLOW, b->d_cls, b->d_md, 7, b->d_naln, b->P.aln_cap, b->stream);
+	else nabwa_launch_collect(b->n, b->d_status, b->d_ovf_ids, b->d_novf, NABWA_ST_OVERFLOW, b->stream);
+	HIP_CHECK(hipGetLastError());
+	b->ran = 1;
+	return NABWA_OK;
+}
+
+/* ---- nabwa_batch_sync: the reads kernel S flagged go to kernel D (nabwa_batch_deep.hip).  Optionally the first-pass kernel runs once
+ * more before that with the largest arena its 16-bit links address (NABWA_TIER_A=1). */
+
+// the kernel-W records of the listed reads again: a search edits them in place (gap_shadow)
+void rebuild_widths(nabwa_batch *b, const SearchParams &Q, unsigned int cnt, bool after_first_pass)
+{
+	SearchParams QW = Q; QW.touch_counter = 0; QW.rd_cls = 0; QW.n_sync = 0; QW.w_sync = 0;
+	/* only a search that found a hit has edited its record; after kernel D has had a read (the guaranteed pass, the searches with longer
+	 * hit lists) its record is rebuilt whatever it found */
+	QW.w_skip_clean = after_first_pass && env_int("NABWA_W_SKIP_CLEAN", 1) ? 1 : 0;
+	QW.n_aln = b->d_naln; QW.max_ent = b->d_maxent; QW.status = b->d_status; QW.aln = b->d_aln; QW.aln_cap = b->P.aln_cap;
+	long bw2 = (2 * (long)cnt + NABWA_SEARCH_BLOCK - 1) / NABWA_SEARCH_BLOCK;     /* one lane per strand */
+	if (bw2 > b->n_blocks_w) bw2 = b->n_blocks_w;
+	(void)hipMemsetAsync(b->d_counter, 0, 16, b->stream);       /* kernel W draws its work items from counter [1] */
+	nabwa_launch_fm_width(&QW, (int)bw2, b->stream);
+}
+
+/* the reads of status `which` into d_ovf_ids, their number into *left; the stream is idle afterwards */
+int recollect(nabwa_batch *b, int which, unsigned int *left)
+{
+	HIP_CHECK(hipMemsetAsync(b->d_novf, 0, 4, b->stream));
+	nabwa_launch_collect(b->n, b->d_status, b->d_ovf_ids, b->d_novf, which, b->stream);
+	HIP_CHECK(hipMemcpyAsync(left, b->d_novf, 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipStreamSynchronize(b->stream));
+	return NABWA_OK;
+}
+
+/* NABWA_TIER_A=1: the first-pass kernel once more over the *cur listed reads, with the largest arena its 16-bit links address */
+static int tier_a_rerun(nabwa_batch *b, unsigned int *cur, bool timing)
+{
+	const double tt0 = now_s();
+	SearchParams Q = b->P;
+	layout(Q, 65534u, b->max_len, b->opt.seed_len, b->P.NS);
+	long blocks = ((long)*cur + NABWA_SEARCH_BLOCK - 1) / NABWA_SEARCH_BLOCK;
+	size_t budget = (size_t)env_int("NABWA_WIDE_GB", 32) << 30;
+	const long fit = (long)(budget / ((size_t)NABWA_SEARCH_BLOCK * Q.lane_stride));
+	if (blocks > fit) blocks = fit < 1 ? 1 : fit;
+	const size_t need = (size_t)blocks * NABWA_SEARCH_BLOCK * Q.lane_stride;
+	if (b->scratch2_bytes < need) {
+		b->scratch2_bytes = 0;
+		HIP_CHECK(b->d_scratch2.release());
+		HIP_CHECK(b->d_scratch2.get(b->ix, need));
+		b->scratch2_bytes = need;
+	}
+	Q.scratch = b->d_scratch2; Q.ids = b->d_ovf_ids; Q.n = (int)*cur; Q.n_sync = 0; Q.w_sync = 0;
+	rebuild_widths(b, Q, *cur, false);
+	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
+	nabwa_launch_fm_search(&Q, (int)blocks, b->stream);
+	HIP_CHECK(hipGetLastError());
+	unsigned int left = 0;
+	if (int r = recollect(b, NABWA_ST_OVERFLOW, &left)) return r;
+	if (timing) fprintf(stderr, "[nabwa] first-pass kernel again, arena of 65534 entries: %u reads on %ld blocks, %u left, %.3f s\n", *cur, blocks, left, now_s() - tt0);
+	*cur = left;
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
+{
+	if (!b) return nabwa_fail(NABWA_EINVAL, "null batch");
+	HIP_CHECK(hipSetDevice(b->ix->device));
+	if (n_second_pass) *n_second_pass = 0;
+	if (b->n == 0) return NABWA_OK;
+	unsigned int novf = 0;
+	HIP_CHECK(hipMemcpyAsync(&novf, b->d_novf, 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipStreamSynchronize(b->stream));
+	HIP_CHECK(hipEventElapsedTime(&b->last_ms, b->ev0, b->ev1));
+	HIP_CHECK(hipEventElapsedTime(&b->last_ms_w, b->evw, b->ev0));
+	if (n_second_pass) *n_second_pass = (int)novf;
+	if (novf == 0) return NABWA_OK;
+	const bool timing = getenv("NABWA_TIMING") != 0;
+	unsigned int cur = novf;
+	b->deep_ran = 0; b->last_ms_deep = 0.f;
+	if (env_int("NABWA_TIER_A", 0) && b->P.cap < 65534 && b->deep_only == 0)
+		if (int r = tier_a_rerun(b, &cur, timing)) return r;
+	return cur ? deep_searches(b, cur, timing) : NABWA_OK;
+}
+
+extern "C" float nabwa_batch_last_kernel_ms(nabwa_batch_t *b) { return b ? b->last_ms : 0.f; }
+extern "C" float nabwa_batch_last_width_ms(nabwa_batch_t *b) { return b ? b->last_ms_w : 0.f; }
+extern "C" float nabwa_batch_last_deep_ms(nabwa_batch_t *b) { return b ? b->last_ms_deep : 0.f; }
+
+/* One extra, untimed run of both passes with the instrumented kernel: total Occ-bucket touches the
+ * REFERENCE algorithm performs on this batch (the "algorithmic bytes" of the roofline are 48 B each). */
+extern "C" int nabwa_batch_count_touches(nabwa_batch_t *b, uint64_t *n_bucket, uint64_t *n_bucket_width)
+{
+	if (!b || !n_bucket) return nabwa_fail(NABWA_EINVAL, "null argument");
+	HIP_CHECK(hipSetDevice(b->ix->device));
+	HIP_CHECK(hipMemsetAsync(b->d_sum, 0, 256, b->stream));
+	b->P.touch_counter = b->d_sum;
+	/* the reference walks every exact tail row by row: count with the tail jump off (NABWA_TRIP_STATS=jump keeps it
+	 * on to profile the production trips; the touch totals are then not the reference's) */
+	const uint32_t kt0 = b->P.bwt[0].kmer_T, kt1 = b->P.bwt[1].kmer_T; const int tm0 = b->P.text_mode;
+	const char *ts = getenv("NABWA_TRIP_STATS");
+	if (!(ts && strcmp(ts, "jump") == 0)) { b->P.bwt[0].kmer_T = b->P.bwt[1].kmer_T = 0; b->P.text_mode = 0; }
+	int r = nabwa_batch_run(b);
+	if (r == NABWA_OK) r = nabwa_batch_sync(b, 0);
+	b->P.touch_counter = 0;
+	b->P.bwt[0].kmer_T = kt0; b->P.bwt[1].kmer_T = kt1; b->P.text_mode = tm0;
+	if (r != NABWA_OK) return r;
+	unsigned long long v[2] = { 0, 0 };
+	HIP_CHECK(hipMemcpy(v, b->d_sum, 16, hipMemcpyDeviceToHost));
+	*n_bucket = v[0];                          /* search kernel (bwt_match_gap) */
+	if (n_bucket_width) *n_bucket_width = v[1];  /* width kernel (bwt_cal_width) */
+	if (getenv("NABWA_TRIP_STATS") && b->class_sort) {
+		unsigned int c[12];
+		HIP_CHECK(hipMemcpy(c, b->d_ncls, 48, hipMemcpyDeviceToHost));
+		fprintf(stderr, "[nabwa] read classes by restarts 0 / 1 / 2+: %u / %u / %u\n", c[0], c[1], c[2]);
+	}
+	if (getenv("NABWA_TRIP_STATS")) {
+		unsigned long long t[32];
+		HIP_CHECK(hipMemcpy(t, b->d_sum, 256, hipMemcpyDeviceToHost));
+		fprintf(stderr, "[nabwa] search kernel: wave-trips %llu; lane-trips: expand %llu exact %llu entry-load %llu spec %llu query %llu two-bucket %llu exited %llu tail-jump %llu text-expand %llu text-tail %llu; longest read %llu trips, %llu reads over 2000 trips, %llu over 500\n",
+				t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], t[15]);
+		fprintf(stderr, "[nabwa] the %llu reads over 8000 trips: %llu trips = expansions key-form %llu, rows two-bucket %llu, rows one-bucket %llu, text %llu (of all: %llu with gaps); pops %llu, tail steps %llu, jumps %llu\n",
+				t[16], t[17], t[18], t[19], t[20], t[21], t[25], t[22], t[23], t[24]);
+	}
+	return NABWA_OK;
+}
+
+/* Tests: the records kernel W writes for reads [first, first + n), unpacked: per read and strand the len + 1 interval widths
+ * and lower bounds of the full pass (bwt_cal_width, bwtaln.c:52-76, 123-124) and the seed_len + 1 bounds of the seed pass
+ * (:126-130; only for reads longer than the seed).  Runs kernel W alone on a fresh record.  Rows are max_len + 1 wide. */
+extern "C" int nabwa_batch_width_records(nabwa_batch_t *b, int first, int n, uint32_t *w_out, uint8_t *bid_out, uint8_t *seed_bid_out)
+{
+	if (!b || first < 0 || n < 0 || first + n > b->n || (n && (!w_out || !bid_out))) return nabwa_fail(NABWA_EINVAL, "bad argument");
+	if (n == 0) return NABWA_OK;
+	HIP_CHECK(hipSetDevice(b->ix->device));
+	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
+	SearchParams PW = b->P; PW.ids = 0; PW.rd_cls = 0; PW.touch_counter = 0;
+	nabwa_launch_fm_width(&PW, b->n_blocks_w, b->stream);
+	HIP_CHECK(hipGetLastError());
+	std::vector<uint8_t> rec((size_t)n * b->P.wstride);
+	HIP_CHECK(hipMemcpyAsync(rec.data(), b->d_wdata + (size_t)first * b->P.wstride, rec.size(), hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipStreamSynchronize(b->stream));
+	const int W = b->max_len + 1, SW = b->opt.seed_len + 1;
+	for (int i = 0; i < n; ++i) {
+		const uint8_t *r = rec.data() + (size_t)i * b->P.wstride;
+		for (int x = 0; x < 2; ++x) {
+			memcpy(w_out + ((size_t)i * 2 + x) * W, (const uint32_t*)r + x * b->P.WL, 4 * (size_t)W);
+			memcpy(bid_out + ((size_t)i * 2 + x) * W, r + b->P.woff_bid + x * b->P.WLB, (size_t)W);
+			if (seed_bid_out && b->max_len > b->opt.seed_len && SW <= (int)b->P.SLB) memcpy(seed_bid_out + ((size_t)i * 2 + x) * SW, r + b->P.woff_sbid + x * b->P.SLB, (size_t)SW);
+		}
+	}
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_batch_checksum(nabwa_batch_t *b, uint64_t *sum, int64_t *n_rows)
+{
+	if (!b) return nabwa_fail(NABWA_EINVAL, "null batch");
+	HIP_CHECK(hipSetDevice(b->ix->device));
+	unsigned long long h[2] = { 0, 0 };
+	HIP_CHECK(hipMemsetAsync(b->d_sum, 0, 16, b->stream));
+	nabwa_launch_checksum(b->n, b->d_naln, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
+						  b->d_sum, b->d_sum + 1, b->stream);
+	HIP_CHECK(hipMemcpyAsync(h, b->d_sum, 16, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipStreamSynchronize(b->stream));
+	if (sum) *sum = h[0];
+	if (n_rows) *n_rows = (int64_t)h[1];
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_batch_config(nabwa_batch_t *b, nabwa_batch_config_t *out)
+{
+	if (!b || !out) return nabwa_fail(NABWA_EINVAL, "null argument");
+	memset(out, 0, sizeof(*out));
+	out->n = b->n; out->min_len = b->min_len; out->max_len = b->max_len;
+	out->deep_only = b->deep_only; out->ns1 = (int32_t)b->NS1; out->ns_wide = (int32_t)b->NS_wide;
+	out->w_sync = b->P.w_sync; out->trip_budget = (int32_t)b->P.trip_budget; out->trip_budget_hard = (int32_t)b->P.trip_budget_hard;
+	out->n_sync = out->hard_budget = -1;
+	for (int q = 0; q < 3; ++q) out->cls[q] = -1;
+	if (b->ran && b->class_sort) {
+		HIP_CHECK(hipSetDevice(b->ix->device));
+		unsigned int c[12];
+		HIP_CHECK(hipMemcpyAsync(c, b->d_ncls, 48, hipMemcpyDeviceToHost, b->stream));
+		HIP_CHECK(hipStreamSynchronize(b->stream));
+		for (int q = 0; q < 3; ++q) out->cls[q] = (int32_t)c[q];
+		out->n_sync = (int32_t)c[10];
+		/* the rule of fm_search_kernel: the hard budget when most reads occur exactly on neither strand */
+		if (!b->deep_only) out->hard_budget = b->P.trip_budget_hard && 2u * c[10] > (uint32_t)b->n ? 1 : 0;
+	}
+	out->coop_lanes = b->deep_coop;
+	out->lds_rd = b->deep_cfg ? (int32_t)b->deep_lds_rd : -1;
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_batch_fetch(nabwa_batch_t *b, int32_t *n_aln, nabwa_aln1_t *aln_out, int64_t aln_cap, int64_t *n_rows,
+								 int32_t *max_entries)
+{
+	if (!b || !n_aln) return nabwa_fail(NABWA_EINVAL, "null argument");
+	HIP_CHECK(hipSetDevice(b->ix->device));
+	if (n_rows) *n_rows = 0;
+	if (b->n == 0) return NABWA_OK;
+	// device-side compaction: exclusive scan of n_aln, then gather rows
+	PoolBuf<uint32_t> d_off; PoolBuf<void> d_tmp; size_t tmp_bytes = 0; PoolBuf<uint4> d_rows;
+	StreamDrain drain{ b->stream };
+	HIP_CHECK(d_off.get(b->ix, (size_t)(b->n + 1) * 4));
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const uint32_t*)b->d_naln.p, d_off.p, b->n, b->stream));
+	HIP_CHECK(d_tmp.get(b->ix, tmp_bytes ? tmp_bytes : 16));
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, (const uint32_t*)b->d_naln.p, d_off.p, b->n, b->stream));
+	uint32_t last_off = 0; int32_t last_n = 0;
+	HIP_CHECK(hipMemcpyAsync(&last_off, d_off + (b->n - 1), 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipMemcpyAsync(&last_n, b->d_naln + (b->n - 1), 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipMemcpyAsync(n_aln, b->d_naln, (size_t)b->n * 4, hipMemcpyDeviceToHost, b->stream));
+	if (max_entries) HIP_CHECK(hipMemcpyAsync(max_entries, b->d_maxent, (size_t)b->n * 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipStreamSynchronize(b->stream));
+	const int64_t total = (int64_t)last_off + last_n;
+	if (n_rows) *n_rows = total;
+	int rc = NABWA_OK;
+	if (total > aln_cap || (total && !aln_out)) rc = nabwa_fail(NABWA_ECAP, "aln_cap too small");
+	else if (total) {
+		HIP_CHECK(d_rows.get(b->ix, (size_t)total * 16));
+		nabwa_launch_gather(b->n, b->d_naln, d_off, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
+							d_rows, b->stream);
+		HIP_CHECK(hipMemcpyAsync(aln_out, d_rows, (size_t)total * 16, hipMemcpyDeviceToHost, b->stream));
+		HIP_CHECK(hipStreamSynchronize(b->stream));
+		HIP_CHECK(d_rows.release());
+	}
+	HIP_CHECK(d_off.release()); HIP_CHECK(d_tmp.release());
+	return rc;
+}

@@ -18,19 +18,19 @@ struct nabwa_reference {          // bntseq_t + the packed reference (bntseq.h:5
 };
 
 struct nabwa_index {
-	int device;
-	DevBwt bwt[2];
-	uint4 *bk[2];
-	uint32_t *sa[2];
-	uint32_t *sa_full[2], *isa[2], *text[2];   // text-mode companions (nabwa_dev.hpp), null when switched off
-	uint2 *kmer[2], *kmer_top[2];  // interval table: levels 1..LW back to back; level T on its own when T > LW (else inside the former)
-	uint64_t bytes;
+	int device = 0;
+	DevBwt bwt[2] = {};
+	uint4 *bk[2] = {};
+	uint32_t *sa[2] = {};
+	uint32_t *sa_full[2] = {}, *isa[2] = {}, *text[2] = {};   // text-mode companions (nabwa_dev.hpp), null when switched off
+	uint2 *kmer[2] = {}, *kmer_top[2] = {};  // interval table: levels 1..LW back to back; level T on its own when T > LW (else inside the former)
+	uint64_t bytes = 0;
 	int kmer_T_pick = -1;           // depth of the interval tables, decided when the first direction is built
-	nabwa_reference *ref;
+	nabwa_reference *ref = nullptr;
 	nabwa_reference *ref_nt = nullptr;   // colour index: the annotations of `ref` over the bases of <prefix>.nt.pac (cs2nt.hip)
 	uint8_t *d_ntpac = nullptr;          // ... and those bases in HBM, with their size in bytes
 	uint64_t ntpac_bytes = 0;
-	struct nabwa_dev_pool *pool;   // released working buffers of earlier batches, kept for the next one (nabwa_api.hip)
+	struct nabwa_dev_pool *pool = nullptr;   // released working buffers of earlier batches, kept for the next one (dev_pool.hpp)
 };
 
 int nabwa_fail(int code, const char *fmt, const char *a = "");

@@ -195,7 +195,7 @@ extern "C" int emu_deep_search(const uint32_t *bwt0, const uint32_t *bwt1, const
 	S.s_mm = opt->s_mm; S.s_gapo = opt->s_gapo; S.s_gape = opt->s_gape; S.mode = opt->mode; S.indel_end_skip = opt->indel_end_skip;
 	S.max_del_occ = opt->max_del_occ; S.max_entries = opt->max_entries; S.max_gape = opt->max_gape; S.max_seed_diff = opt->max_seed_diff;
 	S.seed_len = opt->seed_len; S.max_top2 = opt->max_top2; S.text_mode = knobs[7] ? 2 : 0;
-	// width records (layout of nabwa_api.hip: layout())
+	// width records (layout of nabwa_batch.hip: layout())
 	S.WL = align_up((uint32_t)max_len + 1, 16); S.WLB = S.WL + 16; S.SLB = align_up((uint32_t)(opt->seed_len > 65535 ? 0 : opt->seed_len) + 1, 16) + 16;
 	S.woff_bid = 2 * S.WL * 4; S.woff_sbid = S.woff_bid + 2 * S.WLB; S.wstride = align_up(S.woff_sbid + 2 * S.SLB, 64);
 	std::vector<uint8_t> wdata((size_t)(n ? n : 1) * S.wstride, 0);

@@ -197,7 +197,7 @@ def test_wide_pass_is_bit_exact(gix, olib, oix, monkeypatch):
     {"NABWA_CAP1": "48", "NABWA_ALNCAP1": "1"},                              # the first pass fails on the hit lists too
 ], ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
 def test_flagged_reads_through_kernel_d_are_bit_exact(gix, monkeypatch, env):
-    """reads that outgrow the first pass go to kernel D (fm_deep_body.hpp; nabwa_api.hip: nabwa_batch_sync): speculative rounds
+    """reads that outgrow the first pass go to kernel D (fm_deep_body.hpp; nabwa_batch.hip: nabwa_batch_sync, nabwa_batch_deep.hip): speculative rounds
     of up to 64 chains, ordered commit, paged arenas -- the rows are the reference's, on the option set ancient-DNA pipelines
     use (deep searches), under every knob that changes how the rounds are cut"""
     for k, v in env.items():
@@ -382,7 +382,7 @@ def test_one_shot_entry_flat(gix, olib, oix, per_read):
 
 
 def test_staged_upload_and_pooled_buffers_on_a_large_batch(gix, olib, oix, monkeypatch):
-    """Host buffers of >= 256 MiB go up through four threads and pinned slots (nabwa_api.hip: staged_upload), and the
+    """Host buffers of >= 256 MiB go up through four threads and pinned slots (dev_pool.hip: staged_upload), and the
     working buffers of a call are handed to the next one (pool).  2.2 M reads x 100 bases x {seq, rseq} = 440 MB: every
     thread re-uses its slots.  Same answer as the plain hipMemcpy path on fresh buffers, and as the oracle on a sample."""
     rng = np.random.default_rng(99)

@@ -3,7 +3,7 @@
 For the text A^n every row is known in closed form: row r is the suffix A^r$, SA[r] = n - r, primary = n, L2 = [0, n, n, n, n], and the
 stored BWT (the primary row left out) is all A, so Occ(A, r) = min(r + 1, n).  Its `.bwt` words in the reference's layout (bwtio.c:184-204,
 bwtmisc.c:120-140) are built here in numpy at three sizes:
-  0xfffffefe  the largest text whose searches keep key form (nabwa_api.hip: seq_len < DEEP_KEYL - 1),
+  0xfffffefe  the largest text whose searches keep key form (nabwa_batch_deep.hip: seq_len < DEEP_KEYL - 1),
   0xffffff00  the first whose rows reach DEEP_KEYL (fm_deep.hpp): the root [0, n] and the T child's l are rows that look like the marker,
   0xffffffdf  the largest text the library loads (bwtio.c:175 wraps above it).
 At each size the oracle's occ4 on the wrapped words must give the closed form, and kernel D's CPU emulation (tests/emu/) must give the

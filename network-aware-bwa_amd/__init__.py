@@ -400,6 +400,22 @@ def _sai2sam(tool, args, operands, out, device, timeout):
     return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=timeout)
 
 
+WORKER_PATH = os.path.join(_HERE, "nabwa_worker")
+
+
+def worker(host, port, args=(), device=None, timeout=None):
+    """`bwa worker -h <host> -p <port> [args]` (reference bam2bam.c:2213-2309) with the alignment on the GPU: runs the nabwa_worker tool
+    until the master ends it and returns its subprocess.CompletedProcess (the log and the record counts in .stderr).  libzmq is bound
+    by the tool at run time (NABWA_ZMQ_LIB, libzmq.so.5, .so.3, .so); args: -t N connections, -T minutes."""
+    if not os.path.exists(WORKER_PATH):
+        raise RuntimeError("%s is missing: run __graft_entry__.build()" % WORKER_PATH)
+    env = dict(os.environ)
+    if device is not None:
+        env["NABWA_DEVICE"] = str(int(device))
+    cmd = [WORKER_PATH, "-h", str(host), "-p", str(int(port))] + [str(a) for a in args]
+    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=timeout)
+
+
 def index_build(prefix, device=0, sa_intv=32, verbose=False):
     """The FM-indexes of <prefix>.pac on the GPU: <prefix>.bwt, .rbwt, .sa, .rsa (reference bwtindex.c:104-191)."""
     _chk(lib().nabwa_index_build(os.fsencode(prefix), int(device), int(sa_intv), int(verbose)))

@@ -5,8 +5,8 @@
 // BAM in (BGZF, any other gzip stream or none, as the reference's bamlite reads it; bgzf_in.hpp) -> both passes of the reference's sequential loop
 // (bam2bam.c:1143-1216) through the batch front-end of the library (nabwa_bam_batch_*, bam_batch.hip) -> BGZF BAM out with
 // the header bwa_print_bam_header writes (@HD VN:1.4, a new @PG chained to the old one, @SQ from the .ann file, the other old
-// lines kept; bam2bam.c:164-301).  Host code only; the GPU work is the library's.  Not provided: the 0MQ master / worker modes
-// (-p, `bwa worker`: libzmq is absent from the build image) and resuming from .sai files (-0 -1 -2) -- each is refused, none is
+// lines kept; bam2bam.c:164-301).  Host code only; the GPU work is the library's.  Not provided: the 0MQ master mode
+// (-p; the worker side is nabwa_worker, worker_main.cpp) and resuming from .sai files (-0 -1 -2) -- each is refused, none is
 // silently ignored.  --only-aligned, --drop-aligned, --skip-duplicates, --broken-input and --debug-bam are the library's NABWA_BAM_* flags.
 // -t is accepted and ignored (NABWA_DEVICES=0,1,... names the GPUs: an index replica on each, batches dealt to them in turn, searched as
 // they come and passed in input order; default one GPU, NABWA_DEVICE or 0), --temp-dir likewise (the records wait in memory between the passes).

@@ -866,10 +866,24 @@ extern "C" int nabwa_bam_batch_restore(nabwa_bam_batch_t *b, const nabwa_wire_re
 	if (b->phase != 0 || b->searched) return nabwa_fail(NABWA_EINVAL, "restore needs a batch that was just created");
 	const int n = (int)b->rec.size();
 	b->n_aln.assign(n ? n : 1, 0); b->max_ent.assign(n ? n : 1, 0); b->row0.assign(n + 1, 0);
+	/* the state may come from a socket (nabwa_worker_process): rows and positions index the SA and the reference on the GPU in pass 2, so
+	 * what cannot come from this index stops here.  Rows run 0 .. seq_len, positions 0 .. l_pac; the two BWTs are of one text and its reverse */
+	const uint32_t max_row = b->ix->bwt[0].seq_len < b->ix->bwt[1].seq_len ? b->ix->bwt[0].seq_len : b->ix->bwt[1].seq_len;
+	const int64_t l_pac = b->ix->ref ? b->ix->ref->l_pac : (int64_t)max_row;
+	/* (a hit with insertions at the very start of the text is positioned at rlen - (sa + len) < 0, kept as the u32 it wraps to and read
+	 * back as negative, bwase.c:197: the last `len` values of the u32 range are positions of the library's own making) */
+	auto pos_inside = [&](uint32_t pos, int32_t len) { return (int64_t)pos <= l_pac || (len > 0 && pos >= 0u - (uint32_t)len); };
 	for (int i = 0; i < n; ++i) {
 		const nabwa_wire_read_t &w = in[i];
 		if (w.n_aln < 0 || w.n_multi < 0 || w.n_multi > NABWA_MAX_MULTI || (w.n_aln && !w.aln) || (w.n_multi && !w.multi)) { char m[96]; snprintf(m, sizeof m, "record %d: counts out of range", i); return nabwa_fail(NABWA_EINVAL, "%s", m); }
 		if ((int64_t)w.len != b->off[i + 1] - b->off[i]) { char m[160]; snprintf(m, sizeof m, "record %d: positioned with a length of %d, the batch has %lld (other trimming options?)", i, w.len, (long long)(b->off[i + 1] - b->off[i])); return nabwa_fail(NABWA_EINVAL, "%s", m); }
+		bool inside = w.sa <= max_row && pos_inside(w.pos, w.len);
+		for (int j = 0; j < w.n_aln && inside; ++j) {
+			uint32_t kl[2]; memcpy(kl, w.aln + 16 * (size_t)j + 4, 8);
+			inside = kl[0] <= kl[1] && kl[1] <= max_row;
+		}
+		for (int j = 0; j < w.n_multi && inside; ++j) { uint32_t pos; memcpy(&pos, w.multi + 16 * (size_t)j, 4); inside = pos_inside(pos, w.len); }
+		if (!inside) { char m[96]; snprintf(m, sizeof m, "record %d: hit row outside the index", i); return nabwa_fail(NABWA_EINVAL, "%s", m); }
 		b->n_aln[i] = w.n_aln; b->max_ent[i] = w.max_entries; b->row0[i + 1] = b->row0[i] + w.n_aln;
 	}
 	if (!b->rows.resize(b->row0[n] ? (size_t)b->row0[n] : 1)) return nabwa_fail(NABWA_ENOMEM, "out of memory for the hit rows");

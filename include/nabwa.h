@@ -559,6 +559,23 @@ int nabwa_pe_finish_sampe_cs(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, cons
 int nabwa_pairing_typed(nabwa_pe_end_t p[2], int n_hits, uint64_t *hits, const nabwa_aln1_t *rows0, const nabwa_aln1_t *rows1,
 						int max_isize, int s_mm, const nabwa_isize_t *ii, int type);
 
+/* ---- BGZF on the GPU (bgzf_deflate.hip, nabwa_bgzf.hip): bytes in, BGZF blocks out.  Every block is a gzip member with the BC extra
+ * field, its payload a valid RFC 1951 stream (fixed Huffman codes, or one stored block where that is shorter), CRC-32 and ISIZE made on
+ * the device.  Only the INFLATED bytes are contract: the compressed bytes differ from zlib's and may change between versions.
+ * nabwa_bgzf_bound            upper bound of the output for n input bytes (blocks of <= 0xff00 bytes, each <= 0x10000)
+ * nabwa_bgzf_compress         n bytes -> ceil(n / 0xff00) BGZF blocks, back to back, WITHOUT the end-of-file block; n = 0 -> no block.
+ *                             NABWA_ECAP with *n_out = needed if cap is too small, NABWA_ENODEV without a device.  No block is larger
+ *                             than its slice + 31 bytes.
+ * nabwa_bgzf_create / _handle_compress / _destroy: the same with a handle that keeps its stream, its device buffers and its pinned
+ *                             staging buffers between calls (they grow to 1024 slices at most; longer inputs go through in chunks).
+ *                             One call at a time per handle. */
+typedef struct nabwa_bgzf nabwa_bgzf_t;
+int64_t nabwa_bgzf_bound(int64_t n);
+int nabwa_bgzf_compress(int device, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
+int nabwa_bgzf_create(int device, nabwa_bgzf_t **out);
+int nabwa_bgzf_handle_compress(nabwa_bgzf_t *z, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
+void nabwa_bgzf_destroy(nabwa_bgzf_t *z);
+
 #ifdef __cplusplus
 }
 #endif

@@ -337,6 +337,13 @@ def lib():
     L.nabwa_se_finish_cs.argtypes = [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]
     L.nabwa_pe_finish_sampe_cs.argtypes = [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]
     L.nabwa_pairing_typed.argtypes = [_P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int]
+    L.nabwa_bgzf_bound.restype = C.c_int64
+    L.nabwa_bgzf_bound.argtypes = [C.c_int64]
+    L.nabwa_bgzf_compress.argtypes = [C.c_int, _P, C.c_int64, _P, C.c_int64, _P, _P]
+    L.nabwa_bgzf_create.argtypes = [C.c_int, _P]
+    L.nabwa_bgzf_handle_compress.argtypes = [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]
+    L.nabwa_bgzf_destroy.argtypes = [_P]
+    L.nabwa_bgzf_destroy.restype = None
     _lib = L
     return L
 
@@ -426,6 +433,59 @@ def index_build_estimate(l_pac):
     out = C.c_uint64()
     _chk(lib().nabwa_index_build_estimate(int(l_pac), C.byref(out)))
     return out.value
+
+
+def bgzf_bound(n):
+    """upper bound of bgzf_compress's output for n input bytes (nabwa_bgzf_bound)"""
+    return int(lib().nabwa_bgzf_bound(int(n)))
+
+
+def _bgzf_call(f, first, data, cap):
+    a = np.frombuffer(bytes(data), np.uint8)
+    cap = bgzf_bound(a.size) if cap is None else int(cap)
+    out = np.empty(max(cap, 1), np.uint8)
+    n_out, n_blocks = C.c_int64(), C.c_int64()
+    rc = f(first, _ptr(a), a.size, _ptr(out), cap, C.byref(n_out), C.byref(n_blocks))
+    if rc != OK:
+        e = NabwaError(rc, lib().nabwa_last_error().decode())
+        e.needed = n_out.value
+        raise e
+    return out[:n_out.value].tobytes()
+
+
+def bgzf_compress(data, device=0, cap=None):
+    """data -> its BGZF blocks (slices of <= 0xff00 bytes, one block each, no end-of-file block), compressed on the GPU
+    (nabwa_bgzf_compress).  Only the inflated bytes are contract.  cap: the output capacity handed to the library (default: the
+    bound); a NabwaError of code ECAP carries the size that would do in .needed"""
+    return _bgzf_call(lib().nabwa_bgzf_compress, int(device), data, cap)
+
+
+class Bgzf:
+    """the compressor as a handle that keeps its stream and buffers between calls (nabwa_bgzf_create)"""
+
+    def __init__(self, device=0):
+        self._h = _P()
+        _chk(lib().nabwa_bgzf_create(int(device), C.byref(self._h)))
+
+    def compress(self, data, cap=None):
+        return _bgzf_call(lib().nabwa_bgzf_handle_compress, self._h, data, cap)
+
+    def close(self):
+        if self._h:
+            lib().nabwa_bgzf_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Index:

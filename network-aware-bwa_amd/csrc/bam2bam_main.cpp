@@ -53,12 +53,24 @@ static void bgzf_block(const uint8_t *in, size_t n, int level, std::vector<uint8
 
 struct BgzfOut {
 	FILE *f; std::vector<uint8_t> pend; int level;
+	nabwa_bgzf_t *gpu;                                 /* NABWA_BGZF=gpu: the blocks are made by the library's compressor; null: zlib on host threads */
+	std::vector<uint8_t> packed;
 	void write(const void *p, size_t n) { const uint8_t *b = (const uint8_t*)p; pend.insert(pend.end(), b, b + n); if (pend.size() >= (64u << 20)) flush(false); }
 	void flush(bool all)
 	{
 		const size_t BS = 0xff00;
 		const size_t n_full = pend.size() / BS, n_blocks = all ? (pend.size() + BS - 1) / BS : n_full;
 		if (!n_blocks) return;
+		if (gpu) {
+			const size_t take = n_blocks * BS < pend.size() ? n_blocks * BS : pend.size();
+			const size_t bound = (size_t)nabwa_bgzf_bound((int64_t)take);
+			if (packed.size() < bound) packed.resize(bound);
+			int64_t n_out = 0, nb = 0;
+			if (nabwa_bgzf_handle_compress(gpu, pend.data(), (int64_t)take, packed.data(), (int64_t)packed.size(), &n_out, &nb) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] BGZF on the GPU: %s\n", nabwa_last_error()); fflush(stderr); _exit(2); }
+			if (fwrite(packed.data(), 1, (size_t)n_out, f) != (size_t)n_out) die("output", "write failed");
+			pend.erase(pend.begin(), pend.begin() + take);
+			return;
+		}
 		int nt = (int)std::thread::hardware_concurrency(); if (nt < 1) nt = 1; if (nt > 16) nt = 16;
 		if ((size_t)nt > n_blocks) nt = (int)n_blocks;
 		std::vector<std::vector<uint8_t>> parts(nt);
@@ -242,11 +254,18 @@ int main(int argc, char **argv)
 		fprintf(stderr, "\nUsage:   nabwa_bam2bam -g PREFIX [options of bwa bam2bam] [-f out.bam] <in.bam>\n\n");
 		return 1;
 	}
+	/* NABWA_BGZF: who deflates the output -- host (default: zlib level 2 on host threads) or gpu (the library's compressor on the first
+	 * GPU; other compressed bytes, the same inflated ones) */
+	const char *bgzf_env = getenv("NABWA_BGZF");
+	const bool bgzf_gpu = bgzf_env && !strcmp(bgzf_env, "gpu");
+	if (bgzf_env && !bgzf_gpu && strcmp(bgzf_env, "host")) { fprintf(stderr, "[nabwa_bam2bam] NABWA_BGZF=%s: host or gpu\n", bgzf_env); return 1; }
 	/* one index replica per GPU of NABWA_DEVICES ("0,1,2,3"; default: NABWA_DEVICE or 0); batches are dealt to them in turn */
 	std::vector<int> devices;
 	if (getenv("NABWA_DEVICES"))
 		for (const char *q = getenv("NABWA_DEVICES"); *q; ) { char *e; const long d = strtol(q, &e, 10); if (e == q) break; devices.push_back((int)d); q = *e == ',' ? e + 1 : e; }
 	if (devices.empty()) devices.push_back(getenv("NABWA_DEVICE") ? atoi(getenv("NABWA_DEVICE")) : 0);
+	nabwa_bgzf_t *bgzf = 0;
+	if (bgzf_gpu && nabwa_bgzf_create(devices[0], &bgzf) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] BGZF on the GPU: %s\n", nabwa_last_error()); return 2; }
 	std::vector<nabwa_index_t*> ixs(devices.size(), (nabwa_index_t*)0);
 	{
 		std::vector<std::string> err(devices.size());
@@ -276,7 +295,7 @@ int main(int argc, char **argv)
 
 	FILE *of = ofile ? fopen(ofile, "wb") : stdout;
 	if (!of) die(ofile, "cannot create");
-	BgzfOut out{ of, {}, 2 };
+	BgzfOut out{ of, {}, 2, bgzf, {} };
 	{
 		const std::string text = header_text(ix, old, argc, argv);
 		const int32_t hl = (int32_t)text.size(), ns = nabwa_index_n_contigs(ix);
@@ -464,12 +483,14 @@ int main(int argc, char **argv)
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: start-up (device, index, headers) %.3f s, records %.3f s\n", t_loop - t_main, now_s() - t_loop);
 	if (timing) { double ts = 0; for (double x : t_search) ts += x; fprintf(stderr, "[nabwa_bam2bam] timing: search threads (%zu GPU%s) %.3f s busy\n", n_dev, n_dev > 1 ? "s" : "", ts); }
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: library calls: create %.3f s, pass 1 %.3f s, pass 2 %.3f s, output %.3f s, destroy %.3f s\n", t_call[0], t_call[1], t_call[2], t_call[3], t_call[4]);
-	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: reader thread %.3f s busy (%.3f s of it inflate, %s), passes 1 and 2 on this thread %.3f s (+ %.3f s waiting for input; the output thread waited %.3f s for the writer), writer thread %.3f s busy (deflate + write)\n",
-						t_read, in.t_inflate, in.bgzf ? "BGZF blocks in parallel" : in.raw ? "not compressed" : "one gzip stream", t_lib, t_wait_in, t_wait_out, t_write);
+	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: reader thread %.3f s busy (%.3f s of it inflate, %s), passes 1 and 2 on this thread %.3f s (+ %.3f s waiting for input; the output thread waited %.3f s for the writer), writer thread %.3f s busy (deflate + write; %s)\n",
+						t_read, in.t_inflate, in.bgzf ? "BGZF blocks in parallel" : in.raw ? "not compressed" : "one gzip stream", t_lib, t_wait_in, t_wait_out, t_write,
+						bgzf_gpu ? "BGZF on the GPU" : "zlib level 2 on host threads");
 	fprintf(stderr, "[nabwa_bam2bam] %ld sequences processed\n[nabwa_bam2bam] finished cleanly, shutting down.\n"
 			"[bwa_paired_sw] %lld out of %lld Q%d singletons are mated.\n[bwa_paired_sw] %lld out of %lld Q%d discordant pairs are fixed.\n",
 			tot_seqs, (long long)n_mapped[1], (long long)n_tot[1], 17, (long long)n_mapped[0], (long long)n_tot[0], 17);
 	out.close();
+	if (bgzf) nabwa_bgzf_destroy(bgzf);
 	nabwa_isize_table_destroy(tab);
 	for (nabwa_index_t *p : ixs) nabwa_index_destroy(p);
 	/* final_rename (utils.c:159-173): every trailing '_' goes ("out.bam__" becomes "out.bam") once the file is complete -- unless nothing

@@ -1,4 +1,4 @@
-// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip and fm_deep.hip, declared once.
+// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, fm_deep.hip and bgzf_deflate.hip, declared once.
 // The defining files and every host unit that calls one include this header, so a parameter list that differs between the two sides
 // is a compile error (C linkage carries no types).  Host side only: the kernel headers (nabwa_dev.hpp, fm_search.hpp, fm_deep.hpp,
 // fm_deep_body.hpp) do not include it -- the CPU emulation of the tests compiles those without HIP.
@@ -43,4 +43,7 @@ void nabwa_launch_pad_reads(int n, const uint8_t *seq, const uint8_t *rseq, cons
 /* fm_deep.hip */
 void nabwa_launch_fm_deep(const DeepParams *P, int n_waves, hipStream_t s);
 int nabwa_deep_occupancy(int ns, int lds_rd);
+/* bgzf_deflate.hip: slice k of in[0, n) -> one BGZF block at stage + k * 0x10000, its size in sizes[k]; then the blocks back to back */
+void nabwa_launch_bgzf_deflate(const uint8_t *in, int64_t n, int n_slices, uint8_t *stage, uint32_t *sizes, hipStream_t s);
+void nabwa_launch_bgzf_pack(const uint8_t *stage, const uint32_t *sizes, int n_slices, uint8_t *packed, int64_t *total, hipStream_t s);
 }

@@ -16,31 +16,13 @@
 // resuming into an existing -f file (attempt_recovery, bwtaln.c:259-296) continues the record stream; the reference
 // writes a second copy of the 64-byte header at the resume point (bwtaln.c:387 is unconditional), which makes the
 // resumed file unreadable.  A resumed file here equals the file of an uninterrupted run.
-#include <ctype.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-#include <zlib.h>
-#include <algorithm>
-#include <condition_variable>
+#include <atomic>
 #include <functional>
-#include <chrono>
-#include <deque>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
-#include "../../include/nabwa.h"
+/* a damaged BGZF block ends the run with status 2, a read that cannot be taken with status 1 */
+#define TOOL "nabwa_aln"
+#define TOOL_DIE_STATUS 2
+#include "read_input.hpp"
 
-#define MODE_BAM_ANY   (0x20 | 0x40 | 0x80 | 0x100)   /* BWA_MODE_BAM*, bwtaln.h:137-140 */
 #define MODE_CFY       0x08
 #define MODE_IL13      0x200
 #define MAX_BCLEN      63                              /* bwtaln.h:30 */
@@ -50,14 +32,9 @@ struct Batch {                      /* what one GPU call (or a few) consumes */
 	std::vector<int64_t> off{0};
 	std::vector<uint8_t> seq, rseq;
 	std::vector<int> chunk_max_len;  /* longest read of each REF_CHUNK-sized piece */
+	long no = 0;                     /* which batch of the run this is: its records leave in that order */
 	int n() const { return (int)off.size() - 1; }
 };
-
-/* a damaged BGZF block ends the run (the reader inflates blocks on several threads: no exit handlers under them) */
-static void die(const char *what, const char *why) { fprintf(stderr, "[nabwa_aln] %s: %s\n", what, why); fflush(stderr); _exit(2); }
-static void bad_read(const std::string &msg) { fprintf(stderr, "[nabwa_aln] %s\n", msg.c_str()); exit(1); }
-#define READ_INPUT_TOOL "nabwa_aln"
-#include "read_input.hpp"
 
 /* one record of the shared reader appended to a batch: seq = the read reversed, rseq = its reverse complement (its complement
  * alone for colour space), len bases; '-' (code 5) is searched as N */
@@ -153,8 +130,6 @@ static size_t guess_record_start(const unsigned char *d, size_t from, size_t end
  * stopped exactly where j began -- then j's parse is what the single sequential parse would have produced from there.  At
  * the first piece that does not line up, the rest of the window is dropped and the next window starts where the last
  * good parser stopped, which is a record boundary of the sequential parse by construction. */
-static double dbg_now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
-
 static void read_everything(Source &src, Assembler &as)
 {
 	int n_thr = getenv("NABWA_ALN_THREADS") ? atoi(getenv("NABWA_ALN_THREADS")) : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
@@ -177,7 +152,7 @@ static void read_everything(Source &src, Assembler &as)
 	struct Piece { Source s; Batch b; size_t stop_at = 0; bool ended = false; };
 	std::vector<Piece> piece;
 	while (pos < size && !input_ended) {
-		const double t_start = dbg_now();
+		const double t_start = now_s();
 		const size_t wend = pos + window < size ? pos + window : size;
 		std::vector<size_t> cut{pos};
 		for (int k = 1; k < n_thr; ++k) {
@@ -202,7 +177,7 @@ static void read_everything(Source &src, Assembler &as)
 			if (m == 1) work(); else th.emplace_back(work);
 		}
 		for (auto &x : th) x.join();
-		const double t_parsed = dbg_now();
+		const double t_parsed = now_s();
 		size_t good_to = pos;
 		for (int j = 0; j < m; ++j) {
 			Piece &q = piece[j];
@@ -218,7 +193,7 @@ static void read_everything(Source &src, Assembler &as)
 			if (q.ended) { input_ended = true; break; }            /* end of the input, or a truncated quality string: reading stops for good */
 			if (q.stop_at != cut[j + 1]) break;                   /* the next piece did not start on a record of this parse */
 		}
-		if (getenv("NABWA_ALN_DEBUG")) fprintf(stderr, "[nabwa_aln] window at %zu: %d pieces, accepted up to %zu of %zu; parse %.3f s, assemble %.3f s\n", pos, m, good_to, cut[m], t_parsed - t_start, dbg_now() - t_parsed);
+		if (getenv("NABWA_ALN_DEBUG")) fprintf(stderr, "[nabwa_aln] window at %zu: %d pieces, accepted up to %zu of %zu; parse %.3f s, assemble %.3f s\n", pos, m, good_to, cut[m], t_parsed - t_start, now_s() - t_parsed);
 		pos = good_to;
 	}
 	as.flush();
@@ -288,19 +263,48 @@ static const Opt OPTS[] = {
 	{ '2', nullptr, 0x100, 0, nullptr, "with -b: second reads of pairs only" },
 };
 
-/* bwa_open_reads (bwtaln.c:164-176): BAM with the read selection of -0 -1 -2 (none given: all), or FASTA/FASTQ */
-static bool open_source(Source &src, BamReader &bam, const nabwa_gap_opt_t &opt, const char *fn)
+/* a batch through one GPU: runs of chunks with the same max_gapo clamp -> one call each; the record stream (n_aln, then the
+ * rows; bwtaln.c:242-246) of the whole batch into obuf */
+static bool search_batch(nabwa_index_t *ix, const nabwa_gap_opt_t &opt, const Batch &b, std::vector<char> &obuf)
 {
-	src.mode = opt.mode; src.trim_qual = opt.trim_qual;
-	if (opt.mode & 0x20) {
-		int which = ((opt.mode & 0x40) ? 4 : 0) | ((opt.mode & 0x80) ? 1 : 0) | ((opt.mode & 0x100) ? 2 : 0);
-		bam.which = which ? which : 7;
-		if (!bam.open(fn)) return false;
-		src.bam = &bam;
-		return true;
+	std::vector<int32_t> n_aln, max_entries;
+	std::vector<nabwa_aln1_t> rows;
+	obuf.clear();
+	const int n_chunks = (int)b.chunk_max_len.size();
+	auto clamp_of = [&](int ch) {
+		const int md = opt.fnr > 0.0f ? nabwa_cal_maxdiff(b.chunk_max_len[ch], 0.02, opt.fnr) : opt.max_diff;
+		return md < opt.max_gapo ? md : opt.max_gapo;
+	};
+	for (int c0 = 0; c0 < n_chunks; ) {
+		int c1 = c0 + 1;
+		while (c1 < n_chunks && clamp_of(c1) == clamp_of(c0)) ++c1;
+		const int r0 = c0 * REF_CHUNK, r1 = c1 * REF_CHUNK < b.n() ? c1 * REF_CHUNK : b.n(), n = r1 - r0;
+		std::vector<int64_t> off(n + 1);
+		const int64_t base = b.off[r0];
+		for (int i = 0; i <= n; ++i) off[i] = b.off[r0 + i] - base;
+		n_aln.resize(n); max_entries.resize(n);
+		int64_t cap = (int64_t)n + n / 4 + 1024, n_rows = 0;
+		int rc = NABWA_OK;
+		for (int attempt = 0; attempt < 2; ++attempt) {      /* the second attempt has the row count the first one reported */
+			rows.resize(cap);
+			rc = nabwa_cal_sa_reg_gap(ix, &opt, n, off.data(), b.seq.data() + base, b.rseq.data() + base, 0,
+									  n_aln.data(), rows.data(), cap, &n_rows, max_entries.data());
+			if (rc != NABWA_ECAP || n_rows <= cap) break;
+			cap = n_rows;
+		}
+		if (rc != NABWA_OK) { fprintf(stderr, "[nabwa_aln] GPU search failed: %s\n", nabwa_last_error()); return false; }
+		const size_t at = obuf.size();
+		obuf.resize(at + (size_t)n * 4 + (size_t)n_rows * sizeof(nabwa_aln1_t));
+		char *w = obuf.data() + at; const nabwa_aln1_t *r = rows.data();
+		for (int i = 0; i < n; ++i) {
+			memcpy(w, &n_aln[i], 4); w += 4;
+			memcpy(w, r, (size_t)n_aln[i] * sizeof(nabwa_aln1_t)); w += (size_t)n_aln[i] * sizeof(nabwa_aln1_t); r += n_aln[i];
+		}
+		c0 = c1;
 	}
-	return src.fx.open(fn);
+	return true;
 }
+struct Done { std::vector<char> bytes; int n_reads = 0; };      /* the records of one batch, on their way to the writer */
 
 static int usage(const nabwa_gap_opt_t *o)
 {
@@ -356,13 +360,15 @@ int main(int argc, char *argv[])
 		}
 	const char *prefix = argv[optind], *reads = argv[optind + 1];
 
+	// ---- the reads: nothing is written before they can be opened
+	Source src; BamReader bam;
+	if (!src.open(reads, opt.mode, opt.trim_qual, bam)) { fprintf(stderr, "[nabwa_aln] fail to open file '%s'. Abort!\n", reads); return 2; }
+
 	// ---- NABWA_ALN_PARSE_ONLY: stop after the host side (no index, no GPU, no .sai) and say what the reads look like after
 	// parsing, filtering, trimming and encoding: "reads N bases M fnv H" (=2: also one line per read "len fnv").  Lets the CPU
 	// tests check this file's share of the work against an independent restatement, and times the parser.
 	if (getenv("NABWA_ALN_PARSE_ONLY")) {
 		const bool per_read = atoi(getenv("NABWA_ALN_PARSE_ONLY")) >= 2;
-		Source src; BamReader bam;
-		if (!open_source(src, bam, opt, reads)) { fprintf(stderr, "[nabwa_aln] fail to open file '%s'. Abort!\n", reads); return 2; }
 		auto fnv = [](uint64_t h, const uint8_t *p, size_t n) { for (size_t i = 0; i < n; ++i) { h ^= p[i]; h *= 1099511628211ull; } return h; };
 		uint64_t all = 1469598103934665603ull; long n_reads = 0, n_bases = 0;
 		Assembler as;
@@ -384,31 +390,15 @@ int main(int argc, char *argv[])
 		return 0;
 	}
 
-	// ---- the reads: nothing is written before they can be opened
-	Source src; BamReader bam;
-	if (!open_source(src, bam, opt, reads)) { fprintf(stderr, "[nabwa_aln] fail to open file '%s'. Abort!\n", reads); return 2; }
-
 	// ---- the index, one replica per GPU of NABWA_DEVICES ("0,1,2,3"; default: NABWA_DEVICE or 0): no GPU, no output
-	std::vector<int> devices;
-	if (getenv("NABWA_DEVICES")) {
-		for (const char *q = getenv("NABWA_DEVICES"); *q; ) { char *e; const long d = strtol(q, &e, 10); if (e == q) break; devices.push_back((int)d); q = *e == ',' ? e + 1 : e; }
-	}
-	if (devices.empty()) devices.push_back(getenv("NABWA_DEVICE") ? atoi(getenv("NABWA_DEVICE")) : 0);
+	const std::vector<int> devices = tool_devices();
 	const std::string sa_path = std::string(prefix) + ".sa", rsa_path = std::string(prefix) + ".rsa";
 	const int with_sa = access(sa_path.c_str(), R_OK) == 0 && access(rsa_path.c_str(), R_OK) == 0;   /* optional: lets the library build its text-mode companions */
-	std::vector<nabwa_index_t*> ixs(devices.size(), nullptr);
+	std::vector<nabwa_index_t*> ixs;
 	{
-		std::vector<std::string> err(devices.size());
-		std::vector<std::thread> th;
-		for (size_t g = 0; g < devices.size(); ++g)
-			th.emplace_back([&, g]() { if (nabwa_index_load(prefix, devices[g], with_sa, 0, &ixs[g]) != NABWA_OK) { err[g] = nabwa_last_error(); ixs[g] = nullptr; } });
-		for (auto &x : th) x.join();
-		for (size_t g = 0; g < devices.size(); ++g)
-			if (!ixs[g]) {
-				fprintf(stderr, "[nabwa_aln] cannot set up the index on GPU %d: %s\n", devices[g], err[g].c_str());
-				for (nabwa_index_t *p : ixs) if (p) nabwa_index_destroy(p);
-				return 2;
-			}
+		std::string err;
+		const int g = load_replicas(prefix, devices, with_sa, 0, ixs, err);
+		if (g >= 0) { fprintf(stderr, "[nabwa_aln] cannot set up the index on GPU %d: %s\n", devices[g], err.c_str()); return 2; }
 	}
 
 	FILE *out = stdout;
@@ -429,118 +419,40 @@ int main(int argc, char *argv[])
 	long batch_reads = getenv("NABWA_ALN_BATCH") ? atol(getenv("NABWA_ALN_BATCH")) : (4l << 20);
 	if (batch_reads < REF_CHUNK) batch_reads = REF_CHUNK;
 	batch_reads -= batch_reads % REF_CHUNK;                               /* batches end on the reference's chunk boundaries */
-	std::mutex mu; std::condition_variable cv;
-	std::deque<std::unique_ptr<Batch>> ready; bool done = false;
+	Chan<std::unique_ptr<Batch>> ready(2);
 	std::thread reader([&]() {
 		Assembler as;
+		long n_batches = 0;
 		as.batch_reads = batch_reads;
-		as.emit = [&](std::unique_ptr<Batch> b) {
-			std::unique_lock<std::mutex> lk(mu);
-			cv.wait(lk, [&] { return ready.size() < 2; });
-			ready.push_back(std::move(b));
-			cv.notify_all();
-		};
+		as.emit = [&](std::unique_ptr<Batch> b) { b->no = n_batches++; ready.put(std::move(b)); };
 		read_everything(src, as);
-		std::unique_lock<std::mutex> lk(mu);
-		done = true;
-		cv.notify_all();
+		ready.close();
 	});
 
-	// ---- one worker per GPU takes the batches as they come; the records leave in batch order (the .sai is positional)
-	long tot = 0; int status = 0;
-	/* a batch through one GPU: runs of chunks with the same max_gapo clamp -> one call each; the record stream (n_aln, then the
-	 * rows; bwtaln.c:242-246) of the whole batch into obuf */
-	auto search_batch = [&](nabwa_index_t *ix, const Batch &b, std::vector<char> &obuf) -> bool {
-		std::vector<int32_t> n_aln, max_entries;
-		std::vector<nabwa_aln1_t> rows;
-		obuf.clear();
-		const int n_chunks = (int)b.chunk_max_len.size();
-		auto clamp_of = [&](int ch) {
-			const int md = opt.fnr > 0.0f ? nabwa_cal_maxdiff(b.chunk_max_len[ch], 0.02, opt.fnr) : opt.max_diff;
-			return md < opt.max_gapo ? md : opt.max_gapo;
-		};
-		for (int c0 = 0; c0 < n_chunks; ) {
-			int c1 = c0 + 1;
-			while (c1 < n_chunks && clamp_of(c1) == clamp_of(c0)) ++c1;
-			const int r0 = c0 * REF_CHUNK, r1 = c1 * REF_CHUNK < b.n() ? c1 * REF_CHUNK : b.n(), n = r1 - r0;
-			std::vector<int64_t> off(n + 1);
-			const int64_t base = b.off[r0];
-			for (int i = 0; i <= n; ++i) off[i] = b.off[r0 + i] - base;
-			n_aln.resize(n); max_entries.resize(n);
-			int64_t cap = (int64_t)n + n / 4 + 1024, n_rows = 0;
-			int rc = NABWA_OK;
-			for (int attempt = 0; attempt < 2; ++attempt) {      /* the second attempt has the row count the first one reported */
-				rows.resize(cap);
-				rc = nabwa_cal_sa_reg_gap(ix, &opt, n, off.data(), b.seq.data() + base, b.rseq.data() + base, 0,
-										  n_aln.data(), rows.data(), cap, &n_rows, max_entries.data());
-				if (rc != NABWA_ECAP || n_rows <= cap) break;
-				cap = n_rows;
-			}
-			if (rc != NABWA_OK) { fprintf(stderr, "[nabwa_aln] GPU search failed: %s\n", nabwa_last_error()); return false; }
-			const size_t at = obuf.size();
-			obuf.resize(at + (size_t)n * 4 + (size_t)n_rows * sizeof(nabwa_aln1_t));
-			char *w = obuf.data() + at; const nabwa_aln1_t *r = rows.data();
-			for (int i = 0; i < n; ++i) {
-				memcpy(w, &n_aln[i], 4); w += 4;
-				memcpy(w, r, (size_t)n_aln[i] * sizeof(nabwa_aln1_t)); w += (size_t)n_aln[i] * sizeof(nabwa_aln1_t); r += n_aln[i];
-			}
-			c0 = c1;
-		}
-		return true;
-	};
-	struct Done { std::vector<char> bytes; int n_reads = 0; bool ok = false; };
-	std::mutex omu; std::condition_variable ocv;
-	std::map<long, Done> finished;            /* batch number -> its records, until the writer gets to it */
-	long next_in = 0, next_out = 0; bool failed = false;
+	// ---- one worker per GPU takes the batches as they come; the records leave in batch order (the .sai is positional), and not
+	// more than two finished batches per GPU wait for the writer.  After a failed search or write the workers drain the reader
+	// without searching.
+	InOrder<Done> finished(2 * (long)ixs.size() + 2);
+	std::atomic<size_t> working(ixs.size());
 	std::vector<std::thread> workers;
-	for (size_t g = 0; g < ixs.size(); ++g)
-		workers.emplace_back([&, g]() {
-			for (;;) {
-				std::unique_ptr<Batch> b; long no;
-				{
-					std::unique_lock<std::mutex> lk(mu);
-					cv.wait(lk, [&] { return !ready.empty() || done; });
-					if (ready.empty()) return;
-					b = std::move(ready.front()); ready.pop_front(); no = next_in++;
-					cv.notify_all();
-				}
+	for (nabwa_index_t *ix : ixs)
+		workers.emplace_back([&, ix]() {
+			std::unique_ptr<Batch> b;
+			while (ready.get(b)) {
+				if (finished.failed()) continue;
 				Done d; d.n_reads = b->n();
-				{	/* not more than two finished batches per GPU wait for the writer */
-					std::unique_lock<std::mutex> lk(omu);
-					ocv.wait(lk, [&] { return failed || no - next_out < 2 * (long)ixs.size() + 2; });
-					if (failed) continue;                                 /* drain the reader after a failure */
-				}
-				d.ok = search_batch(ixs[g], *b, d.bytes);
-				std::unique_lock<std::mutex> lk(omu);
-				if (!d.ok) failed = true;
-				finished.emplace(no, std::move(d));
-				ocv.notify_all();
+				if (!search_batch(ix, opt, *b, d.bytes)) finished.fail();
+				else finished.put(b->no, std::move(d));
 			}
+			if (--working == 0) finished.close();
 		});
-	{	/* the writer: this thread */
-		for (;;) {
-			Done d;
-			{
-				std::unique_lock<std::mutex> lk(omu);
-				bool readers_done = false;
-				ocv.wait_for(lk, std::chrono::milliseconds(50), [&] { return finished.count(next_out) != 0 || failed; });
-				if (finished.count(next_out) == 0) {
-					if (failed) { status = 2; break; }
-					lk.unlock();
-					{ std::unique_lock<std::mutex> lk2(mu); readers_done = done && ready.empty() && next_in == next_out; }
-					if (readers_done) break;
-					continue;
-				}
-				d = std::move(finished[next_out]); finished.erase(next_out); ++next_out;
-				ocv.notify_all();
-			}
-			if (!d.ok) { status = 2; break; }
-			if (fwrite(d.bytes.data(), 1, d.bytes.size(), out) != d.bytes.size()) { perror("[nabwa_aln] write"); status = 2; std::unique_lock<std::mutex> lk(omu); failed = true; ocv.notify_all(); break; }
-			tot += d.n_reads;
-			fprintf(stderr, "[nabwa_aln] %ld sequences have been processed.\n", tot);
-		}
-		{ std::unique_lock<std::mutex> lk(omu); if (status) failed = true; ocv.notify_all(); }
+	long tot = 0;
+	for (Done d; finished.get(d); ) {                                     /* the writer: this thread */
+		if (fwrite(d.bytes.data(), 1, d.bytes.size(), out) != d.bytes.size()) { perror("[nabwa_aln] write"); finished.fail(); break; }
+		tot += d.n_reads;
+		fprintf(stderr, "[nabwa_aln] %ld sequences have been processed.\n", tot);
 	}
+	int status = finished.failed() ? 2 : 0;
 	for (auto &w : workers) w.join();
 	reader.join();
 	if (src.n_tot && opt.trim_qual >= 1) fprintf(stderr, "[nabwa_aln] %.1f%% bases are trimmed.\n", 100.0 * src.n_trimmed / src.n_tot);
@@ -549,16 +461,7 @@ int main(int argc, char *argv[])
 	if (fflush(out) != 0) status = status ? status : 2;
 	if (out != stdout) fclose(out);
 	if (status) return status;
-	if (ofile) {                                                          /* final_rename (utils.c:159-173): "x.sai_" becomes "x.sai" once complete */
-		std::string nf(ofile);
-		size_t e = nf.size();
-		while (e > 0 && nf[e - 1] == '_') --e;
-		if (e > 0 && nf[e - 1] != '/' && e < nf.size()) {
-			nf.resize(e);
-			fprintf(stderr, "[nabwa_aln] finished, renaming %s to %s.\n", ofile, nf.c_str());
-			rename(ofile, nf.c_str());
-		}
-	}
+	final_rename(ofile, false);                                           /* "x.sai_" becomes "x.sai" once complete */
 	fprintf(stderr, "[nabwa_aln] finished cleanly, shutting down.\n");
 	return 0;
 }

@@ -1,17 +1,9 @@
 // bgzf_in.hpp -- the plain bytes of a BGZF file, of any other gzip stream, or of a file that is not compressed: the input side of
-// nabwa_bam2bam (what the reference reads through bamlite's gzread, bamlite.h:7-11).  Host code only; `die(what, why)` is the
-// including program's way to end the run.
+// nabwa_bam2bam (what the reference reads through bamlite's gzread, bamlite.h:7-11).  Host code only; a damaged file ends the run
+// through die() of tool_common.hpp, so the including program defines TOOL (and TOOL_DIE_STATUS) first.
 #pragma once
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-#include <sys/time.h>
 #include <zlib.h>
-#include <thread>
-#include <vector>
-
-static double now_s() { struct timeval tv; gettimeofday(&tv, 0); return tv.tv_sec + 1e-6 * tv.tv_usec; }
-static int io_threads() { int nt = (int)std::thread::hardware_concurrency(); if (nt < 1) nt = 1; if (nt > 16) nt = 16; return nt; }
+#include "tool_common.hpp"
 
 /* ---------------------------------------------------------------- BAM in: the plain bytes of a BGZF file (bgzf.c: independent
  * gzip members of <= 64 KB that carry their own size in a "BC" extra field -- inflated many at a time, one thread per run of

@@ -10,14 +10,8 @@
 //
 // Exit status: 0 done, 1 usage or bad input, 2 no usable GPU or a GPU failure.  Without a GPU nothing is written.
 // NABWA_DEVICE picks the GPU (default 0).
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <unistd.h>
-#include <chrono>
-#include <string>
-#include "../../include/nabwa.h"
+#define TOOL "nabwa_index"
+#include "tool_common.hpp"
 
 static int usage()
 {
@@ -50,20 +44,19 @@ int main(int argc, char *argv[])
 	if (optind + 1 > argc) return usage();
 	const char *fasta = argv[optind];
 	if (!prefix) prefix = fasta;
-	const int device = getenv("NABWA_DEVICE") ? atoi(getenv("NABWA_DEVICE")) : 0;
 
-	// no GPU, no output: bad input is still reported as such (the check reads the input and writes nothing)
-	const int ndev = nabwa_device_count();
-	if (device < 0 || device >= ndev) {
+	// no GPU, no output: bad input is still reported as such, and first (the check reads the input and writes nothing)
+	int device;
+	if (!tool_device(&device, nullptr)) {
 		if (nabwa_index_fa2pac(fasta, nullptr) < 0) {
 			fprintf(stderr, "[nabwa_index] %s\n", nabwa_last_error());
 			return 1;
 		}
-		fprintf(stderr, "[nabwa_index] no usable GPU (NABWA_DEVICE=%d, %d device(s) visible); nothing was written\n", device, ndev);
+		tool_device(&device, "; nothing was written");
 		return 2;
 	}
 
-	auto t0 = std::chrono::steady_clock::now();
+	double t0 = now_s();
 	fprintf(stderr, "[nabwa_index] Pack %sFASTA... ", is_color ? "nucleotide FASTA and convert it to colours (" : "");
 	const int64_t l_pac = is_color ? nabwa_index_fa2cspac(fasta, prefix) : nabwa_index_fa2pac(fasta, prefix);
 	if (l_pac < 0) {
@@ -71,14 +64,14 @@ int main(int argc, char *argv[])
 		return 1;
 	}
 	fprintf(stderr, "%s%.2f sec (%lld bases, .pac .ann .amb .rpac%s)\n", is_color ? ") " : "",
-			std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), (long long)l_pac, is_color ? " .nt.*" : "");
+			now_s() - t0, (long long)l_pac, is_color ? " .nt.*" : "");
 
-	t0 = std::chrono::steady_clock::now();
+	t0 = now_s();
 	const int rc = nabwa_index_build(prefix, device, 32, 1);
 	if (rc != NABWA_OK) {
 		fprintf(stderr, "[nabwa_index] building the FM-indexes failed: %s\n", nabwa_last_error());
 		return rc == NABWA_ENODEV || rc == NABWA_ENOMEM ? 2 : 1;
 	}
-	fprintf(stderr, "[nabwa_index] GPU build %.2f sec\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+	fprintf(stderr, "[nabwa_index] GPU build %.2f sec\n", now_s() - t0);
 	return 0;
 }

@@ -1,9 +1,7 @@
 // read_input.hpp -- the read side of bwa_read_seq / bwa_read_bam (bwaseqio.c:125-252), shared by nabwa_aln and
 // nabwa_samse / nabwa_sampe: FASTA / FASTQ records as kseq delivers them, and BAM records as bamlite reads them.
-// The including file defines READ_INPUT_TOOL (the tool name of its messages),
-//   static void die(const char *what, const char *why);        (bgzf_in.hpp stops on a damaged block through it)
-//   static void bad_read(const std::string &msg);              (a read the tools cannot take: does not return)
-// before including this header.  Source is the one place where the records bwa_read_seq keeps are decided: the reads (and the
+// The including file defines TOOL (the tool name of its messages) before including this header; a damaged BGZF block ends the run
+// through die(), a read the tools cannot take through fail(), both of tool_common.hpp.  Source is the one place where the records bwa_read_seq keeps are decided: the reads (and the
 // .sai records) of nabwa_aln and of nabwa_samse / nabwa_sampe cannot drift apart.
 #pragma once
 #include <ctype.h>
@@ -20,9 +18,6 @@
 #include <memory>
 #include <string>
 #include <vector>
-#ifndef READ_INPUT_TOOL
-#define READ_INPUT_TOOL "nabwa"
-#endif
 #include "bgzf_in.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -192,7 +187,7 @@ struct BamReader {
 		if (!file) return false;
 		fp.reset(new BamIn(file, fn));
 		char magic[4]; int32_t l_text = 0, n_ref = 0;
-		if (!get(magic, 4) || memcmp(magic, "BAM\1", 4) != 0) { fprintf(stderr, "[" READ_INPUT_TOOL "] invalid BAM binary header (this is not a BAM file).\n"); return false; }
+		if (!get(magic, 4) || memcmp(magic, "BAM\1", 4) != 0) { fprintf(stderr, "[" TOOL "] invalid BAM binary header (this is not a BAM file).\n"); return false; }
 		if (!get(&l_text, 4) || l_text < 0 || !skip((size_t)l_text) || !get(&n_ref, 4) || n_ref < 0) return false;
 		for (int32_t i = 0; i < n_ref; ++i) { int32_t l_name = 0; if (!get(&l_name, 4) || l_name < 0 || !skip((size_t)l_name + 4)) return false; }
 		return true;
@@ -217,7 +212,6 @@ struct BamReader {
 	}
 };
 
-
 #define READ_MODE_BAM   0x20                           /* BWA_MODE_* bits of gap_opt_t.mode, bwtaln.h:132-141 */
 #define READ_MODE_CFY   0x08
 #define READ_MODE_IL13  0x200
@@ -241,6 +235,17 @@ struct Source {                     /* bwa_read_seq (bwaseqio.c:172-252) and bwa
 	std::vector<uint8_t> code;
 	std::string qa;
 
+	/* bwa_open_reads (bwtaln.c:164-176): BAM (through b) with the read selection of -0 -1 -2 (none given: all), or FASTA / FASTQ */
+	bool open(const char *fn, int mode_, int trim_qual_, BamReader &b)
+	{
+		mode = mode_; trim_qual = trim_qual_;
+		if (!(mode & READ_MODE_BAM)) return fx.open(fn);
+		const int which = ((mode & 0x40) ? 4 : 0) | ((mode & 0x80) ? 1 : 0) | ((mode & 0x100) ? 2 : 0);
+		b.which = which ? which : 7;
+		if (!b.open(fn)) return false;
+		bam = &b;
+		return true;
+	}
 	/* bwa_trim_read (bwaseqio.c:110-123) on phred+33 characters q[0..full): the length that is kept */
 	static int trimmed_len(const char *q, int full, int trim_qual)
 	{
@@ -279,7 +284,7 @@ struct Source {                     /* bwa_read_seq (bwaseqio.c:172-252) and bwa
 		int len = full;
 		if (hq && trim_qual >= 1) { len = trimmed_len(q, full, trim_qual); n_trimmed += full - len; }
 		n_tot += full;
-		if (len > 65535) bad_read("read '" + fx.name + "' is longer than 65535 bases");
+		if (len > 65535) fail("read '" + fx.name + "' is longer than 65535 bases");
 		code.resize((size_t)full);
 		const unsigned char *s = (const unsigned char*)fx.seq.data() + l_bc;
 		for (int i = 0; i < full; ++i) code[i] = NT4[s[i]];
@@ -293,7 +298,7 @@ struct Source {                     /* bwa_read_seq (bwaseqio.c:172-252) and bwa
 		unsigned flag; int l; const unsigned char *s4, *q;
 		if (!bam->next(&flag, &l, &s4, &q)) return false;
 		if (!r) return true;
-		if (l > 65535) bad_read("a read is longer than 65535 bases");
+		if (l > 65535) fail("a read is longer than 65535 bases");
 		code.resize((size_t)l); qa.assign((size_t)l, 0);
 		for (int i = 0; i < l; ++i) {
 			code[i] = nt16_nt4[s4[i >> 1] >> 4 * (1 - (i & 1)) & 0xf];

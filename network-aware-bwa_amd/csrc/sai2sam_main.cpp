@@ -19,19 +19,7 @@
 // reference crashes or reads outside its arrays there:
 //   * nabwa_sampe without -s or -A: bwa_paired_sw hands bwa_paired_sw1 a null pac (bwape.c:651,692-701);
 //   * reads without qualities (FASTA input): bwa_cs2nt_core reads p->qual[...] of a null pointer (cs2nt.c:129).
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <unistd.h>
-#include <algorithm>
-#include <chrono>
 #include <future>
-#include <memory>
-#include <string>
-#include <thread>
-#include <vector>
-#include "../../include/nabwa.h"
 
 #ifndef SAI2SAM_PE
 #define SAI2SAM_PE 0
@@ -42,13 +30,8 @@
 #define TOOL "nabwa_samse"
 #endif
 
-/* a damaged BGZF block ends the run (the reader inflates blocks on several threads: no exit handlers under them) */
-static void die(const char *what, const char *why) { fprintf(stderr, "[" TOOL "] %s: %s\n", what, why); fflush(stderr); _exit(1); }
 /* bad input: exit status 1 (thrown, so that the parser thread hands it to the main thread through its future) */
-struct BadInput { std::string msg; };
-[[noreturn]] static void fail(const std::string &msg) { throw BadInput{ msg }; }
-static void bad_read(const std::string &msg) { fail(msg); }
-#define READ_INPUT_TOOL TOOL
+#define TOOL_FAIL_THROWS
 #include "read_input.hpp"
 
 #define MODE_BAM       0x20                            /* BWA_MODE_BAM*, bwtaln.h:137-140 */
@@ -62,10 +45,6 @@ static void bad_read(const std::string &msg) { fail(msg); }
 #define F_MR 32
 #define F_R1 64
 #define F_R2 128
-
-static const char *VERSION = "0.5.10-evan.6.3+nabwa";  /* as nabwa_bam2bam's @PG */
-
-static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // reads: what bwa_read_seq / bwa_read_bam put into a bwa_seq_t (bwaseqio.c:125-252)
@@ -81,18 +60,7 @@ struct Reads {
 struct Input {                      /* the reader nabwa_aln uses (read_input.hpp), keeping what the SAM text needs of each read */
 	Source src; BamReader bam;
 
-	bool open(const char *fn, int mode, int trim_qual)
-	{
-		src.mode = mode; src.trim_qual = trim_qual;
-		if (mode & MODE_BAM) {                                           /* bwa_open_reads: -b with -0 / -1 / -2 */
-			const int which = ((mode & 0x40) ? 4 : 0) | ((mode & 0x80) ? 1 : 0) | ((mode & 0x100) ? 2 : 0);
-			bam.which = which ? which : 7;
-			if (!bam.open(fn)) return false;
-			src.bam = &bam;
-			return true;
-		}
-		return src.fx.open(fn);
-	}
+	bool open(const char *fn, int mode, int trim_qual) { return src.open(fn, mode, trim_qual, bam); }
 	/* the next read that passes the filters, appended to r; false at the end of the input */
 	bool next(Reads &r)
 	{
@@ -338,19 +306,6 @@ static int set_rg(const char *s, std::string &line, std::string &id)
 	return 0;
 }
 
-static void final_rename(const char *ofile)                              /* utils.c:159-173 */
-{
-	if (!ofile) return;
-	std::string nf(ofile);
-	size_t e = nf.size();
-	while (e > 0 && nf[e - 1] == '_') --e;
-	if (e > 0 && nf[e - 1] != '/' && e < nf.size()) {
-		nf.resize(e);
-		fprintf(stderr, "[" TOOL "] finished, renaming %s to %s.\n", ofile, nf.c_str());
-		rename(ofile, nf.c_str());
-	}
-}
-
 static int usage()
 {
 #if SAI2SAM_PE
@@ -378,6 +333,137 @@ static int usage()
 	return 1;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// one run: its inputs and options, and what lives across its chunks
+static const int N_FILES = SAI2SAM_PE ? 2 : 1;
+struct Run {
+	const char *fn_rd[2] = { nullptr, nullptr };
+	Sai sai[2]; nabwa_gap_opt_t gopt[2]; Input in[2];
+	nabwa_pe_opt_t popt; int n_occ = 3;
+	bool colour = false;                                /* bwase.c:680, bwape.c:690-692 */
+	nabwa_index_t *ix = nullptr; int64_t seq_len = 0;
+	Printer pr;
+	uint64_t rng48 = 0;                                 /* srand48(bns->seed): one stream across all chunks */
+	nabwa_poscache_t *cache = nullptr;
+	nabwa_isize_t last_ii;                              /* sampe: the estimate of the last chunk that had one */
+	bool inputs_done = false;
+	double t_decode[2] = { 0, 0 };                      /* colour space: seconds of the decode stage, milliseconds of its kernels */
+	/* sampe reads file 1 with the first .sai's mode and trimming, file 2 with the second's, and prints both with the second's option block (bwape.c:687-690) */
+	const nabwa_gap_opt_t &opt() const { return gopt[N_FILES - 1]; }
+};
+
+/* ---- parse: one chunk of reads (pairs), their .sai records, the encoded reads; null at the end of the input */
+static std::unique_ptr<Chunk> read_chunk(Run &R)
+{
+	if (R.inputs_done) return nullptr;
+	const double ts = now_s();
+	std::unique_ptr<Chunk> ch(new Chunk());
+	Chunk &k = *ch;
+	while (k.n < CHUNK) {
+		if (!R.in[0].next(k.r[0])) break;
+		if (SAI2SAM_PE && !R.in[1].next(k.r[1])) fail(std::string(R.fn_rd[1]) + " has fewer reads than " + R.fn_rd[0]);
+		++k.n;
+	}
+	if (k.n < CHUNK) {
+		R.inputs_done = true;
+		if (SAI2SAM_PE && R.in[1].next(k.r[1])) fail(std::string(R.fn_rd[1]) + " has more reads than " + R.fn_rd[0]);
+	}
+	if (k.n == 0) return nullptr;
+	const bool comp = R.opt().mode & NABWA_MODE_COMPREAD;
+	for (int i = 0; i < k.n; ++i)
+		for (int f = 0; f < N_FILES; ++f) { R.sai[f].record(k.n_aln, k.aln); encode(k, k.r[f], i, comp); }
+	for (int f = 0; f < N_FILES; ++f)
+		if (R.gopt[f].trim_qual >= 1) {
+			char b[128]; snprintf(b, sizeof b, "[bwa_read_seq] %.1f%% bases are trimmed.\n", 100.0f * R.in[f].src.n_trimmed / R.in[f].src.n_tot);
+			k.log += b; R.in[f].src.n_trimmed = R.in[f].src.n_tot = 0;
+		}
+	k.t_read = now_s() - ts;
+	return ch;
+}
+
+/* a library call of the GPU chain failed: one line, exit status 2 without a usable GPU, else 1 (other threads are working: no exit handlers) */
+[[noreturn]] static void gpu_failed(int r, bool say_caps)
+{
+	fprintf(stderr, "[" TOOL "] %s%s\n", nabwa_last_error(), say_caps && r == NABWA_ECAP ? " -- a record would exceed the library's caps; nothing wrong is written" : "");
+	fflush(stderr); _exit(r == NABWA_ENODEV || r == NABWA_ENOMEM ? 2 : 1);
+}
+
+/* ---- GPU: the finishing chain of one chunk */
+static void gpu_chunk(Run &R, Chunk &k)
+{
+	const double ts = now_s();
+	const nabwa_gap_opt_t &opt = R.opt();
+	fputs(k.log.c_str(), stderr);
+	int r;
+#if SAI2SAM_PE
+	const int n = 2 * k.n;
+	k.pe.resize((size_t)n);
+	r = nabwa_pe_posn(R.ix, &opt, k.n, k.off.data(), k.full_len.data(), k.n_aln.data(), k.aln.data(), &R.rng48, k.pe.data());
+	if (r != NABWA_OK) gpu_failed(r, false);
+	std::vector<uint32_t> pos((size_t)n); std::vector<int32_t> len((size_t)n), mq((size_t)n);
+	for (int i = 0; i < n; ++i) { const nabwa_se_t &s = k.pe[i].se; pos[i] = s.pos; len[i] = s.len; mq[i] = s.type ? s.mapQ : 0; }
+	nabwa_isize_t ii; memset(&ii, 0, sizeof ii); char lg[2048];
+	nabwa_isize_infer_pairs(k.n, pos.data(), len.data(), mq.data(), R.popt.ap_prior, R.seq_len, &ii, lg, sizeof lg);
+	fputs(lg, stderr);
+	if (ii.avg < 0.0 && R.last_ii.avg > 0.0) ii = R.last_ii;
+	if (R.popt.force_isize) {
+		fprintf(stderr, "[bwa_cal_pac_pos_pe] discard insert size estimate as user's request.\n");
+		ii.low = ii.high = 0; ii.avg = ii.std = -1.0;
+	}
+	int cnt_chg = 0;
+	if (R.colour) {
+		k.nt_seq.assign(k.seq.size(), 0); k.nt_rseq.assign(k.seq.size(), 0); k.nt_qual.assign(k.seq.size(), 0);
+		r = nabwa_pe_finish_sampe_cs(R.ix, &opt, &R.popt, &ii, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.qual.data(), k.n_aln.data(), k.aln.data(),
+									 k.pe.data(), R.cache, &cnt_chg, k.nt_seq.data(), k.nt_rseq.data(), k.nt_qual.data(), R.t_decode);
+	} else
+		r = nabwa_pe_finish_sampe(R.ix, &opt, &R.popt, &ii, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.n_aln.data(), k.aln.data(), k.pe.data(),
+								  R.cache, &cnt_chg, nullptr, nullptr);
+	if (r != NABWA_OK) gpu_failed(r, true);
+	fprintf(stderr, "[bwa_sai2sam_pe_core] changing coordinates of %d alignments.\n", cnt_chg);
+	R.last_ii = ii;
+#else
+	k.se.resize((size_t)k.n);
+	if (R.colour) {
+		k.nt_seq.assign(k.seq.size(), 0); k.nt_rseq.assign(k.seq.size(), 0); k.nt_qual.assign(k.seq.size(), 0);
+		r = nabwa_se_finish_cs(R.ix, &opt, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.qual.data(), k.full_len.data(), k.n_aln.data(), k.aln.data(),
+							   R.n_occ, &R.rng48, k.se.data(), k.nt_seq.data(), k.nt_rseq.data(), k.nt_qual.data(), R.t_decode);
+	} else
+		r = nabwa_se_finish(R.ix, &opt, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.full_len.data(), k.n_aln.data(), k.aln.data(),
+							R.n_occ, &R.rng48, k.se.data());
+	if (r != NABWA_OK) gpu_failed(r, true);
+#endif
+	k.t_gpu = now_s() - ts;
+}
+
+/* ---- SAM text on host threads, in slices; written in order */
+static std::vector<std::string> format_chunk(const Run &R, Chunk &k)
+{
+	const double ts = now_s();
+	const int nt = host_threads((size_t)k.n, 4096);
+	const bool colour = R.colour;
+	std::vector<std::string> parts((size_t)nt);
+	host_parallel(nt, (size_t)k.n, [&](int t, size_t lo, size_t hi) {
+		std::string &o = parts[(size_t)t];
+		o.reserve((hi - lo) * (SAI2SAM_PE ? 700 : 350));
+		for (size_t i = lo; i < hi; ++i) {
+#if SAI2SAM_PE
+			const nabwa_pe_t &a = k.pe[2 * i], &b = k.pe[2 * i + 1];
+			const std::string bc = (k.r[0].bc[i].empty() && k.r[1].bc[i].empty()) ? std::string() : k.r[0].bc[i] + k.r[1].bc[i];   /* bwape.c:734-737 */
+			const uint8_t *ns = colour ? k.nt_seq.data() : nullptr, *nq = colour ? k.nt_qual.data() : nullptr;
+			const int64_t oa = k.off[2 * i], ob = k.off[2 * i + 1];
+			R.pr.print1(o, a.se, a.mapQ_paired, a.extra_flag & (F_PD | F_PP | F_R1 | F_R2), &b.se, k.r[0], (int)i, bc, ns ? ns + oa : ns, nq ? nq + oa : nq);
+			R.pr.print1(o, b.se, b.mapQ_paired, b.extra_flag & (F_PD | F_PP | F_R1 | F_R2), &a.se, k.r[1], (int)i, bc, ns ? ns + ob : ns, nq ? nq + ob : nq);
+#else
+			const nabwa_se_t &s = k.se[i];
+			R.pr.print1(o, s, s.mapQ, 0, nullptr, k.r[0], (int)i, k.r[0].bc[i], colour ? k.nt_seq.data() + k.off[i] : nullptr,
+						colour ? k.nt_qual.data() + k.off[i] : nullptr);
+#endif
+		}
+	});
+	k.t_fmt = now_s() - ts;
+	return parts;
+}
+
 static int run(int argc, char *argv[]);
 int main(int argc, char *argv[])
 {
@@ -388,10 +474,11 @@ int main(int argc, char *argv[])
 static int run(int argc, char *argv[])
 {
 	nt4_init();
+	Run R;
 	std::string rg_line, rg_id;
 	const char *ofile = nullptr;
-	int c, n_occ = 3;
-	nabwa_pe_opt_t popt;
+	int c;
+	nabwa_pe_opt_t &popt = R.popt;
 	nabwa_pe_opt_default(&popt);
 #if SAI2SAM_PE
 	const char *optstr = "a:o:sPn:N:c:f:Ar:";
@@ -415,36 +502,33 @@ static int run(int argc, char *argv[])
 		case 'c': popt.ap_prior = atof(optarg); break;
 		case 'A': popt.force_isize = 1; break;
 #else
-		case 'n': n_occ = atoi(optarg); break;
+		case 'n': R.n_occ = atoi(optarg); break;
 #endif
 		default: return 1;
 		}
 	}
-	const int n_files = SAI2SAM_PE ? 2 : 1;
-	if (optind + 1 + 2 * n_files > argc) return usage();
+	if (optind + 1 + 2 * N_FILES > argc) return usage();
 	const char *prefix = argv[optind];
 	const char *fn_sai[2] = { argv[optind + 1], SAI2SAM_PE ? argv[optind + 2] : nullptr };
-	const char *fn_rd[2] = { argv[optind + 1 + n_files], SAI2SAM_PE ? argv[optind + 2 + n_files] : nullptr };
+	R.fn_rd[0] = argv[optind + 1 + N_FILES]; R.fn_rd[1] = SAI2SAM_PE ? argv[optind + 2 + N_FILES] : nullptr;
 #if SAI2SAM_PE
 	if (popt.n_multi < 0 || popt.N_multi < 0 || popt.n_multi > NABWA_MAX_MULTI || popt.N_multi > NABWA_MAX_MULTI)
 		fail("-n / -N must be within 0.." + std::to_string(NABWA_MAX_MULTI) + " (the library's multi-hit cap)");
 #else
-	if (n_occ < 0 || n_occ > NABWA_MAX_MULTI - 1) fail("-n must be within 0.." + std::to_string(NABWA_MAX_MULTI - 1) + " (the library's multi-hit cap)");
+	if (R.n_occ < 0 || R.n_occ > NABWA_MAX_MULTI - 1) fail("-n must be within 0.." + std::to_string(NABWA_MAX_MULTI - 1) + " (the library's multi-hit cap)");
 #endif
 
 	// inputs first: a bad one is reported without a GPU, and before anything is written
-	Sai sai[2]; nabwa_gap_opt_t gopt[2];
-	for (int f = 0; f < n_files; ++f) {
-		if (!sai[f].open(fn_sai[f])) fail(std::string("cannot open ") + fn_sai[f]);
-		if (!sai[f].header(&gopt[f])) fail(std::string(fn_sai[f]) + " is too short for a .sai header");
+	for (int f = 0; f < N_FILES; ++f) {
+		if (!R.sai[f].open(fn_sai[f])) fail(std::string("cannot open ") + fn_sai[f]);
+		if (!R.sai[f].header(&R.gopt[f])) fail(std::string(fn_sai[f]) + " is too short for a .sai header");
 	}
-	/* sampe reads file 1 with the first .sai's mode and trimming, file 2 with the second's, and prints both with the second's option block (bwape.c:687-690) */
-	const nabwa_gap_opt_t &opt = gopt[n_files - 1];
-	const bool colour = !(opt.mode & NABWA_MODE_COMPREAD);              /* bwase.c:680, bwape.c:690-692 */
+	const nabwa_gap_opt_t &opt = R.opt();
+	const bool colour = R.colour = !(opt.mode & NABWA_MODE_COMPREAD);
 	if (colour) {
 		for (const char *ext : { ".nt.ann", ".nt.amb", ".nt.pac" }) {
 			const std::string p = std::string(prefix) + ext;
-			if (access(p.c_str(), R_OK) != 0) fail(std::string(fn_sai[n_files - 1]) + " is a colour-space .sai and " + p + " cannot be read (an index built with `nabwa_index -c` has it)");
+			if (access(p.c_str(), R_OK) != 0) fail(std::string(fn_sai[N_FILES - 1]) + " is a colour-space .sai and " + p + " cannot be read (an index built with `nabwa_index -c` has it)");
 		}
 #if SAI2SAM_PE
 		if (popt.is_sw && !popt.force_isize)
@@ -453,23 +537,18 @@ static int run(int argc, char *argv[])
 		popt.is_sw = 0;
 #endif
 	}
-	Input in[2];
-	for (int f = 0; f < n_files; ++f) {
-		if ((unsigned)gopt[f].mode >> 24 > MAX_BCLEN) fail("the maximum barcode length is 63");
-		if (!in[f].open(fn_rd[f], gopt[f].mode, gopt[f].trim_qual)) fail(std::string("cannot open ") + fn_rd[f]);
+	for (int f = 0; f < N_FILES; ++f) {
+		if ((unsigned)R.gopt[f].mode >> 24 > MAX_BCLEN) fail("the maximum barcode length is 63");
+		if (!R.in[f].open(R.fn_rd[f], R.gopt[f].mode, R.gopt[f].trim_qual)) fail(std::string("cannot open ") + R.fn_rd[f]);
 	}
 	for (const char *ext : { ".ann", ".amb", ".pac", ".bwt", ".rbwt", ".sa", ".rsa" }) {
 		const std::string p = std::string(prefix) + ext;
 		if (access(p.c_str(), R_OK) != 0) fail("cannot read " + p);
 	}
-	const int device = getenv("NABWA_DEVICE") ? atoi(getenv("NABWA_DEVICE")) : 0;
-	const int ndev = nabwa_device_count();
-	if (device < 0 || device >= ndev) {
-		fprintf(stderr, "[" TOOL "] no usable GPU (NABWA_DEVICE=%d, %d device(s) visible); nothing was written\n", device, ndev);
-		return 2;
-	}
-	double t0 = now();
-	nabwa_index_t *ix = nullptr;
+	int device;
+	if (!tool_device(&device, "; nothing was written")) return 2;
+	double t0 = now_s();
+	nabwa_index_t *&ix = R.ix;
 	int rc = nabwa_index_load(prefix, device, 1, 0, &ix);
 	if (rc == NABWA_OK) rc = nabwa_index_attach_reference(ix, prefix);
 	if (rc == NABWA_OK && colour) rc = nabwa_index_attach_nt_reference(ix, prefix);
@@ -477,8 +556,8 @@ static int run(int argc, char *argv[])
 		fprintf(stderr, "[" TOOL "] loading the index failed: %s\n", nabwa_last_error());
 		return rc == NABWA_ENODEV || rc == NABWA_ENOMEM ? 2 : 1;
 	}
-	const double t_load = now() - t0;
-	Printer pr; pr.ix = ix; pr.mode = opt.mode; pr.max_top2 = opt.max_top2; pr.rg_id = rg_id;
+	const double t_load = now_s() - t0;
+	Printer &pr = R.pr; pr.ix = ix; pr.mode = opt.mode; pr.max_top2 = opt.max_top2; pr.rg_id = rg_id;
 	int64_t l_pac = 0; uint32_t seed = 0;
 	nabwa_index_reference_info(ix, &l_pac, &seed);
 	for (int i = 0, n = nabwa_index_n_contigs(ix); i < n; ++i) {
@@ -486,7 +565,7 @@ static int run(int argc, char *argv[])
 		nabwa_index_contig(ix, i, nm, sizeof nm, &o, &l);
 		pr.names.push_back(nm); pr.offs.push_back(o); pr.lens.push_back(l);
 	}
-	const int64_t seq_len = (int64_t)nabwa_index_seq_len(ix, 0);
+	R.seq_len = (int64_t)nabwa_index_seq_len(ix, 0);
 
 	FILE *out = stdout;
 	if (ofile && !(out = fopen(ofile, "w"))) fail(std::string("cannot write ") + ofile);
@@ -499,174 +578,59 @@ static int run(int argc, char *argv[])
 		fwrite(h.data(), 1, h.size(), out);
 	}
 
-	uint64_t rng48 = (uint64_t)seed << 16 | 0x330E;                     /* srand48(bns->seed) */
-	nabwa_poscache_t *cache = SAI2SAM_PE ? nabwa_poscache_create() : nullptr;
-	nabwa_isize_t last_ii; memset(&last_ii, 0, sizeof last_ii); last_ii.avg = -1.0;
-	bool inputs_done = false;
+	R.rng48 = (uint64_t)seed << 16 | 0x330E;
+	R.cache = SAI2SAM_PE ? nabwa_poscache_create() : nullptr;
+	memset(&R.last_ii, 0, sizeof R.last_ii); R.last_ii.avg = -1.0;
 
-	/* ---- parse: one chunk of reads (pairs), their .sai records, the encoded reads */
-	auto read_chunk = [&]() -> std::unique_ptr<Chunk> {
-		if (inputs_done) return nullptr;
-		const double ts = now();
-		std::unique_ptr<Chunk> ch(new Chunk());
-		Chunk &k = *ch;
-		while (k.n < CHUNK) {
-			if (!in[0].next(k.r[0])) break;
-			if (SAI2SAM_PE && !in[1].next(k.r[1])) fail(std::string(fn_rd[1]) + " has fewer reads than " + fn_rd[0]);
-			++k.n;
-		}
-		if (k.n < CHUNK) {
-			inputs_done = true;
-			if (SAI2SAM_PE && in[1].next(k.r[1])) fail(std::string(fn_rd[1]) + " has more reads than " + fn_rd[0]);
-		}
-		if (k.n == 0) return nullptr;
-		const bool comp = opt.mode & NABWA_MODE_COMPREAD;
-		for (int i = 0; i < k.n; ++i)
-			for (int f = 0; f < n_files; ++f) { sai[f].record(k.n_aln, k.aln); encode(k, k.r[f], i, comp); }
-		for (int f = 0; f < n_files; ++f)
-			if (gopt[f].trim_qual >= 1) {
-				char b[128]; snprintf(b, sizeof b, "[bwa_read_seq] %.1f%% bases are trimmed.\n", 100.0f * in[f].src.n_trimmed / in[f].src.n_tot);
-				k.log += b; in[f].src.n_trimmed = in[f].src.n_tot = 0;
-			}
-		k.t_read = now() - ts;
-		return ch;
-	};
-
-	/* ---- GPU: the finishing chain of one chunk */
 	long long tot = 0;
-	double t_decode[2] = { 0, 0 };                                      /* colour space: seconds of the decode stage, milliseconds of its kernels */
-	auto gpu_chunk = [&](Chunk &k) {
-		const double ts = now();
-		fputs(k.log.c_str(), stderr);
-		int r;
-#if SAI2SAM_PE
-		const int n = 2 * k.n;
-		k.pe.resize((size_t)n);
-		r = nabwa_pe_posn(ix, &opt, k.n, k.off.data(), k.full_len.data(), k.n_aln.data(), k.aln.data(), &rng48, k.pe.data());
-		if (r != NABWA_OK) { fprintf(stderr, "[" TOOL "] %s\n", nabwa_last_error()); fflush(stderr); _exit(r == NABWA_ENODEV || r == NABWA_ENOMEM ? 2 : 1); }
-		std::vector<uint32_t> pos((size_t)n); std::vector<int32_t> len((size_t)n), mq((size_t)n);
-		for (int i = 0; i < n; ++i) { const nabwa_se_t &s = k.pe[i].se; pos[i] = s.pos; len[i] = s.len; mq[i] = s.type ? s.mapQ : 0; }
-		nabwa_isize_t ii; memset(&ii, 0, sizeof ii); char lg[2048];
-		nabwa_isize_infer_pairs(k.n, pos.data(), len.data(), mq.data(), popt.ap_prior, seq_len, &ii, lg, sizeof lg);
-		fputs(lg, stderr);
-		if (ii.avg < 0.0 && last_ii.avg > 0.0) ii = last_ii;
-		if (popt.force_isize) {
-			fprintf(stderr, "[bwa_cal_pac_pos_pe] discard insert size estimate as user's request.\n");
-			ii.low = ii.high = 0; ii.avg = ii.std = -1.0;
-		}
-		int cnt_chg = 0;
-		if (colour) {
-			k.nt_seq.assign(k.seq.size(), 0); k.nt_rseq.assign(k.seq.size(), 0); k.nt_qual.assign(k.seq.size(), 0);
-			r = nabwa_pe_finish_sampe_cs(ix, &opt, &popt, &ii, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.qual.data(), k.n_aln.data(), k.aln.data(),
-										 k.pe.data(), cache, &cnt_chg, k.nt_seq.data(), k.nt_rseq.data(), k.nt_qual.data(), t_decode);
-		} else
-		r = nabwa_pe_finish_sampe(ix, &opt, &popt, &ii, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.n_aln.data(), k.aln.data(), k.pe.data(),
-								  cache, &cnt_chg, nullptr, nullptr);
-		if (r != NABWA_OK) {
-			fprintf(stderr, "[" TOOL "] %s%s\n", nabwa_last_error(), r == NABWA_ECAP ? " -- a record would exceed the library's caps; nothing wrong is written" : "");
-			fflush(stderr); _exit(r == NABWA_ENODEV || r == NABWA_ENOMEM ? 2 : 1);         /* (other threads are working: no exit handlers) */
-		}
-		fprintf(stderr, "[bwa_sai2sam_pe_core] changing coordinates of %d alignments.\n", cnt_chg);
-		last_ii = ii;
-#else
-		k.se.resize((size_t)k.n);
-		if (colour) {
-			k.nt_seq.assign(k.seq.size(), 0); k.nt_rseq.assign(k.seq.size(), 0); k.nt_qual.assign(k.seq.size(), 0);
-			r = nabwa_se_finish_cs(ix, &opt, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.qual.data(), k.full_len.data(), k.n_aln.data(), k.aln.data(),
-								   n_occ, &rng48, k.se.data(), k.nt_seq.data(), k.nt_rseq.data(), k.nt_qual.data(), t_decode);
-		} else
-		r = nabwa_se_finish(ix, &opt, k.n, k.off.data(), k.seq.data(), k.rseq.data(), k.full_len.data(), k.n_aln.data(), k.aln.data(),
-							n_occ, &rng48, k.se.data());
-		if (r != NABWA_OK) {
-			fprintf(stderr, "[" TOOL "] %s%s\n", nabwa_last_error(), r == NABWA_ECAP ? " -- a record would exceed the library's caps; nothing wrong is written" : "");
-			fflush(stderr); _exit(r == NABWA_ENODEV || r == NABWA_ENOMEM ? 2 : 1);         /* (other threads are working: no exit handlers) */
-		}
-#endif
-		k.t_gpu = now() - ts;
-	};
-
-	/* ---- SAM text on host threads, in slices; written in order */
-	auto format_chunk = [&](Chunk &k) -> std::vector<std::string> {
-		const double ts = now();
-		int nt = (int)std::thread::hardware_concurrency(); nt = std::max(1, std::min(nt, 16));
-		if (getenv("NABWA_HOST_THREADS")) nt = std::max(1, atoi(getenv("NABWA_HOST_THREADS")));
-		if (k.n < 4096) nt = 1;
-		std::vector<std::string> parts((size_t)nt);
-		auto work = [&](int t) {
-			std::string &o = parts[(size_t)t];
-			const int lo = (int)((int64_t)k.n * t / nt), hi = (int)((int64_t)k.n * (t + 1) / nt);
-			o.reserve((size_t)(hi - lo) * (SAI2SAM_PE ? 700 : 350));
-			for (int i = lo; i < hi; ++i) {
-#if SAI2SAM_PE
-				const nabwa_pe_t &a = k.pe[2 * (size_t)i], &b = k.pe[2 * (size_t)i + 1];
-				const std::string bc = (k.r[0].bc[i].empty() && k.r[1].bc[i].empty()) ? std::string() : k.r[0].bc[i] + k.r[1].bc[i];   /* bwape.c:734-737 */
-				const uint8_t *ns = colour ? k.nt_seq.data() : nullptr, *nq = colour ? k.nt_qual.data() : nullptr;
-				const int64_t oa = k.off[2 * (size_t)i], ob = k.off[2 * (size_t)i + 1];
-				pr.print1(o, a.se, a.mapQ_paired, a.extra_flag & (F_PD | F_PP | F_R1 | F_R2), &b.se, k.r[0], i, bc, ns ? ns + oa : ns, nq ? nq + oa : nq);
-				pr.print1(o, b.se, b.mapQ_paired, b.extra_flag & (F_PD | F_PP | F_R1 | F_R2), &a.se, k.r[1], i, bc, ns ? ns + ob : ns, nq ? nq + ob : nq);
-#else
-				const nabwa_se_t &s = k.se[(size_t)i];
-				pr.print1(o, s, s.mapQ, 0, nullptr, k.r[0], i, k.r[0].bc[i], colour ? k.nt_seq.data() + k.off[(size_t)i] : nullptr,
-						  colour ? k.nt_qual.data() + k.off[(size_t)i] : nullptr);
-#endif
-			}
-		};
-		if (nt == 1) work(0);
-		else { std::vector<std::thread> th; for (int t = 0; t < nt; ++t) th.emplace_back(work, t); for (auto &x : th) x.join(); }
-		k.t_fmt = now() - ts;
-		return parts;
-	};
-
 	double t_read = 0, t_gpu = 0, t_fmt = 0, t_write = 0;
 	double t_wait_parse = 0, t_wait_write = 0, t_first_parse = 0;    /* the main thread's time is GPU chain + these waits */
-	const double t_run0 = now();
-	std::future<std::unique_ptr<Chunk>> next = std::async(std::launch::async, read_chunk);
+	const double t_run0 = now_s();
+	std::future<std::unique_ptr<Chunk>> next = std::async(std::launch::async, read_chunk, std::ref(R));
 	std::future<void> writing;
 	for (;;) {
 		std::unique_ptr<Chunk> k;
-		const double tw0 = now();
+		const double tw0 = now_s();
 		try { k = next.get(); }
 		catch (...) { if (writing.valid()) writing.wait(); throw; }      /* bad input in the next chunk: the chunk being written stays alive until then */
-		if (tot == 0) t_first_parse = now() - tw0; else t_wait_parse += now() - tw0;
+		if (tot == 0) t_first_parse = now_s() - tw0; else t_wait_parse += now_s() - tw0;
 		if (!k) break;
 		t_read += k->t_read;
-		next = std::async(std::launch::async, read_chunk);               /* chunk k+1 is parsed ... */
-		gpu_chunk(*k);                                                   /* ... while chunk k is on the GPU and chunk k-1 is written */
+		next = std::async(std::launch::async, read_chunk, std::ref(R));  /* chunk k+1 is parsed ... */
+		gpu_chunk(R, *k);                                                /* ... while chunk k is on the GPU and chunk k-1 is written */
 		t_gpu += k->t_gpu;
-		const double tw1 = now();
+		const double tw1 = now_s();
 		if (writing.valid()) writing.get();
-		t_wait_write += now() - tw1;
+		t_wait_write += now_s() - tw1;
 		tot += k->n;
 		fprintf(stderr, "[" TOOL "] %lld %s have been processed (GPU chain of the last chunk %.2f sec).\n", tot, SAI2SAM_PE ? "pairs" : "reads", k->t_gpu);
 		/* the writer owns the chunk from here and frees it (hundreds of MB of records) off the main thread */
 		std::shared_ptr<Chunk> kp(std::move(k));
 		writing = std::async(std::launch::async, [&, kp]() mutable {
-			std::vector<std::string> parts = format_chunk(*kp);
-			const double tw = now();
+			std::vector<std::string> parts = format_chunk(R, *kp);
+			const double tw = now_s();
 			for (const std::string &p : parts) fwrite(p.data(), 1, p.size(), out);
-			kp->t_write = now() - tw;
+			kp->t_write = now_s() - tw;
 			t_fmt += kp->t_fmt; t_write += kp->t_write;
 			parts.clear(); kp.reset();
 		});
 	}
-	const double tw2 = now();
+	const double tw2 = now_s();
 	if (writing.valid()) writing.get();
 	if (fflush(out) != 0 || (out != stdout && fclose(out) != 0)) fail("writing the output failed");
-	const double t_drain = now() - tw2;
-	const double t_run = now() - t_run0;
-	for (int f = 0; f < n_files; ++f) in[f].close();
-	if (cache) nabwa_poscache_destroy(cache);
+	const double t_drain = now_s() - tw2;
+	const double t_run = now_s() - t_run0;
+	for (int f = 0; f < N_FILES; ++f) R.in[f].close();
+	if (R.cache) nabwa_poscache_destroy(R.cache);
 	nabwa_index_destroy(ix);
-	final_rename(ofile);
+	final_rename(ofile, false);
 	fprintf(stderr, "[" TOOL "] %lld %s in %.2f sec (%.0f %s/s); index load %.2f sec; stage totals: parse %.2f sec, GPU chain %.2f sec, "
 			"SAM text %.2f sec, write %.2f sec (parse and text overlap the GPU chain)\n", tot, SAI2SAM_PE ? "pairs" : "reads", t_run,
 			t_run > 0 ? tot / t_run : 0.0, SAI2SAM_PE ? "pairs" : "reads", t_load, t_read, t_gpu, t_fmt, t_write);
 	fprintf(stderr, "[" TOOL "] main thread: first chunk parsed %.2f sec (fill), GPU chain %.2f sec, waited for the parser %.2f sec and for "
 			"the writer %.2f sec, last chunk's text and write %.2f sec (drain), other %.2f sec\n", t_first_parse, t_gpu, t_wait_parse, t_wait_write, t_drain,
 			t_run - (t_first_parse + t_gpu + t_wait_parse + t_wait_write + t_drain));
-	if (colour) {
-		const double dec_s = t_decode[0], dec_ms = t_decode[1];
-		fprintf(stderr, "[" TOOL "] colour space: decoding the mapped reads took %.3f sec of the GPU chain (records, copies and kernels; the kernels alone %.2f ms)\n", dec_s, dec_ms);
-	}
+	if (colour)
+		fprintf(stderr, "[" TOOL "] colour space: decoding the mapped reads took %.3f sec of the GPU chain (records, copies and kernels; the kernels alone %.2f ms)\n", R.t_decode[0], R.t_decode[1]);
 	return 0;
 }

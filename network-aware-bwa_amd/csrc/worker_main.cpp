@@ -22,16 +22,9 @@
 #include <errno.h>
 #include <getopt.h>
 #include <signal.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include <sys/utsname.h>
-#include <time.h>
-#include <deque>
-#include <string>
-#include <vector>
-#include "../../include/nabwa.h"
+#define TOOL "nabwa_worker"
+#include "tool_common.hpp"
 
 /* ---------------------------------------------------------------- libzmq 3.2 / 4.x, as much of its ABI as is used (zmq.h of those versions) */
 enum { ZMQ_SUB = 2, ZMQ_REQ = 3, ZMQ_DEALER = 5 };                                    /* socket types */
@@ -97,7 +90,6 @@ struct Net {
 	std::deque<size_t> from;                   /* which connection each unanswered record came over: its answer goes back the same way */
 	double deadline; End end; std::string detail;
 };
-static double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 
 /* handle_broadcast (bam2bam.c:2079-2097): 1 = go on, 0 = the termination code, -1 = it cannot be read or its estimates cannot be decoded */
 static int take_broadcast(Net *s)
@@ -179,7 +171,6 @@ static int net_send(void *ctx, const uint8_t *msg, int64_t len)
 }
 
 static void close_now(Zmq &z, void *sock) { if (!sock) return; const int linger = 0; z.setsockopt(sock, ZMQ_LINGER, &linger, sizeof linger); z.close(sock); }
-static int env_int(const char *name, int dflt, int lo) { const char *v = getenv(name); if (!v || !*v) return dflt; const long x = strtol(v, 0, 10); return x < lo ? lo : x > 0x7fffffff ? 0x7fffffff : (int)x; }
 
 static int usage(int nthreads, const char *host, int port, int minutes)
 {
@@ -253,13 +244,8 @@ int main(int argc, char **argv)
 		return fail_conf("options beyond the library's limits from", "-D 0..15, -h / -H 0..16, -M / -O / -E at least 1");
 	fprintf(stderr, "[nabwa_worker] %s: configuration from %s, index %s\n", node.c_str(), addr, prefix);
 
-	const int device = getenv("NABWA_DEVICE") ? atoi(getenv("NABWA_DEVICE")) : 0;
-	const int ndev = nabwa_device_count();
-	if (device < 0 || device >= ndev) {
-		fprintf(stderr, "[nabwa_worker] no usable GPU (NABWA_DEVICE=%d, %d device(s) visible)\n", device, ndev);
-		close_now(z, conf); end_ctx();
-		return 2;
-	}
+	int device;
+	if (!tool_device(&device, "")) { close_now(z, conf); end_ctx(); return 2; }
 	nabwa_index_t *ix = 0; nabwa_worker_t *w = 0;
 	int rc = nabwa_index_load(prefix, device, 1, 1, &ix);
 	if (rc == NABWA_OK) rc = nabwa_worker_create(ix, &go, &po, &w);

@@ -1,9 +1,7 @@
 // bgzf_in_main.cpp -- test harness for csrc/bgzf_in.hpp: the plain bytes of the file named on the command line go to standard
 // output, read in the uneven steps a BAM reader takes (4 bytes, then a record); a damaged file ends with status 3 and a message.
-#include <stdio.h>
-#include <stdlib.h>
-#include <unistd.h>
-static void die(const char *what, const char *why) { fprintf(stderr, "%s: %s\n", what, why); fflush(stderr); _exit(3); }
+#define TOOL "bgzf_in_main"
+#define TOOL_DIE_STATUS 3
 #include "../../network-aware-bwa_amd/csrc/bgzf_in.hpp"
 
 int main(int argc, char **argv)

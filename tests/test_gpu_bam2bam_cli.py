@@ -427,3 +427,35 @@ def test_temp_dir_keeps_what_waits_for_pass_2_in_a_file(tmp_path, switches):
     assert raw_a[raw_a.index(b"\n@SQ"):] == raw_b[raw_b.index(b"\n@SQ"):]      # everything after the @PG line (it holds the command line)
     if not switches:
         assert len(out_a) == len(recs)
+
+
+def test_temp_dir_pairs_then_batches_of_single_reads_keep_input_order(tmp_path):
+    """Two batches of pairs, then three batches that hold only single reads (some of them unmappable): with --temp-dir those are finished
+    when they are spilled and come back as bytes already made, behind pair batches that still need pass 2 -- everything reaches the
+    writer over one path (bam2bam_main.cpp: done_ch), so the output is the in-memory run's, byte for byte."""
+    pe = [T.read_fastq(os.path.join(T.GOLDEN, "reads_pe_%d.fq" % e)) for e in (1, 2)]
+    se = T.read_fastq(os.path.join(T.GOLDEN, "reads_se.fq"))[:192]
+    rng = np.random.default_rng(11)
+    recs = []
+    for i in range(64):
+        n, s1, q1 = pe[0][i]
+        _, s2, q2 = pe[1][i]
+        recs.append(B.make_record(n, s1, q1, 1 | 64 | 4 | 8))
+        recs.append(B.make_record(n, s2, q2, 1 | 128 | 4 | 8))
+    for i, (n, s, q) in enumerate(se):
+        if i % 7 == 3:                                # no such sequence in the toy genome
+            s = "".join("ACGT"[int(x)] for x in rng.integers(0, 4, len(s)))
+        recs.append(B.make_record(n, s, q, 4))
+    assert len(recs) == 128 + 192
+    a = tmp_path / "a"; b = tmp_path / "b"; tdir = tmp_path / "scratch"
+    for d in (a, b, tdir):
+        d.mkdir()
+    env = {"NABWA_BAM_BATCH": "64"}
+    _, _, out_a = run(a, recs, [], env=env)
+    _, _, out_b = run(b, recs, ["--temp-dir", str(tdir)], env=env)
+    assert [o["name"] for o in out_a] == [pe[0][i // 2][0] for i in range(128)] + [r[0] for r in se]
+    assert any(o["flag"] & 4 for o in out_a[128:]) and not all(o["flag"] & 4 for o in out_a[128:])
+    raw_a = gzip.decompress(open(str(a / "out.bam"), "rb").read())
+    raw_b = gzip.decompress(open(str(b / "out.bam"), "rb").read())
+    assert raw_a[raw_a.index(b"\n@SQ"):] == raw_b[raw_b.index(b"\n@SQ"):]      # everything after the @PG line (it holds the command line)
+    assert out_a == out_b

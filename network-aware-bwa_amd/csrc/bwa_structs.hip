@@ -10,6 +10,7 @@
 #include <vector>
 #include "../../include/nabwa.h"
 #include "nabwa_internal.hpp"
+#include "read_trim.hpp"
 
 static_assert(sizeof(nabwa_bwa_seq_t) == 200, "nabwa_bwa_seq_t must match bwa_seq_t (bwtaln.h:64-90)");
 static_assert(offsetof(nabwa_bwa_seq_t, n_aln) == 48 && offsetof(nabwa_bwa_seq_t, aln) == 56, "bwa_seq_t layout");
@@ -84,16 +85,7 @@ extern "C" int nabwa_encode_read(int full_len, const uint8_t *codes, const uint8
 		if (reverse && b < 4) b = 3 - b;
 		c[i] = b; q[i] = qual ? qual[j] : 0;
 	}
-	int len = full_len;
-	if (trim_qual >= 1 && qual) {
-		int s = 0, mx = 0, max_l = full_len - 1;
-		for (int l = full_len - 1; l >= 35 - 1; --l) {
-			s += trim_qual - (int)q[l];
-			if (s < 0) break;
-			if (s > mx) { mx = s; max_l = l; }
-		}
-		len = max_l + 1;
-	}
+	const int len = trim_qual >= 1 && qual ? bwa_trimmed_len(full_len, trim_qual, [&](int l) { return (int)q[l]; }) : full_len;
 	for (int i = 0; i < len; ++i) {
 		const uint8_t b = c[len - 1 - i];
 		seq_out[i] = b;

@@ -1,9 +1,13 @@
-// host_util.hpp -- the library's host plumbing: the NABWA_TIMING clock, integer switches of the environment and slices of independent records on host threads.
+// host_util.hpp -- the library's host plumbing: the last error, the NABWA_TIMING clock, integer switches of the environment and slices of independent records on host threads.
 #pragma once
 #include <stdlib.h>
 #include <chrono>
 #include <thread>
 #include <vector>
+
+/* the library's last error (nabwa_api.hip): keeps the message for nabwa_last_error and returns `code`.  Declared here for the units that
+ * are host code only; the tools, which share this header, never call it. */
+int nabwa_fail(int code, const char *fmt, const char *a = "");
 
 /* wall clock of the NABWA_TIMING lines, in seconds */
 static inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }

@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../include/nabwa.h"
 #include "fm_search.hpp"
+#include "host_util.hpp"
 
 struct nabwa_ann { int64_t offset; int32_t len, n_ambs; std::string name; };    // bntann1_t, bntseq.h:39-45
 struct nabwa_hole { int64_t offset; int32_t len; char amb; };                   // bntamb1_t, bntseq.h:47-51
@@ -32,8 +33,6 @@ struct nabwa_index {
 	uint64_t ntpac_bytes = 0;
 	struct nabwa_dev_pool *pool = nullptr;   // released working buffers of earlier batches, kept for the next one (dev_pool.hpp)
 };
-
-int nabwa_fail(int code, const char *fmt, const char *a = "");
 
 /* a failed HIP call: "<expr> failed: <hip error> (<file>:<line>)" as the last error, NABWA_ENODEV as the result */
 static inline int nabwa_hip_fail(hipError_t e, const char *expr, const char *file, int line)

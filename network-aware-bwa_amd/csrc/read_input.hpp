@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "bgzf_in.hpp"
+#include "bam_rec.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // FASTA / FASTQ records the way kseq_read delivers them (kseq.h:155-193): a record starts at the next '>' or '@';
@@ -247,16 +248,7 @@ struct Source {                     /* bwa_read_seq (bwaseqio.c:172-252) and bwa
 		return true;
 	}
 	/* bwa_trim_read (bwaseqio.c:110-123) on phred+33 characters q[0..full): the length that is kept */
-	static int trimmed_len(const char *q, int full, int trim_qual)
-	{
-		int sum = 0, best = 0, best_l = full - 1;
-		for (int l = full - 1; l >= READ_MIN_RDLEN - 1; --l) {
-			sum += trim_qual - ((int)(unsigned char)q[l] - 33);
-			if (sum < 0) break;
-			if (sum > best) { best = sum; best_l = l; }
-		}
-		return best_l + 1;
-	}
+	static int trimmed_len(const char *q, int full, int trim_qual) { return bwa_trimmed_len(full, trim_qual, [q](int l) { return (int)(unsigned char)q[l] - 33; }); }
 	/* the next record that survives the filters, into *r; r null: skip it (nothing decoded, nothing counted).  false at the end. */
 	bool next(SeqRead *r)
 	{
@@ -294,7 +286,6 @@ struct Source {                     /* bwa_read_seq (bwaseqio.c:172-252) and bwa
 	/* no barcode, no Casava filter, empty reads kept; qualities are always there (255 -> 126) */
 	bool next_bam(SeqRead *r)
 	{
-		static const uint8_t nt16_nt4[16] = { 4, 0, 1, 4, 2, 4, 4, 4, 3, 4, 4, 4, 4, 4, 4, 4 };
 		unsigned flag; int l; const unsigned char *s4, *q;
 		if (!bam->next(&flag, &l, &s4, &q)) return false;
 		if (!r) return true;

@@ -655,3 +655,41 @@ int ref_khash_str_order(int n, const char *const *keys, int *order_out)
 	kh_destroy_refwords(h);
 	return m;
 }
+
+/* The create stage of bam2bam over a whole file, every call the reference's own: bwa_bam_open, then read_bam_pair (pairing rules, QC flag,
+ * erase_unwanted_tags; bwaseqio.c:340-494) until it returns <= 0, and for every record of a logical record bam_get_rg (bamlite.c:157-201)
+ * and bam1_to_seq (bwaseqio.c:272-307).  bamlite reads through zlib, so a gzip stream of "BAM\1", an empty header and the records is
+ * input enough.  What comes back, as 32-bit integers and bytes back to back: per call its result and the kind; while the result is > 0,
+ * per record tid, pos, bin, qual, l_qname, flag, n_cigar, l_qseq, mtid, mpos, isize, data_len, the data, the length of the read group and
+ * the read group, the trimmed length, seq and rseq.  Returns the bytes needed; nothing is written beyond cap. */
+#include "bamlite.h"
+typedef struct { uint8_t *p; int64_t n, cap; } ref_sink_t;
+static void ref_put(ref_sink_t *s, const void *p, int64_t n) { if (s->n + n <= s->cap) memcpy(s->p + s->n, p, n); s->n += n; }
+static void ref_put32(ref_sink_t *s, int32_t x) { ref_put(s, &x, 4); }
+int64_t ref_read_bam_pairs(const char *fn, int allow_broken, int ignore_aligned, int is_comp, int trim_qual, uint8_t *out, int64_t cap)
+{
+	ref_sink_t s = { out, 0, cap };
+	bam_pair_t pair;
+	bwa_seqio_t *bs = bwa_bam_open(fn, 7, 0, 0, 0);
+	for (;;) {
+		int i, r = read_bam_pair(bs, &pair, allow_broken, ignore_aligned);
+		ref_put32(&s, r); ref_put32(&s, (int32_t)pair.kind);
+		if (r <= 0) break;
+		for (i = 0; i < (int)pair.kind; ++i) {
+			bam1_t *b = &pair.bam_rec[i]; const bam1_core_t *c = &b->core;
+			const char *rg = bam_get_rg(b);
+			bwa_seq_t q;
+			ref_put32(&s, c->tid); ref_put32(&s, c->pos); ref_put32(&s, c->bin); ref_put32(&s, c->qual); ref_put32(&s, c->l_qname);
+			ref_put32(&s, c->flag); ref_put32(&s, c->n_cigar); ref_put32(&s, c->l_qseq); ref_put32(&s, c->mtid); ref_put32(&s, c->mpos); ref_put32(&s, c->isize);
+			ref_put32(&s, b->data_len); ref_put(&s, b->data, b->data_len);
+			ref_put32(&s, (int32_t)strlen(rg)); ref_put(&s, rg, strlen(rg));
+			memset(&q, 0, sizeof q);
+			bam1_to_seq(b, &q, is_comp, trim_qual);
+			ref_put32(&s, q.len); ref_put(&s, q.seq, q.len); ref_put(&s, q.rseq, q.len);
+			bwa_free_read_seq1(&q);
+			free(b->data);
+		}
+	}
+	bwa_seq_close(bs);
+	return s.n;
+}

@@ -130,6 +130,10 @@ typedef struct {
 	int32_t lds_rd;                           /* kernel D: bytes of one read's data in LDS (0: the read is read from HBM) */
 } nabwa_batch_config_t;
 int nabwa_batch_config(nabwa_batch_t *b, nabwa_batch_config_t *out);
+/* tests, diagnostics: with NABWA_SURE0_STATS=1 at batch creation, what kernel S's shortcut for reads with an exact occurrence (NABWA_SURE0,
+ * DESIGN.md 4) did in the runs so far: out[0] reads whose search in kernel S began with the flag set (those it later handed to kernel D included), out[1] 1-mismatch key-form children found dead in the interval table where they were created,
+ * out[2] such children stored landed at table depth, out[3] reads its safety net handed to kernel D.  All 0 without the variable. */
+int nabwa_batch_sure0_stats(nabwa_batch_t *b, uint64_t out[4]);
 void nabwa_batch_destroy(nabwa_batch_t *b);
 
 /* ---- paired-end host pieces (config 3) --------------------------------------------------------- */

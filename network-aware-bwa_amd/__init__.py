@@ -302,6 +302,9 @@ def lib():
     L.nabwa_batch_checksum.argtypes = [_P, _P, _P]
     L.nabwa_batch_count_touches.argtypes = [_P, _P, _P]
     L.nabwa_batch_config.argtypes = [_P, _P]
+    if hasattr(L, "nabwa_batch_sure0_stats"):      # (a library of an earlier build, loaded through NABWA_LIB for an A/B run, has no such entry)
+        L.nabwa_batch_sure0_stats.restype = C.c_int
+        L.nabwa_batch_sure0_stats.argtypes = [_P, _P]
     L.nabwa_dp_form_counts.argtypes = [_P, C.c_int]
     L.nabwa_dp_form_counts.restype = None
     L.nabwa_batch_destroy.argtypes = [_P]
@@ -781,6 +784,13 @@ class Batch:
         c = BatchConfig()
         _chk(lib().nabwa_batch_config(self._h, C.byref(c)))
         return {f: (list(getattr(c, f)) if f == "cls" else getattr(c, f)) for f, _ in BatchConfig._fields_}
+
+    def sure0_stats(self):
+        """NABWA_SURE0_STATS=1: [reads that took kernel S's exact-occurrence shortcut, children resolved as dead, children stored
+        landed, reads its safety net handed to kernel D] over the runs so far (nabwa_batch_sure0_stats); all 0 without the variable"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().nabwa_batch_sure0_stats(self._h, out))
+        return [int(x) for x in out]
 
     def close(self):
         if self._h:

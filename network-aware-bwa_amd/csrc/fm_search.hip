@@ -364,7 +364,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 #define RID item                                            /* results and width records are indexed by read */
 #define REC (P.wdata + (size_t)RID * P.wstride)            /* this read's width record (kernel W) */
 #define MD_READ ((int)(mdmg & 0xffu))
-#define MG_READ ((int)(mdmg >> 8))
+#define MG_READ ((int)(mdmg >> 8 & 0x7fu))   /* (at most 15 here: option blocks beyond that go to kernel D whole) */
 	// current interval
 	uint32_t k = 0, l = 0;
 	// search globals
@@ -386,6 +386,15 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 	uint32_t rk_kf = 0, rk_row2 = 0, rk_row1 = 0, rk_tx = 0, rk_pop = 0, rk_tail = 0, rk_jump = 0, rk_gap = 0;   // COUNT only: this read's trips by kind
 	unsigned long long st_trips = 0, st_expand = 0, st_exact = 0, st_ent = 0, st_spec = 0, st_query = 0, st_two = 0, st_exit = 0, st_jump = 0, st_txe = 0, st_txt = 0;
 	bool ovf = false;
+	// A read one of whose strands occurs exactly (kernel W's class 0; DESIGN.md 4, "sure0").  Its first hit is the exact one, at score 0, after which max_diff is 1
+	// and the search ends at the first pop above s_mm (bwtgap.c:144,166-172): so, from the first trip on, an entry above s_mm is never popped, and a popped
+	// 1-mismatch child is an exact tail;
+	// the flag and what it counts share the register of the read's max_diff: mdmg bit 31 the flag (S0_ON), bit 30: store survivors landed (S0_LAND),
+	// bits 16-22 / 23-29 this read's key-form children whose level-KT entry was empty / that were stored landed (at most 3 per level, KT - 1 levels, two strands)
+#define s0f mdmg
+#define S0_ON  0x80000000u
+#define S0_LAND 0x40000000u
+#define S0_WAS 0x8000u      /* the flag was set at refill (it may be dropped on the way): the read is counted at its end */
 
 	auto head_get = [&](int score) -> uint32_t {
 		return (uint32_t)s_head[score * NABWA_SEARCH_BLOCK + threadIdx.x];
@@ -403,7 +412,9 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 	// After the first hit best_score is final (bwtgap.c:170), and the loop ends at the first pop whose score
 	// exceeds best_score + s_mm (bwtgap.c:144): such a child can never be expanded.  It is still COUNTED
 	// (n_entries feeds max_entries and the bwtgap.c:140 cut-off) but never written to the arena.
-	auto never_popped = [&](int score) -> bool { return !nonstop && n_aln > 0 && score > best_score + P.s_mm; };
+	// (Before the first hit best_score is its start value, which no entry's score exceeds: that is what bwtgap.c:144 itself relies on.  A sure0 read
+	// starts with best_score = 0, the score its first hit is known to have, so for it the rule holds from the first trip on.)
+	auto never_popped = [&](int score) -> bool { return !nonstop && score > best_score + P.s_mm; };
 	// append an entry to the in-memory list of its score (n_entries is maintained by the callers)
 	// the arena word of an entry: {k, l, i | last_diff_pos << 16, counters / state / strand (+ the list link, first pass)}
 	auto mk_entry = [&](uint32_t nk, uint32_t nl, int ni, int nldp, int nmm, int ngo, int nge, int nstate, int na) -> uint4 {
@@ -510,11 +521,19 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 					rk_kf = rk_row2 = rk_row1 = rk_tx = rk_pop = rk_tail = rk_jump = rk_gap = 0;
 					sq_tag = -1; bw_a = -1; sw_a = -1; p_score = -1; pf_slot = NIL;
 					if (text_ok) s_tw[threadIdx.x] = make_uint2(0u, 0x7fffffffu);
+					// by the class bytes of the read itself (chunks of the work order straddle the class boundary); not where the entry count could come
+					// near the bwtgap.c:140 cut-off (checked again at every expansion: one adds at most 9 entries, and 4 * len >= 9 for every read with a key)
+					if (!COUNT && P.sure0 && P.rd_cls && !nonstop && P.s_gapo > P.s_mm && MD_READ >= 1 && len > 0 && 2 + 4 * len <= P.max_entries) {
+						const uint32_t cw = *(const uint16_t*)(P.rd_cls + 2 * (size_t)rid);
+						if ((cw & 0xffu) == 0u || (cw >> 8) == 0u) {
+							s0f |= P.sure0 > 1 ? S0_ON | S0_LAND | S0_WAS : S0_ON | S0_WAS;
+						}
+					}
 					if (len > 0 && (int)P.rd_nN[rid] <= MD_READ) {      // too many N: no search (bwtgap.c:118-123)
 						// ---- start of bwt_match_gap (bwtgap.c:104-128)
 						seeded = len > P.seed_len;
 						max_diff = MD_READ;
-						best_score = (MD_READ + 1) * P.s_mm + (MG_READ + 1) * P.s_gapo + (P.max_gape + 1) * P.s_gape;
+						best_score = (s0f & S0_ON) ? 0 : (MD_READ + 1) * P.s_mm + (MG_READ + 1) * P.s_gapo + (P.max_gape + 1) * P.s_gape;
 						best_cnt = 0;
 						// roots: strand 0 is pushed first, strand 1 second -> strand 1 (pending) is expanded first
 						bump = 0; mask_lo = 0ull;
@@ -599,8 +618,10 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 				else {
 					// the pre-check needs bound[e_i-1]; an expansion then needs bound[e_i-2] as well
 					const bool tail = m == 0 && (e_state == STATE_M || gape_mode || e_ge == P.max_gape);
-					win_hi = e_i - 1;
-					const int win_lo = (tail || e_i < 2) ? e_i - 1 : e_i - 2;
+					// a 1-mismatch child stored landed (see the expansion) is checked against the bound at its own position, as when it was created there
+					const bool landed = e_state == STATE_M && e_ldp > e_i;
+					win_hi = landed ? e_ldp - 1 : e_i - 1;
+					const int win_lo = landed ? win_hi : ((tail || e_i < 2) ? e_i - 1 : e_i - 2);
 					bool go = true;
 					if (bw_a == e_a && win_lo >= bw_base && win_hi < bw_base + 16) {
 						if (m < (int)(BW_BYTE(win_hi - bw_base) & 127u)) go = false;   // bwtgap.c:156
@@ -625,7 +646,10 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 							forced = rdkey_ok && d < KT && (kf || row_known) && (int)(s_fb[threadIdx.x] >> (e_a << 3) & 0xffu) == m;
 							if (forced) kind = 4;
 							else if (kf && d >= KT) { kind = 6; mlev = d; midx = k; }     // depth KT: rows from here on
-							else { kind = 1; --e_i; kx = kf; }
+							else {
+								kind = 1; --e_i; kx = kf;
+								if ((s0f & S0_ON) && n_entries + 4 * len > P.max_entries) s0f &= ~S0_ON;
+							}
 						}
 					}
 				}
@@ -678,10 +702,25 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 		else if (tx && kind == 3) r_x = (qb ? P.bwt[1].isa : P.bwt[0].isa)[k];
 		else if (to_text) r_x = (qb ? P.bwt[1].sa_full : P.bwt[0].sa_full)[k];
 		uint2 r_km = make_uint2(1u, 0u);
-		if (kind == 4) {
-			uint32_t key = e_a ? s_key[threadIdx.x].y : s_key[threadIdx.x].x;
+		// sure0: a key-form parent that is the read's own prefix.  Each substituted child will be popped as an exact tail and jump (kind 4) to the level-KT
+		// entry of (its key ++ the read's next symbols), a key known here: fetch the three entries beside the children
+		// (in the data registers of the rank query, which such a trip leaves free: a2 = the entries of the second and third substitute, a3.x = 4 | the read's symbol)
+		uint4 a0, a1, a2, a3, b0, b1, b2, b3;
+		a0 = a1 = a2 = a3 = b0 = b1 = b2 = b3 = make_uint4(0, 0, 0, 0);
+		// (not where the bound at the children's position is above 0, or not at hand: see the expansion)
+		bool gh = kx && e_i > 0 && (s0f & S0_ON) && (e_mm | e_go | e_ge) == 0 && len - e_i < KT && !need_win && (BW_BYTE(e_i - 1 - bw_base) & 127u) == 0u;
+		if (kind == 4 || gh) {
+			uint32_t key = e_a ? s_key[threadIdx.x].y : s_key[threadIdx.x].x, key2 = 0, key3 = 0;
 			const int d = len - e_i;
-			if (l == KEYM) {          // the path so far, then the read's own next KT - d symbols
+			if (gh) {
+				if (key == 0xffffffffu) { gh = false; key = 0; }
+				else {
+					const uint32_t sh = 2u * (uint32_t)(KT - d), low = key & ((1u << sh) - 1u);
+					const uint32_t gh_c = key >> sh & 3u;
+					a3.x = 4u | gh_c;
+					key = (k * 4u + ((gh_c + 1u) & 3u)) << sh | low; key2 = (k * 4u + ((gh_c + 2u) & 3u)) << sh | low; key3 = (k * 4u + ((gh_c + 3u) & 3u)) << sh | low;
+				}
+			} else if (l == KEYM) {          // the path so far, then the read's own next KT - d symbols
 				if (d > 0) { const uint32_t sh = 2u * (uint32_t)(KT - d); key = (k << sh) | (sh ? key & ((1u << sh) - 1u) : 0u); }
 			} else if (e_mm) {     // the substituted symbol is the one k was derived with: k lies in (C(c), C(c+1)]
 				const uint32_t c1 = qb ? P.bwt[1].L2[1] : P.bwt[0].L2[1], c2 = qb ? P.bwt[1].L2[2] : P.bwt[0].L2[2], c3 = qb ? P.bwt[1].L2[3] : P.bwt[0].L2[3];
@@ -689,12 +728,13 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 				const uint32_t sh = 2u * (uint32_t)(KT - d);
 				key = (key & ~(3u << sh)) | cs << sh;
 			}
-			r_km = (qb ? P.bwt[1].kmer : P.bwt[0].kmer)[key];
+			const uint2 *const tab = qb ? P.bwt[1].kmer : P.bwt[0].kmer;
+			r_km = tab[key];
+			if (gh) { const uint2 g2 = tab[key2], g3 = tab[key3]; a2 = make_uint4(g2.x, g2.y, g3.x, g3.y); }
 		}
 		if (kind == 6) r_km = ((qb ? P.bwt[1].kmer_lo : P.bwt[0].kmer_lo) + LVO(mlev))[midx];
 		// the rank query: Occ of all four bases at rows k-1 and l of index qb (bwt.c:159-216 conventions)
-		uint4 a0, a1, a2, a3, b0, b1, b2, b3; uint32_t rk = 0, rl = 0; bool kvalid = false, two = false;
-		a0 = a1 = a2 = a3 = b0 = b1 = b2 = b3 = make_uint4(0, 0, 0, 0);
+		uint32_t rk = 0, rl = 0; bool kvalid = false, two = false;
 		if (kx) {       // key form: the four children of this level, 32 bytes of the next table level
 			const uint4 *const ch = (const uint4*)((qb ? P.bwt[1].kmer_lo : P.bwt[0].kmer_lo) + LVO(len - e_i) + (size_t)k * 4);
 			a0 = ch[0]; a1 = ch[1];
@@ -820,6 +860,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 				const int score = e_mm * P.s_mm + e_go * P.s_gapo + e_ge * P.s_gape;
 				bool do_add = true;
 				if (n_aln == 0) {
+					if ((s0f & S0_ON) && score != 0) { status = NABWA_ST_OVERFLOW; finish = true; do_add = false; s0f &= ~S0_ON; if (P.s0_stats) atomicAdd(P.s0_stats + 3, 1ull); }   // not the exact hit first: kernel D searches the read from the start
 					best_score = score;
 					const int best_diff = e_mm + e_go + (gape_mode ? e_ge : 0);
 					if (!nonstop) max_diff = best_diff + 1 > MD_READ ? MD_READ : best_diff + 1;
@@ -873,10 +914,13 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 			// ---- node expansion (bwtgap.c:201-260); e_i is already decremented
 			const uint32_t occ = tx1 ? 1u : l - k + 1u;                   // (key form: only read by deletion-state parents, which are never in key form)
 			bool match_child = false;
-			bool allow_diff = true, allow_M = true;
+			bool allow_diff = true, allow_M = true, mm_dead = false;
 			if (e_i > 0) {
 				const uint32_t B1 = BW_BYTE(e_i - 1 - bw_base), B0 = BW_BYTE(e_i - bw_base);
 				const int b1 = (int)(B1 & 127u), b0v = (int)(B0 & 127u);
+				// sure0: a 1-mismatch child is popped with m == 0, and a bound never falls back to 0 (gap_shadow sets 1): with a bound above 0 at
+				// its position it fails bwtgap.c:156 whenever it is popped -- counted, never stored (the strand that does not occur: every level)
+				mm_dead = (s0f & S0_ON) && b1 > 0;
 				if (b1 > m - 1) allow_diff = false;
 				else if (b1 == m - 1 && b0v == m - 1 && (B0 & 128u)) allow_M = false;
 				if (use_seed) {
@@ -961,7 +1005,20 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 				for (int j = 1; j <= 4; ++j) {
 					const int cc = (c + j) & 3; const bool is_mm = (j != 4 || c > 3);
 					const uint32_t nk = L2Q(cc) + CK(cc) + 1u, nl = L2Q(cc) + CL(cc);
-					if (nk <= nl) { emit(sc0 + (is_mm ? P.s_mm : 0), nk, nl, e_i, is_mm ? e_i : 0, e_mm + (is_mm ? 1 : 0), e_go, e_ge, STATE_M, 1); if (!is_mm) match_child = true; }
+					if (nk <= nl) {
+						// sure0: the substituted child of a parent that is the read's own prefix, with the level-KT entry its tail jump will find (see the loads)
+						uint32_t ek = nk, el = nl; int ei = e_i; bool dead = is_mm && mm_dead;
+						if (kx && is_mm && !dead && a3.x == (4u | (uint32_t)c)) {
+							const uint32_t gk = j == 1 ? r_km.x : (j == 2 ? a2.x : a2.z), gl = j == 1 ? r_km.y : (j == 2 ? a2.y : a2.w);
+							if (gk > gl) { dead = true; s0f += 1u << 16; }    // the jump would find nothing
+							else if (s0f & S0_LAND) {                          // stored as the jump would leave it; ldp > i marks it (its pop-time bound is the one at ldp - 1)
+								ek = gk; el = gl; ei = len - KT; s0f += 1u << 23;
+							}
+						}
+						if (dead) ++n_entries;                                // counted like a never-stored entry, never popped
+						else emit(sc0 + (is_mm ? P.s_mm : 0), ek, el, ei, is_mm ? e_i : 0, e_mm + (is_mm ? 1 : 0), e_go, e_ge, STATE_M, 1);
+						if (!is_mm) match_child = true;
+					}
 				}
 			} else if (c < 4) {
 				const uint32_t nk = L2Q(c) + CK(c) + 1u, nl = L2Q(c) + CL(c);
@@ -976,6 +1033,13 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 #undef CL
 
 		if (finish) {
+			const bool net = (s0f & S0_ON) && status == NABWA_ST_OK && n_aln == 0;       // the exact occurrence was not found: kernel D searches the read from the start
+			if (net) status = NABWA_ST_OVERFLOW;
+			if (P.s0_stats && (s0f & S0_WAS)) atomicAdd(P.s0_stats, 1ull);
+			if (P.s0_stats && (s0f >> 16 & 0x3fffu)) {
+				atomicAdd(P.s0_stats + 1, (unsigned long long)(s0f >> 16 & 0x7fu)); atomicAdd(P.s0_stats + 2, (unsigned long long)(s0f >> 23 & 0x7fu));
+			}
+			if (P.s0_stats && net) atomicAdd(P.s0_stats + 3, 1ull);
 			P.n_aln[item] = n_aln; P.max_ent[item] = (!COUNT && status == NABWA_ST_OVERFLOW) ? (int)rd_trips : max_ent; P.status[item] = (uint8_t)status;      // (a search handed on: the trips it took here -- kernel D's statistics dump reads them; its own max_ent replaces this)
 			if (COUNT && status == NABWA_ST_OK) touches += rd_touch;   // abandoned reads are counted by the wide pass
 			if (COUNT && P.touch_counter && rd_trips > 8000u) {
@@ -999,6 +1063,10 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 }
 
 #undef p_valid
+#undef S0_ON
+#undef S0_LAND
+#undef S0_WAS
+#undef s0f
 #undef BW_BYTE
 #undef SW_BYTE
 #undef SQ_BYTE

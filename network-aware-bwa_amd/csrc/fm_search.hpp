@@ -51,6 +51,9 @@ struct SearchParams {
 	const unsigned int *n_sync;               // work items from *n_sync on are class-0 reads: their waves run in lockstep (see fm_search_kernel, partition_kernel)
 	unsigned long long *touch_counter;        // non-null: also count the reference algorithm's bucket touches
 	const uint32_t *ixtab;                    // NABWA_IXTAB_WORDS words (device): per index what a lane picks by the strand of its entry -- see below
+	int sure0;                                // kernel S, with rd_cls set (NABWA_SURE0): 0 off; 1: a read one of whose strands occurs exactly stores no entry that cannot be popped and
+	                                          // resolves its 1-mismatch key-form children where they are created; 2: it also stores the surviving ones landed at depth KT
+	unsigned long long *s0_stats;             // non-null (NABWA_SURE0_STATS): [0] such reads, [1] key-form children whose level-KT entry was empty, [2] children stored landed, [3] reads handed to kernel D by the safety net
 };
 
 /* The per-index constants a lane of kernel D selects by its entry's strand, as a table the kernel copies into LDS (fm_deep_body.hpp): as

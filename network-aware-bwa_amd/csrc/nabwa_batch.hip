@@ -195,6 +195,16 @@ static int working_buffers(nabwa_batch *b, const BatchShape &s)
 	P.trip_budget_hard = (uint32_t)env_int("NABWA_TRIP_BUDGET_HARD", max_len > opt->seed_len ? 200 : (int)P.trip_budget);      /* (a batch of reads that mostly occur on neither strand: fm_search.hip) */
 	if (getenv("NABWA_TRIP_BUDGET") && !getenv("NABWA_TRIP_BUDGET_HARD")) P.trip_budget_hard = P.trip_budget;                       /* (a sweep of the one knob means the one budget) */
 	b->class_sort = env_int("NABWA_CLASS_SORT", 1);
+	/* kernel S's shortcut for a read one of whose strands occurs exactly (kernel W's class 0; fm_search.hip): 0 off, 1 nothing stored that
+	 * cannot be popped + 1-mismatch key-form children resolved where they are created, 2 also the surviving ones stored landed */
+	P.sure0 = env_int("NABWA_SURE0", 2);
+	if (P.sure0 < 0) P.sure0 = 0;
+	if (P.sure0 > 2) P.sure0 = 2;
+	if (env_int("NABWA_SURE0_STATS", 0)) {
+		HIP_CHECK(b->d_s0stats.get(ix, 32));
+		HIP_CHECK(hipMemset(b->d_s0stats, 0, 32));
+		P.s0_stats = b->d_s0stats;
+	}
 	{
 		P.w_sync = (n > 0 && s.min_len == max_len) ? env_int("NABWA_W_SYNC", 1) : 0;
 	}
@@ -283,6 +293,7 @@ extern "C" int nabwa_batch_run(nabwa_batch_t *b)
 	}
 	HIP_CHECK(hipEventRecord(b->ev0, b->stream));
 	SearchParams PS = b->P; PS.ids = b->class_sort ? b->d_perm : 0; PS.n_sync = b->class_sort ? b->d_ncls + 10 : 0;
+	PS.rd_cls = b->class_sort ? b->d_cls : 0;      /* (this launch only: the re-runs over handed-on reads search without the shortcut) */
 	if (!b->deep_only) nabwa_launch_fm_search(&PS, b->n_blocks, b->stream);
 	else {      /* option blocks the first-pass kernel's compact entries cannot hold: every read goes to kernel D */
 		HIP_CHECK(hipMemsetAsync(b->d_status, NABWA_ST_OVERFLOW, b->n, b->stream));
@@ -479,6 +490,19 @@ extern "C" int nabwa_batch_config(nabwa_batch_t *b, nabwa_batch_config_t *out)
 	}
 	out->coop_lanes = b->deep_coop;
 	out->lds_rd = b->deep_cfg ? (int32_t)b->deep_lds_rd : -1;
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_batch_sure0_stats(nabwa_batch_t *b, uint64_t out[4])
+{
+	if (!b || !out) return nabwa_fail(NABWA_EINVAL, "null argument");
+	for (int q = 0; q < 4; ++q) out[q] = 0;
+	if (!b->d_s0stats) return NABWA_OK;
+	HIP_CHECK(hipSetDevice(b->ix->device));
+	unsigned long long v[4];
+	HIP_CHECK(hipMemcpyAsync(v, b->d_s0stats, 32, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipStreamSynchronize(b->stream));
+	for (int q = 0; q < 4; ++q) out[q] = v[q];
 	return NABWA_OK;
 }
 

@@ -17,7 +17,7 @@ struct nabwa_batch {
 	float last_ms = 0.f;
 	// device inputs
 	PoolBuf<uint8_t> d_seq, d_rseq, d_md, d_mg; PoolBuf<int64_t> d_poff; PoolBuf<int32_t> d_len; PoolBuf<uint32_t> d_key, d_pack; int pack_stride = 0;
-	PoolBuf<uint8_t> d_cls; PoolBuf<int32_t> d_perm; PoolBuf<unsigned int> d_ncls; int max_len = 0;
+	PoolBuf<unsigned long long> d_s0stats; PoolBuf<uint8_t> d_cls; PoolBuf<int32_t> d_perm; PoolBuf<unsigned int> d_ncls; int max_len = 0;
 	// first pass
 	SearchParams P = {}; int class_sort = 0; uint32_t NS_wide = 0; int n_blocks = 0, n_blocks_w = 0; PoolBuf<uint8_t> d_scratch, d_wdata, d_nN; float last_ms_w = 0.f;
 	PoolBuf<int32_t> d_naln, d_maxent, d_wide_idx; PoolBuf<uint8_t> d_status; PoolBuf<uint4> d_aln;

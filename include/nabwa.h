@@ -134,6 +134,10 @@ int nabwa_batch_config(nabwa_batch_t *b, nabwa_batch_config_t *out);
  * DESIGN.md 4) did in the runs so far: out[0] reads whose search in kernel S began with the flag set (those it later handed to kernel D included), out[1] 1-mismatch key-form children found dead in the interval table where they were created,
  * out[2] such children stored landed at table depth, out[3] reads its safety net handed to kernel D.  All 0 without the variable. */
 int nabwa_batch_sure0_stats(nabwa_batch_t *b, uint64_t out[4]);
+/* the same four values, then what the leap (NABWA_SURE0=3) did: out[4] leaps taken (a text-form entry that is the read's own prefix on a strand
+ * that occurs exactly, replaced by its hit), out[5] levels leapt over, out[6] such entries that walked instead because their text position was
+ * short of the levels left (expected 0), out[7] 0. */
+int nabwa_batch_sure0_stats_ex(nabwa_batch_t *b, uint64_t out[8]);
 void nabwa_batch_destroy(nabwa_batch_t *b);
 
 /* ---- paired-end host pieces (config 3) --------------------------------------------------------- */

@@ -305,6 +305,9 @@ def lib():
     if hasattr(L, "nabwa_batch_sure0_stats"):      # (a library of an earlier build, loaded through NABWA_LIB for an A/B run, has no such entry)
         L.nabwa_batch_sure0_stats.restype = C.c_int
         L.nabwa_batch_sure0_stats.argtypes = [_P, _P]
+    if hasattr(L, "nabwa_batch_sure0_stats_ex"):
+        L.nabwa_batch_sure0_stats_ex.restype = C.c_int
+        L.nabwa_batch_sure0_stats_ex.argtypes = [_P, _P]
     L.nabwa_dp_form_counts.argtypes = [_P, C.c_int]
     L.nabwa_dp_form_counts.restype = None
     L.nabwa_batch_destroy.argtypes = [_P]
@@ -790,6 +793,13 @@ class Batch:
         landed, reads its safety net handed to kernel D] over the runs so far (nabwa_batch_sure0_stats); all 0 without the variable"""
         out = (C.c_uint64 * 4)()
         _chk(lib().nabwa_batch_sure0_stats(self._h, out))
+        return [int(x) for x in out]
+
+    def sure0_stats_ex(self):
+        """sure0_stats()'s four values, then [leaps taken, levels leapt over, proven entries that walked instead (expected 0), 0]
+        (nabwa_batch_sure0_stats_ex; NABWA_SURE0=3)"""
+        out = (C.c_uint64 * 8)()
+        _chk(lib().nabwa_batch_sure0_stats_ex(self._h, out))
         return [int(x) for x in out]
 
     def close(self):

@@ -364,7 +364,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 #define RID item                                            /* results and width records are indexed by read */
 #define REC (P.wdata + (size_t)RID * P.wstride)            /* this read's width record (kernel W) */
 #define MD_READ ((int)(mdmg & 0xffu))
-#define MG_READ ((int)(mdmg >> 8 & 0x7fu))   /* (at most 15 here: option blocks beyond that go to kernel D whole) */
+#define MG_READ ((int)(mdmg >> 8 & 0xfu))    /* (at most 15 here: option blocks beyond that go to kernel D whole) */
 	// current interval
 	uint32_t k = 0, l = 0;
 	// search globals
@@ -390,11 +390,13 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 	// and the search ends at the first pop above s_mm (bwtgap.c:144,166-172): so, from the first trip on, an entry above s_mm is never popped, and a popped
 	// 1-mismatch child is an exact tail;
 	// the flag and what it counts share the register of the read's max_diff: mdmg bit 31 the flag (S0_ON), bit 30: store survivors landed (S0_LAND),
-	// bits 16-22 / 23-29 this read's key-form children whose level-KT entry was empty / that were stored landed (at most 3 per level, KT - 1 levels, two strands)
+	// bits 16-22 / 23-29 this read's key-form children whose level-KT entry was empty / that were stored landed (at most 3 per level, KT - 1 levels, two strands),
+	// bits 12 / 13 (above max_gapo, which is at most 15 in this kernel): strand 0 / 1 itself occurs exactly -- its class byte is 0 -- and the leap is on (S0_PRV << strand)
 #define s0f mdmg
 #define S0_ON  0x80000000u
 #define S0_LAND 0x40000000u
 #define S0_WAS 0x8000u      /* the flag was set at refill (it may be dropped on the way): the read is counted at its end */
+#define S0_PRV 0x1000u
 
 	auto head_get = [&](int score) -> uint32_t {
 		return (uint32_t)s_head[score * NABWA_SEARCH_BLOCK + threadIdx.x];
@@ -527,6 +529,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 						const uint32_t cw = *(const uint16_t*)(P.rd_cls + 2 * (size_t)rid);
 						if ((cw & 0xffu) == 0u || (cw >> 8) == 0u) {
 							s0f |= P.sure0 > 1 ? S0_ON | S0_LAND | S0_WAS : S0_ON | S0_WAS;
+							if (P.sure0 > 2) s0f |= ((cw & 0xffu) == 0u ? S0_PRV : 0u) | ((cw >> 8) == 0u ? S0_PRV << 1 : 0u);
 						}
 					}
 					if (len > 0 && (int)P.rd_nN[rid] <= MD_READ) {      // too many N: no search (bwtgap.c:118-123)
@@ -646,7 +649,31 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 							forced = rdkey_ok && d < KT && (kf || row_known) && (int)(s_fb[threadIdx.x] >> (e_a << 3) & 0xffu) == m;
 							if (forced) kind = 4;
 							else if (kf && d >= KT) { kind = 6; mlev = d; midx = k; }     // depth KT: rows from here on
+							// The leap ("sure0").  A text-form entry that is the read's own prefix on a strand kernel W proved to occur: its one row
+							// IS that occurrence, so every symbol still to come matches the text, every mismatch sibling is empty, and the gap children of those
+							// levels are counted and never stored (their score is above s_mm).  The walk would end in the suffix e_i positions further left with
+							// i == 0: that entry is made here and reported in this same trip (kind 3), with the entries the walk's levels would have counted.
+							// (k < e_i cannot be for a real occurrence; such an entry walks as before.)
+							else if (l == TXM && (s0f & S0_ON) && (s0f & S0_PRV << e_a) && e_state == STATE_M && (e_mm | e_go | e_ge) == 0
+									 && n_entries + 4 * len <= P.max_entries && k >= (uint32_t)e_i) {
+								// On this strand every bound and seed bound is 0 while entries of score 0 are popped, so a level icur (e_i-1 .. 0) pushes its
+								// insertion and its deletion (bwtgap.c:216-240) iff it is clear of both read ends, an opening is left, and -- inside the
+								// seed -- max_seed_diff allows a difference (m == max_diff >= 1 here: no counted difference yet, and this is no tail)
+								const int ies = P.indel_end_skip + (loggap ? 1 : 0);
+								int hi = e_i - 1;
+								if (hi > len - ies) hi = len - ies;
+								if (seeded && P.max_seed_diff < 1 && hi > len - P.seed_len) hi = len - P.seed_len;
+								const int gl = (MG_READ > 0 && hi >= ies) ? hi - ies + 1 : 0;
+								if (P.s0_stats) { atomicAdd(P.s0_stats + 4, 1ull); atomicAdd(P.s0_stats + 5, (unsigned long long)e_i); }
+								// the chain's entry count only rises, so its peak is at the pop of the last entry: n_entries + 2 per such level + that entry
+								n_entries += 2 * gl;
+								if (max_ent < n_entries + 1) max_ent = n_entries + 1;
+								k -= (uint32_t)e_i; e_i = 0; e_ldp = 0;
+								kind = 3; need_win = false; spec = false;
+							}
 							else {
+								if (P.s0_stats && l == TXM && (s0f & S0_ON) && (s0f & S0_PRV << e_a) && e_state == STATE_M && (e_mm | e_go | e_ge) == 0
+									&& n_entries + 4 * len <= P.max_entries) atomicAdd(P.s0_stats + 6, 1ull);     // (then k < e_i)
 								kind = 1; --e_i; kx = kf;
 								if ((s0f & S0_ON) && n_entries + 4 * len > P.max_entries) s0f &= ~S0_ON;
 							}
@@ -1066,6 +1093,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 #undef S0_ON
 #undef S0_LAND
 #undef S0_WAS
+#undef S0_PRV
 #undef s0f
 #undef BW_BYTE
 #undef SW_BYTE

@@ -52,8 +52,10 @@ struct SearchParams {
 	unsigned long long *touch_counter;        // non-null: also count the reference algorithm's bucket touches
 	const uint32_t *ixtab;                    // NABWA_IXTAB_WORDS words (device): per index what a lane picks by the strand of its entry -- see below
 	int sure0;                                // kernel S, with rd_cls set (NABWA_SURE0): 0 off; 1: a read one of whose strands occurs exactly stores no entry that cannot be popped and
-	                                          // resolves its 1-mismatch key-form children where they are created; 2: it also stores the surviving ones landed at depth KT
-	unsigned long long *s0_stats;             // non-null (NABWA_SURE0_STATS): [0] such reads, [1] key-form children whose level-KT entry was empty, [2] children stored landed, [3] reads handed to kernel D by the safety net
+	                                          // resolves its 1-mismatch key-form children where they are created; 2: it also stores the surviving ones landed at depth KT;
+	                                          // 3: also the leap -- a text-form entry that is the read's own prefix on a strand whose class byte is 0 is replaced by its hit
+	unsigned long long *s0_stats;             // non-null (NABWA_SURE0_STATS): [0] such reads, [1] key-form children whose level-KT entry was empty, [2] children stored landed, [3] reads handed to kernel D by the safety net,
+	                                          // [4] leaps taken, [5] levels leapt over, [6] proven entries that walked instead (text position < levels left), [7] unused: eight words
 };
 
 /* The per-index constants a lane of kernel D selects by its entry's strand, as a table the kernel copies into LDS (fm_deep_body.hpp): as

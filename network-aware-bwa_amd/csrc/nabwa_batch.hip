@@ -196,13 +196,14 @@ static int working_buffers(nabwa_batch *b, const BatchShape &s)
 	if (getenv("NABWA_TRIP_BUDGET") && !getenv("NABWA_TRIP_BUDGET_HARD")) P.trip_budget_hard = P.trip_budget;                       /* (a sweep of the one knob means the one budget) */
 	b->class_sort = env_int("NABWA_CLASS_SORT", 1);
 	/* kernel S's shortcut for a read one of whose strands occurs exactly (kernel W's class 0; fm_search.hip): 0 off, 1 nothing stored that
-	 * cannot be popped + 1-mismatch key-form children resolved where they are created, 2 also the surviving ones stored landed */
-	P.sure0 = env_int("NABWA_SURE0", 2);
+	 * cannot be popped + 1-mismatch key-form children resolved where they are created, 2 also the surviving ones stored landed, 3 also the leap: a
+	 * text-form entry that is the read's own prefix on a strand that occurs is replaced by its hit (profiles/exact_leap_bench.txt) */
+	P.sure0 = env_int("NABWA_SURE0", 3);
 	if (P.sure0 < 0) P.sure0 = 0;
-	if (P.sure0 > 2) P.sure0 = 2;
+	if (P.sure0 > 3) P.sure0 = 3;
 	if (env_int("NABWA_SURE0_STATS", 0)) {
-		HIP_CHECK(b->d_s0stats.get(ix, 32));
-		HIP_CHECK(hipMemset(b->d_s0stats, 0, 32));
+		HIP_CHECK(b->d_s0stats.get(ix, 64));
+		HIP_CHECK(hipMemset(b->d_s0stats, 0, 64));
 		P.s0_stats = b->d_s0stats;
 	}
 	{
@@ -503,6 +504,19 @@ extern "C" int nabwa_batch_sure0_stats(nabwa_batch_t *b, uint64_t out[4])
 	HIP_CHECK(hipMemcpyAsync(v, b->d_s0stats, 32, hipMemcpyDeviceToHost, b->stream));
 	HIP_CHECK(hipStreamSynchronize(b->stream));
 	for (int q = 0; q < 4; ++q) out[q] = v[q];
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_batch_sure0_stats_ex(nabwa_batch_t *b, uint64_t out[8])
+{
+	if (!b || !out) return nabwa_fail(NABWA_EINVAL, "null argument");
+	for (int q = 0; q < 8; ++q) out[q] = 0;
+	if (!b->d_s0stats) return NABWA_OK;
+	HIP_CHECK(hipSetDevice(b->ix->device));
+	unsigned long long v[8];
+	HIP_CHECK(hipMemcpyAsync(v, b->d_s0stats, 64, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipStreamSynchronize(b->stream));
+	for (int q = 0; q < 8; ++q) out[q] = v[q];
 	return NABWA_OK;
 }
 

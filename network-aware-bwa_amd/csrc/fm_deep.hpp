@@ -40,7 +40,7 @@ struct DeepParams {
 	uint4 *pages;                    // the pool: n_pages x 256 entries x 16 B
 	uint32_t *page_prev;             // per page: the page below it in its level's stack
 	uint32_t n_pages;
-	unsigned int *page_bump;         // pages handed out so far (a wave keeps what it took and re-uses it for its next reads)
+	unsigned int *page_bump;         // pages handed out so far (a wave keeps what it took and re-uses it for its next reads); the host puts it in slot DS_PAGE_BUMP of the statistics block
 	uint32_t *own;                   // per wave 2 x own_cap ids: the pages it holds, and those of them that are free
 	uint32_t own_cap;
 	uint4 *stage;                    // per wave [64][stage_k] records of 64 bytes: what the chains of the running round push, lane by lane
@@ -50,8 +50,8 @@ struct DeepParams {
 	                                 // LDS per wave: DEEP_LDS_WORDS(NS, lds_rd) words
 	uint32_t key_T;                  // depth of the interval tables the searches may use for key-form entries (0: rows only -- no tables, or the touch-counting run)
 	uint32_t coop_lanes;             // a chain on one row is taken over by the whole wave (64 levels at a time) when no more than this many chains of the round are still running (0: never)
-	int hist;                        // statistics build: also the expansions by depth and form (stats[32 ..])
+	int hist;                        // statistics build: 1 also the expansions by depth and form (DS_HIST1), 2 the rounds by width (DS_HIST2_*)
 	int careful_all, max_lanes;      // test knobs: every round one pop; lanes a round may use (production: 0, 64)
 	uint32_t *rounds_out;            // or null (statistics build): per work item the rounds its search took
-	unsigned long long *stats;       // or null: [0] rounds, [1] lane-chains run, [2] chains committed, [3] chain steps, [4] careful rounds, [5] pool failures, [6] rank steps and [7] text finishes of exact tails (lane counts)
+	unsigned long long *stats;       // or null: DS_WORDS counters, DS_* (search_slots.hpp); in the CPU emulation: the harness's ES_WORDS words, ES_*
 };

@@ -38,6 +38,7 @@ struct DeepLane { uint32_t k, l; uint32_t i : 16, ldp : 16; uint32_t mm : 8, go 
 #define DEEP_FN static
 DEEP_FN uint4 deep_ld_global16(const uint4 *p) { return *p; }
 #define DEEP_ATOMIC_ADD_U64(p, v) (*(p) += (v))
+#define DEEP_ATOMIC_MAX_U64(p, v) do { if (*(p) < (v)) *(p) = (v); } while (0)
 #define DEEP_CLOCK() 0ull
 #else
 #define DEEP_FN __device__ __forceinline__
@@ -50,6 +51,7 @@ DEEP_FN uint4 deep_ld_global16(const uint4 *p)
 	return make_uint4(v.x, v.y, v.z, v.w);
 }
 #define DEEP_ATOMIC_ADD_U64(p, v) atomicAdd((p), (v))
+#define DEEP_ATOMIC_MAX_U64(p, v) atomicMax((p), (v))
 #define DEEP_CLOCK() ((unsigned long long)wall_clock64())      /* 100 MHz */
 #endif
 
@@ -235,7 +237,7 @@ DEEP_FN void deep_wave_body(const DeepParams &P_, uint32_t *lds, uint32_t wave
 		WAVE_SYNC(); } while (0)
 
 	for (;;) {
-		LANES { L(tu) = 0; if (ln == 0) L(tu) = ATOMIC_ADD_U32(S.work_counter, 1u); }
+		LANES { L(tu) = 0; if (ln == 0) L(tu) = ATOMIC_ADD_U32(S.work_counter + WC_SEARCH, 1u); }
 		const uint32_t idx = WUNI(WBCAST(tu, 0));
 		if (idx >= (uint32_t)S.n) break;
 		const uint32_t rid = WUNI(S.ids ? (uint32_t)S.ids[idx] : idx);
@@ -321,7 +323,7 @@ DEEP_FN void deep_wave_body(const DeepParams &P_, uint32_t *lds, uint32_t wave
 #ifndef NABWA_EMU
 				// (statistics build, NABWA_DEEP_HIST=2: rounds and wave-steps by the round's width -- 1, 2, 3-4, 5-8, ... 33-64 entries)
 				const uint32_t wbin = W <= 1u ? 0u : 32u - (uint32_t)__clz((int)(W - 1u));
-				if (PROF && P.stats && P.hist == 2) { ONE_LANE { atomicAdd(P.stats + 32 + wbin, 1ull); } }
+				if (PROF && P.stats && P.hist == 2) { ONE_LANE { atomicAdd(P.stats + DS_HIST2_ROUNDS + wbin, 1ull); } }
 #endif
 
 				unsigned long long pc1 = 0; if (prof) { LANES { L(tu) = L(e).k; } (void)WUNI(WBCAST(tu, 0)); pc1 = DEEP_CLOCK(); ph_pop += pc1 - pc0; }
@@ -338,7 +340,7 @@ DEEP_FN void deep_wave_body(const DeepParams &P_, uint32_t *lds, uint32_t wave
 					const bool coop_ok = COOP && n_act <= P.coop_lanes && (coop_n < 16u || coop_lv >= 4u * coop_n);
 					if (PROF) { ++st_steps; st_lanesteps += n_act; }
 #ifndef NABWA_EMU
-					if (PROF && P.stats && P.hist == 2) { ONE_LANE { atomicAdd(P.stats + 64 + wbin, 1ull); } }
+					if (PROF && P.stats && P.hist == 2) { ONE_LANE { atomicAdd(P.stats + DS_HIST2_STEPS + wbin, 1ull); } }
 #endif
 					LANES { if (L(act)) {
 						DeepLane &E = L(e);
@@ -367,7 +369,7 @@ DEEP_FN void deep_wave_body(const DeepParams &P_, uint32_t *lds, uint32_t wave
 								uint32_t nk0, nl0, nk1, nl1, nk2, nl2, nk3, nl3;
 								if (PROF) L(pk_exp) += 1u;
 #ifndef NABWA_EMU
-								if (PROF && P.stats && P.hist == 1) { const uint32_t dd = (uint32_t)(len - i - 1) < 31u ? (uint32_t)(len - i - 1) : 31u; atomicAdd(P.stats + 32 + (kf ? 64u : (E.k == E.l ? 32u : 0u)) + dd, 1ull); }
+								if (PROF && P.stats && P.hist == 1) { const uint32_t dd = (uint32_t)(len - i - 1) < DS_HIST1_BINS - 1u ? (uint32_t)(len - i - 1) : DS_HIST1_BINS - 1u; atomicAdd(P.stats + DS_HIST1 + (kf ? 2u * DS_HIST1_BINS : (E.k == E.l ? 1u * DS_HIST1_BINS : 0u)) + dd, 1ull); }
 #endif
 								const int m_seed = S.max_seed_diff - E.mm - E.go - (gape_mode ? E.ge : 0);
 								bool allow_diff = true, allow_M = true;
@@ -983,7 +985,7 @@ DEEP_FN void deep_wave_body(const DeepParams &P_, uint32_t *lds, uint32_t wave
 		ONE_LANE { S.n_aln[item] = n_aln; S.max_ent[item] = max_ent; S.status[item] = (uint8_t)status; }
 		if (PROF && P.rounds_out) { ONE_LANE { P.rounds_out[idx] = (uint32_t)(st_rounds - rounds0); } }
 		if (prof) { const unsigned long long dt = DEEP_CLOCK() - clk0; st_sumclk += dt; if (dt > st_maxclk) st_maxclk = dt; if (st_rounds - rounds0 > st_maxrounds) st_maxrounds = st_rounds - rounds0; }
-		if (counting && status == NABWA_ST_OK) { ONE_LANE { DEEP_ATOMIC_ADD_U64(S.touch_counter, rd_touch); } }
+		if (counting && status == NABWA_ST_OK) { ONE_LANE { DEEP_ATOMIC_ADD_U64(S.touch_counter + TS_TOUCH_S, rd_touch); } }
 	}
 	if (PROF && P.stats) {
 		uint32_t t6 = 0, t7 = 0;
@@ -1001,18 +1003,33 @@ DEEP_FN void deep_wave_body(const DeepParams &P_, uint32_t *lds, uint32_t wave
 		LANES { L(d) = L(pk_f1); } WEXSCAN_U32(L(off), L(d), s_f1);
 		LANES { L(d) = L(pk_fw); } WEXSCAN_U32(L(off), L(d), s_fw);
 		ONE_LANE {
+			// one map for the GPU and the emulation: DS_* (search_slots.hpp).  The emulation's harness hands in ES_WORDS words, not DS_WORDS:
+			// there the slots are filled in a block of this wave's own and the harness's words (ES_*) picked out of it below
 #ifdef NABWA_EMU
-			P.stats[10] += s_key; P.stats[11] += s_ktl; P.stats[12] += s_fk; P.stats[13] += s_f1; P.stats[14] += st_coop; P.stats[15] += st_cooplev;
-			P.stats[0] += st_rounds; P.stats[1] += st_run; P.stats[2] += st_commit; P.stats[3] += st_steps; P.stats[4] += st_careful; P.stats[5] += st_pool; P.stats[6] += t6; P.stats[7] += t7;
+			unsigned long long blk[DS_WORDS] = { 0 };
+			unsigned long long *const stats = blk;
 #else
-			atomicAdd(P.stats + 0, st_rounds); atomicAdd(P.stats + 1, st_run); atomicAdd(P.stats + 2, st_commit);
-			atomicAdd(P.stats + 3, st_steps); atomicAdd(P.stats + 4, st_careful); atomicAdd(P.stats + 5, st_pool);
-			atomicAdd(P.stats + 6, (unsigned long long)t6); atomicAdd(P.stats + 7, (unsigned long long)t7);
-			atomicAdd(P.stats + 16, ph_pop); atomicAdd(P.stats + 17, ph_chain); atomicAdd(P.stats + 18, ph_tail); atomicAdd(P.stats + 19, ph_commit); atomicAdd(P.stats + 20, ph_hit); atomicAdd(P.stats + 21, st_tailit); atomicAdd(P.stats + 22, st_lanesteps); atomicAdd(P.stats + 23, (unsigned long long)s_key); atomicAdd(P.stats + 24, (unsigned long long)s_ktl);
-			atomicAdd(P.stats + 25, (unsigned long long)s_rec); atomicAdd(P.stats + 26, (unsigned long long)s_chl); atomicAdd(P.stats + 27, (unsigned long long)s_prn); atomicAdd(P.stats + 28, (unsigned long long)s_exp); atomicAdd(P.stats + 29, (unsigned long long)s_two);
-			atomicAdd(P.stats + 30, (unsigned long long)s_fk); atomicAdd(P.stats + 31, (unsigned long long)s_f1); atomicAdd(P.stats + 9, (unsigned long long)s_fw);
-			atomicMax(P.stats + 10, st_maxclk); atomicMax(P.stats + 11, st_maxrounds); atomicAdd(P.stats + 12, st_sumclk); atomicMax(P.stats + 13, DEEP_CLOCK() - clk_start);
+			unsigned long long *const stats = P.stats;
 #endif
+#define DEEP_STAT(slot_, v_) DEEP_ATOMIC_ADD_U64(stats + (slot_), (v_))
+			DEEP_STAT(DS_ROUNDS, st_rounds); DEEP_STAT(DS_CHAINS_RUN, st_run); DEEP_STAT(DS_CHAINS_DONE, st_commit);
+			DEEP_STAT(DS_STEPS, st_steps); DEEP_STAT(DS_CAREFUL, st_careful); DEEP_STAT(DS_POOL_FAIL, st_pool);
+			DEEP_STAT(DS_TAIL_RANK, (unsigned long long)t6); DEEP_STAT(DS_TAIL_TEXT, (unsigned long long)t7);
+			DEEP_STAT(DS_PH_POP, ph_pop); DEEP_STAT(DS_PH_CHAIN, ph_chain); DEEP_STAT(DS_PH_TAIL, ph_tail); DEEP_STAT(DS_PH_COMMIT, ph_commit); DEEP_STAT(DS_PH_HIT, ph_hit);
+			DEEP_STAT(DS_TAIL_TURNS, st_tailit); DEEP_STAT(DS_LANE_STEPS, st_lanesteps); DEEP_STAT(DS_KEY_EXPAND, (unsigned long long)s_key); DEEP_STAT(DS_KEY_TAIL, (unsigned long long)s_ktl);
+			DEEP_STAT(DS_RECORDS, (unsigned long long)s_rec); DEEP_STAT(DS_CHILDREN, (unsigned long long)s_chl); DEEP_STAT(DS_PRUNED, (unsigned long long)s_prn);
+			DEEP_STAT(DS_EXPAND, (unsigned long long)s_exp); DEEP_STAT(DS_TWO, (unsigned long long)s_two);
+			DEEP_STAT(DS_FORCED_KEY, (unsigned long long)s_fk); DEEP_STAT(DS_FORCED_ONE, (unsigned long long)s_f1); DEEP_STAT(DS_FORCED_ROWS, (unsigned long long)s_fw);
+			DEEP_ATOMIC_MAX_U64(stats + DS_MAX_CLK, st_maxclk); DEEP_ATOMIC_MAX_U64(stats + DS_MAX_ROUNDS, st_maxrounds); DEEP_STAT(DS_SUM_CLK, st_sumclk);
+			DEEP_ATOMIC_MAX_U64(stats + DS_WAVE_CLK, DEEP_CLOCK() - clk_start);
+#ifdef NABWA_EMU
+			DEEP_STAT(DS_EMU_COOP, st_coop); DEEP_STAT(DS_EMU_COOP_LEV, st_cooplev);
+			unsigned long long *const es = P.stats;
+			for (int q = DS_ROUNDS; q <= DS_TAIL_TEXT; ++q) es[q] += blk[q];
+			es[ES_KEY_EXPAND] += blk[DS_KEY_EXPAND]; es[ES_KEY_TAIL] += blk[DS_KEY_TAIL]; es[ES_FORCED_KEY] += blk[DS_FORCED_KEY]; es[ES_FORCED_ONE] += blk[DS_FORCED_ONE];
+			es[ES_COOP] += blk[DS_EMU_COOP]; es[ES_COOP_LEV] += blk[DS_EMU_COOP_LEV];
+#endif
+#undef DEEP_STAT
 		}
 	}
 }

@@ -39,13 +39,6 @@
 #include "fm_search.hpp"
 #include "launchers.hpp"
 
-#define ST_IDLE   0
-#define ST_WIDTH  1
-#define ST_POP    2
-#define ST_EXACT  3
-#define ST_EXPAND 4
-#define ST_EXIT   5
-
 #define STATE_M 0
 #define STATE_I 1
 #define STATE_D 2
@@ -140,7 +133,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 			// refill (a single address takes ~10^8 atomics per second)
 			if (w_next == w_end) {
 				unsigned int base = 0;
-				if (lane == 0) base = atomicAdd(P.work_counter + 1, (unsigned int)NABWA_WORK_CHUNK);
+				if (lane == 0) base = atomicAdd(P.work_counter + WC_WIDTH, (unsigned int)NABWA_WORK_CHUNK);
 				w_next = __builtin_amdgcn_readfirstlane(base); w_end = w_next + NABWA_WORK_CHUNK;
 			}
 			const unsigned int rank = (unsigned int)__popcll(need & ((1ull << lane) - 1ull)), avail = w_end - w_next;
@@ -310,7 +303,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 	}
 	if (COUNT) {
 		for (int o = 32; o > 0; o >>= 1) touches += __shfl_down(touches, o);
-		if (lane == 0 && P.touch_counter) atomicAdd(P.touch_counter + 1, touches);
+		if (lane == 0 && P.touch_counter) atomicAdd(P.touch_counter + TS_TOUCH_W, touches);
 	}
 #undef WREC
 #undef BX
@@ -327,11 +320,23 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 // When the bound window is stale at pop time the rank query is issued speculatively together
 // with the window; if the entry then turns out to be pruned (bwtgap.c:156) the counts are dropped.
 // =====================================================================================
-#define LS_IDLE  0
-#define LS_POP   1   // needs to pop
-#define LS_HAVE  2   // the entry popped from the arena in the previous trip is in e_*
-#define LS_EXACT 3   // inside an exact tail (bwt.c:237-252), next position e_i - 1
-#define LS_EXIT  4
+enum {           // a lane's state between trips
+	LS_IDLE  = 0,
+	LS_POP   = 1,   // needs to pop
+	LS_HAVE  = 2,   // the entry popped from the arena in the previous trip is in e_*
+	LS_EXACT = 3,   // inside an exact tail (bwt.c:237-252), next position e_i - 1
+	LS_EXIT  = 4
+};
+enum {           // what a lane does with its current entry in one trip: what the trip loads, and the state `st` it leaves
+	TK_NONE      = 0,   // nothing: no entry, an entry pruned at the pop, or a pop whose arena entry is only fetched; st as phase 1 set it
+	TK_EXPAND    = 1,   // a rank query (rows), 32 bytes of the next table level (key form) or the text word (text form): children pushed; LS_POP
+	TK_TAIL      = 2,   // one exact-tail step on rows, a rank query: LS_EXACT, LS_POP when the interval dies or the hit is recorded
+	TK_HIT       = 3,   // an entry with i == 0 is recorded, no query (text form: its row from isa): LS_POP
+	TK_JUMP      = 4,   // a tail or forced walk lands at depth KT, one level-KT table entry: LS_EXACT (tail), LS_HAVE (forced), LS_POP (empty)
+	TK_GROUP     = 5,   // a deletion popped from a gap group, the parent's rank query again: LS_HAVE as that child
+	TK_ROWS      = 6,   // a key-form entry takes on rows, one table entry of its level: LS_HAVE as the same entry in row form (popped from a gap group: as that member)
+	TK_TEXT_TAIL = 7    // an exact tail compared with the text, one text word: LS_EXACT, LS_HAVE at i == 0 (reported next trip), LS_POP on a mismatch
+};
 
 template <bool COUNT>
 __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search_kernel(const SearchParams P_)
@@ -383,7 +388,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 	int bw_base = -1, bw_a = -1;         // 16 bound bytes of strand bw_a from bw_base
 	int sw_base = -1, sw_a = -1;         // same for the seed bounds
 	unsigned long long touches = 0; uint32_t rd_touch = 0, rd_trips = 0;  // COUNT only
-	uint32_t rk_kf = 0, rk_row2 = 0, rk_row1 = 0, rk_tx = 0, rk_pop = 0, rk_tail = 0, rk_jump = 0, rk_gap = 0;   // COUNT only: this read's trips by kind
+	uint32_t rk_kf = 0, rk_row2 = 0, rk_row1 = 0, rk_tx = 0, rk_pop = 0, rk_tail = 0, rk_jump = 0, rk_gap = 0;   // COUNT only: this read's trips by kind (TS_LONG_*)
 	unsigned long long st_trips = 0, st_expand = 0, st_exact = 0, st_ent = 0, st_spec = 0, st_query = 0, st_two = 0, st_exit = 0, st_jump = 0, st_txe = 0, st_txt = 0;
 	bool ovf = false;
 	// A read one of whose strands occurs exactly (kernel W's class 0; DESIGN.md 4, "sure0").  Its first hit is the exact one, at score 0, after which max_diff is 1
@@ -494,12 +499,12 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 		if (need) {
 			if (w_next == w_end) {          // blocks of read numbers per wave, as in kernel W
 				unsigned int b0 = 0;
-				if (lane == 0) b0 = atomicAdd(P.work_counter, (unsigned int)NABWA_WORK_CHUNK);
+				if (lane == 0) b0 = atomicAdd(P.work_counter + WC_SEARCH, (unsigned int)NABWA_WORK_CHUNK);
 				w_next = __builtin_amdgcn_readfirstlane(b0); w_end = w_next + NABWA_WORK_CHUNK;
 				// class 0 (end of the work order): lockstep.  Class 2+ (start of the work order): also 64 reads at a time without
 				// refilling -- not for convergence but for the stragglers: the fewer lanes of a wave are still searching, the fewer
-				// code paths a trip runs through, and the launch waits for exactly those reads (cnt[2] = n_sync[-8])
-				w_sync = P.n_sync && (w_next >= *P.n_sync || w_next < P.n_sync[-8]);
+				// code paths a trip runs through, and the launch waits for exactly those reads (class 2+'s size, seen from n_sync)
+				w_sync = P.n_sync && (w_next >= *P.n_sync || w_next < P.n_sync[NCLS_SIZE + 2 - NCLS_FIRST0]);
 			}
 			const unsigned int rank = (unsigned int)__popcll(need & ((1ull << lane) - 1ull)), avail = w_end - w_next;
 			const unsigned int base = w_next;
@@ -589,9 +594,9 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 			}
 		}
 		// what this lane does with its current entry in this trip
-		int kind = 0;                 // 1 expand, 2 exact-tail step, 3 hit without query (i == 0), 4 tail jump, 5 group member
+		int kind = TK_NONE;
 		bool need_win = false, spec = false, forced = false; int win_hi = 0;
-		int grp_c = 0, mlev = -1, mpost = 0; uint32_t midx = 0; bool kx = false;      // mlev/midx: table entry that turns a key-form entry into rows (kind 6)
+		int grp_c = 0, mlev = -1, mpost = 0; uint32_t midx = 0; bool kx = false;      // mlev/midx: table entry that turns a key-form entry into rows (TK_ROWS)
 		if (have && !finish && e_state == STATE_GROUP) {
 			// pop ONE member of a gap group, newest first (deletion of T, G, C, A, then the insertion); the rest goes back
 			// on the stack it came from, where it is again the top
@@ -604,12 +609,12 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 			if (ext) ++e_ge; else ++e_go;
 			if (l == KEYM) {                                                // key form: the parent (depth len - e_i - 1) or its child j-1, as rows
 				const int dp = len - e_i - 1;
-				kind = 6; st = LS_POP; have = false;
+				kind = TK_ROWS; st = LS_POP; have = false;
 				if (j == 0) { mpost = 1; mlev = dp; midx = k; } else { mpost = 2; mlev = dp + 1; midx = k * 4u + (uint32_t)(j - 1); }
 			}
 			else if (j == 0) { e_state = STATE_I; e_ldp = e_i; }            // the insertion keeps the parent's interval
 			else if (l == TXM) { k -= 1u; e_i += 1; e_state = STATE_D; e_ldp = e_i; }   // text form: the deleted base is the one to the left
-			else { kind = 5; grp_c = j - 1; st = LS_POP; have = false; }    // a deletion: re-derive its interval
+			else { kind = TK_GROUP; grp_c = j - 1; st = LS_POP; have = false; }    // a deletion: re-derive its interval
 		}
 		if (have && !finish) {
 			st = LS_POP;
@@ -617,7 +622,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 			if (m >= 0) {
 				const bool kf = l == KEYM;
 				const int d = len - e_i;                                      // depth of a gap-free entry
-				if (e_i == 0) { if (kf) { kind = 6; mlev = d; midx = k; } else kind = 3; }
+				if (e_i == 0) { if (kf) { kind = TK_ROWS; mlev = d; midx = k; } else kind = TK_HIT; }
 				else {
 					// the pre-check needs bound[e_i-1]; an expansion then needs bound[e_i-2] as well
 					const bool tail = m == 0 && (e_state == STATE_M || gape_mode || e_ge == P.max_gape);
@@ -634,11 +639,11 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 						// row form: the path is known when it is the read's own symbols with at most the one just consumed substituted
 						const bool row_known = l != TXM && !kf && (e_go | e_ge) == 0 && e_state == STATE_M && (e_mm == 0 || (e_mm == 1 && e_ldp == e_i));
 						if (tail) {                                 // nothing may differ any more: exact tail (bwt.c:237-252)
-							kind = 2;                                   // its cursor is e_i: position e_i - 1 is consumed next
+							kind = TK_TAIL;                                   // its cursor is e_i: position e_i - 1 is consumed next
 							// tail jump: the interval after KT symbols (the path so far, then the read's own) is one table entry away
-							if (l == TXM) kind = 7;                  // text form: compare the rest of the read with the text
-							else if (kf) { if (rdkey_ok) kind = 4; else { kind = 6; mlev = d; midx = k; } }
-							else if (rdkey_ok && row_known && d <= KT) kind = 4;
+							if (l == TXM) kind = TK_TEXT_TAIL;                  // text form: compare the rest of the read with the text
+							else if (kf) { if (rdkey_ok) kind = TK_JUMP; else { kind = TK_ROWS; mlev = d; midx = k; } }
+							else if (rdkey_ok && row_known && d <= KT) kind = TK_JUMP;
 						}
 						else {
 							// Forced matches.  Differences are allowed at a level only where the bound of the symbols still to
@@ -647,12 +652,12 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 							// the matching one, popped at once (same score, newest) -- an exact walk in all but name.  For an entry
 							// whose path is known the table gives the interval it arrives with, or that it dies.
 							forced = rdkey_ok && d < KT && (kf || row_known) && (int)(s_fb[threadIdx.x] >> (e_a << 3) & 0xffu) == m;
-							if (forced) kind = 4;
-							else if (kf && d >= KT) { kind = 6; mlev = d; midx = k; }     // depth KT: rows from here on
+							if (forced) kind = TK_JUMP;
+							else if (kf && d >= KT) { kind = TK_ROWS; mlev = d; midx = k; }     // depth KT: rows from here on
 							// The leap ("sure0").  A text-form entry that is the read's own prefix on a strand kernel W proved to occur: its one row
 							// IS that occurrence, so every symbol still to come matches the text, every mismatch sibling is empty, and the gap children of those
 							// levels are counted and never stored (their score is above s_mm).  The walk would end in the suffix e_i positions further left with
-							// i == 0: that entry is made here and reported in this same trip (kind 3), with the entries the walk's levels would have counted.
+							// i == 0: that entry is made here and reported in this same trip (TK_HIT), with the entries the walk's levels would have counted.
 							// (k < e_i cannot be for a real occurrence; such an entry walks as before.)
 							else if (l == TXM && (s0f & S0_ON) && (s0f & S0_PRV << e_a) && e_state == STATE_M && (e_mm | e_go | e_ge) == 0
 									 && n_entries + 4 * len <= P.max_entries && k >= (uint32_t)e_i) {
@@ -664,24 +669,24 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 								if (hi > len - ies) hi = len - ies;
 								if (seeded && P.max_seed_diff < 1 && hi > len - P.seed_len) hi = len - P.seed_len;
 								const int gl = (MG_READ > 0 && hi >= ies) ? hi - ies + 1 : 0;
-								if (P.s0_stats) { atomicAdd(P.s0_stats + 4, 1ull); atomicAdd(P.s0_stats + 5, (unsigned long long)e_i); }
+								if (P.s0_stats) { atomicAdd(P.s0_stats + S0S_LEAPS, 1ull); atomicAdd(P.s0_stats + S0S_LEAP_LEVELS, (unsigned long long)e_i); }
 								// the chain's entry count only rises, so its peak is at the pop of the last entry: n_entries + 2 per such level + that entry
 								n_entries += 2 * gl;
 								if (max_ent < n_entries + 1) max_ent = n_entries + 1;
 								k -= (uint32_t)e_i; e_i = 0; e_ldp = 0;
-								kind = 3; need_win = false; spec = false;
+								kind = TK_HIT; need_win = false; spec = false;
 							}
 							else {
 								if (P.s0_stats && l == TXM && (s0f & S0_ON) && (s0f & S0_PRV << e_a) && e_state == STATE_M && (e_mm | e_go | e_ge) == 0
-									&& n_entries + 4 * len <= P.max_entries) atomicAdd(P.s0_stats + 6, 1ull);     // (then k < e_i)
-								kind = 1; --e_i; kx = kf;
+									&& n_entries + 4 * len <= P.max_entries) atomicAdd(P.s0_stats + S0S_WALKED, 1ull);     // (then k < e_i)
+								kind = TK_EXPAND; --e_i; kx = kf;
 								if ((s0f & S0_ON) && n_entries + 4 * len > P.max_entries) s0f &= ~S0_ON;
 							}
 						}
 					}
 				}
 			}
-		} else if (st == LS_EXACT) kind = l == TXM ? 7 : 2;
+		} else if (st == LS_EXACT) kind = l == TXM ? TK_TEXT_TAIL : TK_TAIL;
 		// a key-form entry turned into rows becomes the current entry of the next trip; a popped gap member takes its shape now
 		auto rows_arrived = [&](uint32_t nk, uint32_t nl) {
 			k = nk; l = nl;
@@ -689,26 +694,26 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 			else if (mpost == 2) { e_i += 1; e_state = STATE_D; e_ldp = e_i; }
 			st = LS_HAVE;
 		};
-		if (kind == 6 && mlev == 0) { rows_arrived(0u, e_a ? P.bwt[0].seq_len : P.bwt[1].seq_len); kind = 0; }   // depth 0: every row
+		if (kind == TK_ROWS && mlev == 0) { rows_arrived(0u, e_a ? P.bwt[0].seq_len : P.bwt[1].seq_len); kind = TK_NONE; }   // depth 0: every row
 
 		const int qb = 1 - e_a;
-		const bool tx = l == TXM && (kind == 1 || kind == 3 || kind == 7);
-		const int spos = (kind == 2 || kind == 7) ? e_i - 1 : e_i;
+		const bool tx = l == TXM && (kind == TK_EXPAND || kind == TK_HIT || kind == TK_TEXT_TAIL);
+		const int spos = (kind == TK_TAIL || kind == TK_TEXT_TAIL) ? e_i - 1 : e_i;
 		const int stag = (e_a << 20) | (spos >> 4);
-		const bool need_seq = (kind == 1 || kind == 2 || kind == 7) && stag != sq_tag;
-		bool query = (kind == 1 && !tx && !kx) || kind == 2 || kind == 5;
-		// text word in front of the suffix (kinds 1 and 7 in text form)
+		const bool need_seq = (kind == TK_EXPAND || kind == TK_TAIL || kind == TK_TEXT_TAIL) && stag != sq_tag;
+		bool query = (kind == TK_EXPAND && !tx && !kx) || kind == TK_TAIL || kind == TK_GROUP;
+		// text word in front of the suffix (TK_EXPAND and TK_TEXT_TAIL in text form)
 		uint2 tw = make_uint2(0u, 0u); bool need_tw = false;
-		if (tx && kind != 3 && k > 0u) {
+		if (tx && kind != TK_HIT && k > 0u) {
 			const uint32_t tag = ((k - 1u) >> 4) | (uint32_t)qb << 31;
 			tw = s_tw[threadIdx.x];
 			need_tw = tw.y != tag;
 			tw.y = tag;
 		}
-		const bool to_text = kind == 1 && !tx && !kx && text_ok && k == l;   // one row left: its children go on in text form
-		if (kind == 2 && !need_seq && SQ_BYTE((uint32_t)spos & 15u) > 3u) query = false;   // an N: no query
+		const bool to_text = kind == TK_EXPAND && !tx && !kx && text_ok && k == l;   // one row left: its children go on in text form
+		if (kind == TK_TAIL && !need_seq && SQ_BYTE((uint32_t)spos & 15u) > 3u) query = false;   // an N: no query
 		const int ii = e_i - (len - P.seed_len);
-		const bool use_seed = kind == 1 && e_i > 0 && seeded && ii > 0;
+		const bool use_seed = kind == TK_EXPAND && e_i > 0 && seeded && ii > 0;
 		const bool need_seed = use_seed && !(sw_a == e_a && ii - 1 >= sw_base && ii < sw_base + 16);
 
 		// ================================================================ phase 2: issue every load
@@ -726,17 +731,17 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 		}
 		uint32_t r_x = 0u;       // text word, or the row of a reported suffix, or the position of the last row
 		if (need_tw) r_x = (qb ? P.bwt[1].text : P.bwt[0].text)[(k - 1u) >> 4];
-		else if (tx && kind == 3) r_x = (qb ? P.bwt[1].isa : P.bwt[0].isa)[k];
+		else if (tx && kind == TK_HIT) r_x = (qb ? P.bwt[1].isa : P.bwt[0].isa)[k];
 		else if (to_text) r_x = (qb ? P.bwt[1].sa_full : P.bwt[0].sa_full)[k];
 		uint2 r_km = make_uint2(1u, 0u);
-		// sure0: a key-form parent that is the read's own prefix.  Each substituted child will be popped as an exact tail and jump (kind 4) to the level-KT
+		// sure0: a key-form parent that is the read's own prefix.  Each substituted child will be popped as an exact tail and jump (TK_JUMP) to the level-KT
 		// entry of (its key ++ the read's next symbols), a key known here: fetch the three entries beside the children
 		// (in the data registers of the rank query, which such a trip leaves free: a2 = the entries of the second and third substitute, a3.x = 4 | the read's symbol)
 		uint4 a0, a1, a2, a3, b0, b1, b2, b3;
 		a0 = a1 = a2 = a3 = b0 = b1 = b2 = b3 = make_uint4(0, 0, 0, 0);
 		// (not where the bound at the children's position is above 0, or not at hand: see the expansion)
 		bool gh = kx && e_i > 0 && (s0f & S0_ON) && (e_mm | e_go | e_ge) == 0 && len - e_i < KT && !need_win && (BW_BYTE(e_i - 1 - bw_base) & 127u) == 0u;
-		if (kind == 4 || gh) {
+		if (kind == TK_JUMP || gh) {
 			uint32_t key = e_a ? s_key[threadIdx.x].y : s_key[threadIdx.x].x, key2 = 0, key3 = 0;
 			const int d = len - e_i;
 			if (gh) {
@@ -759,7 +764,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 			r_km = tab[key];
 			if (gh) { const uint2 g2 = tab[key2], g3 = tab[key3]; a2 = make_uint4(g2.x, g2.y, g3.x, g3.y); }
 		}
-		if (kind == 6) r_km = ((qb ? P.bwt[1].kmer_lo : P.bwt[0].kmer_lo) + LVO(mlev))[midx];
+		if (kind == TK_ROWS) r_km = ((qb ? P.bwt[1].kmer_lo : P.bwt[0].kmer_lo) + LVO(mlev))[midx];
 		// the rank query: Occ of all four bases at rows k-1 and l of index qb (bwt.c:159-216 conventions)
 		uint32_t rk = 0, rl = 0; bool kvalid = false, two = false;
 		if (kx) {       // key form: the four children of this level, 32 bytes of the next table level
@@ -783,7 +788,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 		// look-ahead pop (see s_pf): only from inside a tail, with nothing pending in registers
 		bool pf_now = false; uint32_t pf_cand = NIL;
 		if (want_ent) { pf_cand = ent_slot; pf_now = true; }                // a pop that was not fetched ahead: fetch now, pop next trip
-		else if ((kind == 2 || kind == 4 || kind == 7) && !p_valid && mask_any()) {
+		else if ((kind == TK_TAIL || kind == TK_JUMP || kind == TK_TEXT_TAIL) && !p_valid && mask_any()) {
 			const int bm = mask_first();
 			pf_cand = head_get(bm);
 			pf_now = pf_cand != pf_slot;
@@ -792,12 +797,12 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 		if (!COUNT && P.trip_budget && st != LS_IDLE && st != LS_EXIT) ++rd_trips;
 		if (COUNT && st != LS_IDLE && st != LS_EXIT) {
 			++rd_trips;
-			if (kind == 1) { if (kx) ++rk_kf; else if (tx) ++rk_tx; else if (two) ++rk_row2; else ++rk_row1; if (e_go | e_ge) ++rk_gap; }
-			else if (want_ent) ++rk_pop; else if (kind == 2 || kind == 7) ++rk_tail; else if (kind == 4) ++rk_jump;
+			if (kind == TK_EXPAND) { if (kx) ++rk_kf; else if (tx) ++rk_tx; else if (two) ++rk_row2; else ++rk_row1; if (e_go | e_ge) ++rk_gap; }
+			else if (want_ent) ++rk_pop; else if (kind == TK_TAIL || kind == TK_TEXT_TAIL) ++rk_tail; else if (kind == TK_JUMP) ++rk_jump;
 		}
-		if (COUNT) {   // trip statistics (instrumented build only): [2] trips, [3..] lane-trips by activity
-			const unsigned long long bx = __ballot(kind == 1), be = __ballot(kind == 2), bm = __ballot(want_ent),
-				bs = __ballot(spec), bq = __ballot(query), b2 = __ballot(query && two), bi = __ballot(st == LS_EXIT), bj = __ballot(kind == 4), bt = __ballot(tx && kind == 1), b7 = __ballot(kind == 7);
+		if (COUNT) {   // trip statistics (instrumented build only): TS_TRIPS, then lane-trips by activity
+			const unsigned long long bx = __ballot(kind == TK_EXPAND), be = __ballot(kind == TK_TAIL), bm = __ballot(want_ent),
+				bs = __ballot(spec), bq = __ballot(query), b2 = __ballot(query && two), bi = __ballot(st == LS_EXIT), bj = __ballot(kind == TK_JUMP), bt = __ballot(tx && kind == TK_EXPAND), b7 = __ballot(kind == TK_TEXT_TAIL);
 			if (lane == 0) {
 				st_trips += 1; st_expand += __popcll(bx); st_exact += __popcll(be); st_ent += __popcll(bm); st_spec += __popcll(bs);
 				st_query += __popcll(bq); st_two += __popcll(b2); st_exit += __popcll(bi); st_jump += __popcll(bj); st_txe += __popcll(bt); st_txt += __popcll(b7);
@@ -807,29 +812,29 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 		__builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the window loads above wrote LDS behind the compiler's back
 		// ================================================================ phase 3: consume
 		if (pf_now) { s_pf[threadIdx.x] = r_ent; pf_slot = pf_cand; }
-		if (spec && m < (int)(BW_BYTE(win_hi - bw_base) & 127u)) kind = 0;   // pruned after all (bwtgap.c:156)
+		if (spec && m < (int)(BW_BYTE(win_hi - bw_base) & 127u)) kind = TK_NONE;   // pruned after all (bwtgap.c:156)
 		if (need_tw) { tw.x = r_x; s_tw[threadIdx.x] = tw; }
 		int c = 4;
-		if (kind == 1 || kind == 2) c = (int)SQ_BYTE((uint32_t)spos & 15u);
-		if (kind == 2 && c > 3) query = false;
+		if (kind == TK_EXPAND || kind == TK_TAIL) c = (int)SQ_BYTE((uint32_t)spos & 15u);
+		if (kind == TK_TAIL && c > 3) query = false;
 		Occ4 ck, cl;
 		ck.c[0] = ck.c[1] = ck.c[2] = ck.c[3] = 0; cl = ck;
-		if (query && kind) {
+		if (query && kind != TK_NONE) {
 			cl = nabwa_count4(a0, a1, a2, a3, rl);
 			if (kvalid) {       // one counting sequence for row k-1 too: pick its bucket first (16 selects < a third copy of the count)
 				const uint4 s0 = two ? b0 : a0, s1 = two ? b1 : a1, s2 = two ? b2 : a2, s3 = two ? b3 : a3;
 				ck = nabwa_count4(s0, s1, s2, s3, rk);
 			}
-			if (COUNT && kind != 5) rd_touch += ref_touches(qb ? P.bwt[1] : P.bwt[0], k - 1u, l, kind == 1);   // (the reference derived a group's members in the parent's query)
+			if (COUNT && kind != TK_GROUP) rd_touch += ref_touches(qb ? P.bwt[1] : P.bwt[0], k - 1u, l, kind == TK_EXPAND);   // (the reference derived a group's members in the parent's query)
 		}
-		if (kx && kind == 1) {
+		if (kx && kind == TK_EXPAND) {
 			// key form: child j exists iff its table interval is not empty, and is again a key: present it to the generic
 			// expansion below as "counts" (with C(.) = 0) that yield {key * 4 + j, KEYM}
 			const uint32_t ek[4] = { a0.x, a0.z, a1.x, a1.z }, el[4] = { a0.y, a0.w, a1.y, a1.w };
 #pragma unroll
 			for (int j = 0; j < 4; ++j) { const bool ne = ek[j] <= el[j]; ck.c[j] = ne ? k * 4u + (uint32_t)j - 1u : 0u; cl.c[j] = ne ? KEYM : 0u; }
 		}
-		const bool tx1 = tx && kind == 1;
+		const bool tx1 = tx && kind == TK_EXPAND;
 		if (tx1) {
 			// the one row's only non-empty child is for the text base b to the left of the suffix, and it is the suffix
 			// starting there: present it to the generic expansion below as "counts" (with C(.) = 0) that yield {k-1, TXM}
@@ -837,7 +842,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 #pragma unroll
 			for (int j = 0; j < 4; ++j) { ck.c[j] = b == (uint32_t)j ? k - 2u : 0u; cl.c[j] = b == (uint32_t)j ? TXM : 0u; }
 		}
-		const bool syn = tx1 || (kx && kind == 1);
+		const bool syn = tx1 || (kx && kind == TK_EXPAND);
 		const uint32_t L2q0 = syn ? 0u : (qb ? P.bwt[1].L2[0] : P.bwt[0].L2[0]), L2q1 = syn ? 0u : (qb ? P.bwt[1].L2[1] : P.bwt[0].L2[1]);
 		const uint32_t L2q2 = syn ? 0u : (qb ? P.bwt[1].L2[2] : P.bwt[0].L2[2]), L2q3 = syn ? 0u : (qb ? P.bwt[1].L2[3] : P.bwt[0].L2[3]);
 		const uint32_t seqlen_q = qb ? P.bwt[1].seq_len : P.bwt[0].seq_len;
@@ -845,17 +850,17 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 #define CK(cc) ((cc) == 0 ? ck.c[0] : ((cc) == 1 ? ck.c[1] : ((cc) == 2 ? ck.c[2] : ck.c[3])))
 #define CL(cc) ((cc) == 0 ? cl.c[0] : ((cc) == 1 ? cl.c[1] : ((cc) == 2 ? cl.c[2] : cl.c[3])))
 
-		if (kind == 6) rows_arrived(r_km.x, r_km.y);
-		else if (kind == 5) {                                   // the popped deletion: one more base of the reference, same read position
+		if (kind == TK_ROWS) rows_arrived(r_km.x, r_km.y);
+		else if (kind == TK_GROUP) {                                   // the popped deletion: one more base of the reference, same read position
 			k = L2Q(grp_c) + CK(grp_c) + 1u; l = L2Q(grp_c) + CL(grp_c);
 			e_i += 1; e_state = STATE_D; e_ldp = e_i;
 			st = LS_HAVE;
-		} else if (kind == 4) {                                 // landed at depth KT (len > KT, so the tail goes on)
+		} else if (kind == TK_JUMP) {                                 // landed at depth KT (len > KT, so the tail goes on)
 			k = r_km.x; l = r_km.y;
 			if (k > l) st = LS_POP;
 			else if (forced) { e_i = len - KT; e_ldp = 0; st = LS_HAVE; }   // arrives as the matching child it would have become
 			else { e_i = len - KT; st = LS_EXACT; }
-		} else if (kind == 7) {
+		} else if (kind == TK_TEXT_TAIL) {
 			// exact tail in text form: read symbols e_i-1, e_i-2, ... against the text to the left, as far as both 16-base words reach
 			uint32_t pp = k; bool fail = false;
 			for (;;) {
@@ -870,10 +875,10 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 			if (fail) st = LS_POP;
 			else if (e_i == 0) st = LS_HAVE;                          // matched to the end: reported (as a row) in the next trip
 			else st = LS_EXACT;
-		} else if (kind == 2 || kind == 3) {
+		} else if (kind == TK_TAIL || kind == TK_HIT) {
 			bool hit = false;
-			if (kind == 3 && tx) { k = r_x; l = r_x; }                // the row of the suffix (isa)
-			if (kind == 3) hit = true;
+			if (kind == TK_HIT && tx) { k = r_x; l = r_x; }                // the row of the suffix (isa)
+			if (kind == TK_HIT) hit = true;
 			else if (c > 3) st = LS_POP;                          // an N in the tail: no match
 			else {
 				k = L2Q(c) + CK(c) + 1u; l = L2Q(c) + CL(c);
@@ -887,7 +892,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 				const int score = e_mm * P.s_mm + e_go * P.s_gapo + e_ge * P.s_gape;
 				bool do_add = true;
 				if (n_aln == 0) {
-					if ((s0f & S0_ON) && score != 0) { status = NABWA_ST_OVERFLOW; finish = true; do_add = false; s0f &= ~S0_ON; if (P.s0_stats) atomicAdd(P.s0_stats + 3, 1ull); }   // not the exact hit first: kernel D searches the read from the start
+					if ((s0f & S0_ON) && score != 0) { status = NABWA_ST_OVERFLOW; finish = true; do_add = false; s0f &= ~S0_ON; if (P.s0_stats) atomicAdd(P.s0_stats + S0S_NET, 1ull); }   // not the exact hit first: kernel D searches the read from the start
 					best_score = score;
 					const int best_diff = e_mm + e_go + (gape_mode ? e_ge : 0);
 					if (!nonstop) max_diff = best_diff + 1 > MD_READ ? MD_READ : best_diff + 1;
@@ -937,7 +942,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 					}
 				}
 			}
-		} else if (kind == 1) {
+		} else if (kind == TK_EXPAND) {
 			// ---- node expansion (bwtgap.c:201-260); e_i is already decremented
 			const uint32_t occ = tx1 ? 1u : l - k + 1u;                   // (key form: only read by deletion-state parents, which are never in key form)
 			bool match_child = false;
@@ -1062,29 +1067,29 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 		if (finish) {
 			const bool net = (s0f & S0_ON) && status == NABWA_ST_OK && n_aln == 0;       // the exact occurrence was not found: kernel D searches the read from the start
 			if (net) status = NABWA_ST_OVERFLOW;
-			if (P.s0_stats && (s0f & S0_WAS)) atomicAdd(P.s0_stats, 1ull);
+			if (P.s0_stats && (s0f & S0_WAS)) atomicAdd(P.s0_stats + S0S_READS, 1ull);
 			if (P.s0_stats && (s0f >> 16 & 0x3fffu)) {
-				atomicAdd(P.s0_stats + 1, (unsigned long long)(s0f >> 16 & 0x7fu)); atomicAdd(P.s0_stats + 2, (unsigned long long)(s0f >> 23 & 0x7fu));
+				atomicAdd(P.s0_stats + S0S_KF_EMPTY, (unsigned long long)(s0f >> 16 & 0x7fu)); atomicAdd(P.s0_stats + S0S_KF_LANDED, (unsigned long long)(s0f >> 23 & 0x7fu));
 			}
-			if (P.s0_stats && net) atomicAdd(P.s0_stats + 3, 1ull);
+			if (P.s0_stats && net) atomicAdd(P.s0_stats + S0S_NET, 1ull);
 			P.n_aln[item] = n_aln; P.max_ent[item] = (!COUNT && status == NABWA_ST_OVERFLOW) ? (int)rd_trips : max_ent; P.status[item] = (uint8_t)status;      // (a search handed on: the trips it took here -- kernel D's statistics dump reads them; its own max_ent replaces this)
 			if (COUNT && status == NABWA_ST_OK) touches += rd_touch;   // abandoned reads are counted by the wide pass
 			if (COUNT && P.touch_counter && rd_trips > 8000u) {
-				atomicAdd(P.touch_counter + 16, 1ull); atomicAdd(P.touch_counter + 17, (unsigned long long)rd_trips); atomicAdd(P.touch_counter + 18, (unsigned long long)rk_kf);
-				atomicAdd(P.touch_counter + 19, (unsigned long long)rk_row2); atomicAdd(P.touch_counter + 20, (unsigned long long)rk_row1); atomicAdd(P.touch_counter + 21, (unsigned long long)rk_tx);
-				atomicAdd(P.touch_counter + 22, (unsigned long long)rk_pop); atomicAdd(P.touch_counter + 23, (unsigned long long)rk_tail); atomicAdd(P.touch_counter + 24, (unsigned long long)rk_jump); atomicAdd(P.touch_counter + 25, (unsigned long long)rk_gap);
+				atomicAdd(P.touch_counter + TS_LONG_READS, 1ull); atomicAdd(P.touch_counter + TS_LONG_TRIPS, (unsigned long long)rd_trips); atomicAdd(P.touch_counter + TS_LONG_KF, (unsigned long long)rk_kf);
+				atomicAdd(P.touch_counter + TS_LONG_ROW2, (unsigned long long)rk_row2); atomicAdd(P.touch_counter + TS_LONG_ROW1, (unsigned long long)rk_row1); atomicAdd(P.touch_counter + TS_LONG_TEXT, (unsigned long long)rk_tx);
+				atomicAdd(P.touch_counter + TS_LONG_POP, (unsigned long long)rk_pop); atomicAdd(P.touch_counter + TS_LONG_TAIL, (unsigned long long)rk_tail); atomicAdd(P.touch_counter + TS_LONG_JUMP, (unsigned long long)rk_jump); atomicAdd(P.touch_counter + TS_LONG_GAP, (unsigned long long)rk_gap);
 			}
-			if (COUNT && P.touch_counter) { atomicMax(P.touch_counter + 13, (unsigned long long)rd_trips); if (rd_trips > 2000u) atomicAdd(P.touch_counter + 14, 1ull); if (rd_trips > 500u) atomicAdd(P.touch_counter + 15, 1ull); }
+			if (COUNT && P.touch_counter) { atomicMax(P.touch_counter + TS_MAX_TRIPS, (unsigned long long)rd_trips); if (rd_trips > 2000u) atomicAdd(P.touch_counter + TS_OVER_2000, 1ull); if (rd_trips > 500u) atomicAdd(P.touch_counter + TS_OVER_500, 1ull); }
 			st = LS_IDLE;
 		}
 	}
 	if (COUNT) {
 		for (int o = 32; o > 0; o >>= 1) touches += __shfl_down(touches, o);
 		if (lane == 0 && P.touch_counter) {
-			atomicAdd(P.touch_counter, touches);
-			atomicAdd(P.touch_counter + 2, st_trips); atomicAdd(P.touch_counter + 3, st_expand); atomicAdd(P.touch_counter + 4, st_exact);
-			atomicAdd(P.touch_counter + 5, st_ent); atomicAdd(P.touch_counter + 6, st_spec); atomicAdd(P.touch_counter + 7, st_query);
-			atomicAdd(P.touch_counter + 8, st_two); atomicAdd(P.touch_counter + 9, st_exit); atomicAdd(P.touch_counter + 10, st_jump); atomicAdd(P.touch_counter + 11, st_txe); atomicAdd(P.touch_counter + 12, st_txt);
+			atomicAdd(P.touch_counter + TS_TOUCH_S, touches);
+			atomicAdd(P.touch_counter + TS_TRIPS, st_trips); atomicAdd(P.touch_counter + TS_EXPAND, st_expand); atomicAdd(P.touch_counter + TS_EXACT, st_exact);
+			atomicAdd(P.touch_counter + TS_ENT_LOAD, st_ent); atomicAdd(P.touch_counter + TS_SPEC, st_spec); atomicAdd(P.touch_counter + TS_QUERY, st_query);
+			atomicAdd(P.touch_counter + TS_TWO, st_two); atomicAdd(P.touch_counter + TS_EXITED, st_exit); atomicAdd(P.touch_counter + TS_JUMP, st_jump); atomicAdd(P.touch_counter + TS_TEXT_EXPAND, st_txe); atomicAdd(P.touch_counter + TS_TEXT_TAIL, st_txt);
 		}
 	}
 }
@@ -1127,324 +1132,4 @@ extern "C" int nabwa_search_occupancy(int ns)
 	hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fm_search_kernel<false>, NABWA_SEARCH_BLOCK,
 																(size_t)ns * NABWA_SEARCH_BLOCK * 2 + NABWA_SEARCH_BLOCK * 84);
 	return e == hipSuccess ? nb : 0;
-}
-
-// re-lay the reads out with every read starting on a 16-byte boundary (register windows load 16 bases), and form
-// the interval-table keys: the first T symbols the search consumes (positions len-1 down to len-T) of each strand.
-// 16 lanes per read, one 16-base chunk of both strands per lane and turn: loads and stores of a read are consecutive
-// across its lanes (one thread per read walking bytes took 62 ms for 10 M reads; this form streams at HBM rate).
-__global__ __launch_bounds__(256) void pad_reads_kernel(int n, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ rseq,
-													const int64_t *__restrict__ off, const int64_t *__restrict__ poff,
-													uint8_t *__restrict__ pseq, uint8_t *__restrict__ prseq, int32_t *__restrict__ rd_len,
-													uint32_t *__restrict__ rd_key, int T, int seed_len, uint32_t *__restrict__ rd_pack, int pack_stride,
-													const uint8_t *__restrict__ md_tab, const uint8_t *__restrict__ mg_tab,
-													uint8_t *__restrict__ rd_md, uint8_t *__restrict__ rd_mg)
-{
-	const int t = threadIdx.x & 15;
-	const int i = blockIdx.x * 16 + (threadIdx.x >> 4);
-	if (i >= n) return;                                          /* whole 16-lane groups leave together */
-	const int64_t o = off[i], p = poff[i];
-	const int L = (int)(off[i + 1] - o), NC = (int)(poff[i + 1] - p) >> 4;
-	if (t == 0) { rd_len[i] = L; rd_md[i] = md_tab[L]; rd_mg[i] = mg_tab[L]; }      /* max_diff / max_gapo of a read follow from its length (host tables) */
-	// both strands 2 bits per base as well, base j in word j>>4 from the TOP bits down, so that the 16 symbols from any position
-	// are one 32-bit extract in table-key order; the word after the last says whether the strand holds an N (then: no keys)
-	const int PW = pack_stride / 2;
-	uint32_t *const pk = rd_pack ? rd_pack + (size_t)i * pack_stride : 0;
-	const int n_turns = pk && PW - 1 > NC ? PW - 1 : NC;
-	uint32_t anyN[2] = { 0u, 0u };
-	for (int c = t; c < n_turns; c += 16) {
-		for (int st = 0; st < 2; ++st) {
-			const uint8_t *src = (st ? rseq : seq) + o + 16 * c;
-			uint32_t w[4] = { 0x04040404u, 0x04040404u, 0x04040404u, 0x04040404u };
-			const int have = L - 16 * c;                          /* bases of this chunk that exist */
-			if (have >= 16) __builtin_memcpy(w, src, 16);
-			else {
-#pragma unroll
-				for (int k = 0; k < 16; ++k) if (k < have) { const uint32_t v = src[k]; w[k >> 2] = (w[k >> 2] & ~(0xffu << (8 * (k & 3)))) | v << (8 * (k & 3)); }
-			}
-			if (c < NC) *(uint4*)((st ? prseq : pseq) + p + 16 * c) = make_uint4(w[0], w[1], w[2], w[3]);
-			if (pk && c < PW - 1) {
-				uint32_t x = 0;
-#pragma unroll
-				for (int k = 0; k < 16; ++k) {
-					const uint32_t v = k < have ? (w[k >> 2] >> (8 * (k & 3)) & 0xffu) : 0u;
-					anyN[st] |= v > 3u ? 1u : 0u;
-					x |= (v & 3u) << (30 - 2 * k);
-				}
-				pk[st * PW + c] = x;
-			}
-		}
-	}
-	if (pk) {
-		for (int m = 8; m; m >>= 1) { anyN[0] |= __shfl_xor(anyN[0], m, 16); anyN[1] |= __shfl_xor(anyN[1], m, 16); }
-		if (t < 2) pk[t * PW + PW - 1] = anyN[t];
-	}
-	// keys (first consumed symbol = most significant digit): [0,1] kernel S, from position L-1 downwards, seq / rseq;
-	// [2,3] kernel W full passes, from position 0 upwards; [4,5] kernel W seed passes, from position L-seed_len upwards
-	if (t < 6) {
-		const int v = t >> 1;
-		uint32_t key = 0xffffffffu;
-		if (T > 0 && L > T && (v < 2 || (L > seed_len && seed_len > T))) {
-			const uint8_t *src = ((t & 1) ? rseq : seq) + o;
-			uint32_t a = 0; bool ok = true;
-			for (int q = 1; q <= T; ++q) {
-				const int pos = v == 0 ? L - q : (v == 1 ? q - 1 : L - seed_len + q - 1);
-				const uint32_t x = src[pos];
-				ok = ok && x < 4u; a = a << 2 | (x & 3u);
-			}
-			if (ok) key = a;
-		}
-		rd_key[6 * (size_t)i + t] = key;
-	}
-}
-
-extern "C" void nabwa_launch_pad_reads(int n, const uint8_t *seq, const uint8_t *rseq, const int64_t *off, const int64_t *poff,
-									   uint8_t *pseq, uint8_t *prseq, int32_t *rd_len, uint32_t *rd_key, int T, int seed_len, uint32_t *rd_pack, int pack_stride,
-									   const uint8_t *md_tab, const uint8_t *mg_tab, uint8_t *rd_md, uint8_t *rd_mg, hipStream_t s)
-{
-	if (n <= 0) return;
-	hipLaunchKernelGGL(pad_reads_kernel, dim3((n + 15) / 16), dim3(256), 0, s, n, seq, rseq, off, poff, pseq, prseq, rd_len, rd_key, T, seed_len, rd_pack, pack_stride,
-					   md_tab, mg_tab, rd_md, rd_mg);
-}
-
-// padded length of every read (starts go on 16-byte boundaries), and 0 after the last: input of the scan that gives the starts
-__global__ __launch_bounds__(256) void padded_len_kernel(int n, const int64_t *__restrict__ off, int64_t *__restrict__ plen)
-{
-	const int i = blockIdx.x * 256 + threadIdx.x;
-	if (i <= n) plen[i] = i < n ? (off[i + 1] - off[i] + 15) / 16 * 16 : 0;
-}
-
-extern "C" void nabwa_launch_padded_len(int n, const int64_t *off, int64_t *plen, hipStream_t s)
-{
-	hipLaunchKernelGGL(padded_len_kernel, dim3(n / 256 + 1), dim3(256), 0, s, n, off, plen);
-}
-
-__global__ __launch_bounds__(256) void collect_kernel(int n, const uint8_t *__restrict__ status, int32_t *__restrict__ ids,
-												  unsigned int *__restrict__ count, int which)
-{
-	const int i = blockIdx.x * 256 + threadIdx.x;
-	if (i < n && status[i] == which) ids[atomicAdd(count, 1u)] = i;
-}
-
-// The same, in the order kernel D should start them: its launch ends with its longest search, so the searches that look
-// longest go first.  (Measured with NABWA_DEEP_DUMP + profiles/probes/deep_order_probe.py on the ancient-DNA workload: by the searches'
-// round counts this key schedules no better than a random order, 1.19 x the bound, and a key of {no hit yet, max_diff, read length}
-// reaches 1.07 -- but the launch got 4 % SLOWER with it: the longest search then runs its whole life beside a full machine, 21 us per
-// round instead of 17 when it finishes alone.  Wave priority for the head of the list changed nothing.  Not kept.)  Key = max_diff - (the lower bound of the read's differences from kernel W: the smaller restart count of
-// its two strands): the more differences the bounds leave open, the larger the tree; reads that filled the first pass's hit list
-// (repeat families: hundreds of hit rows, every one-difference variant walked to the end) go before everything else.  One pass per
-// key value, largest first.
-__global__ __launch_bounds__(256) void collect_keyed_kernel(int n, const uint8_t *__restrict__ status, int32_t *__restrict__ ids,
-															unsigned int *__restrict__ count, int which, const uint8_t *__restrict__ cls,
-															const uint8_t *__restrict__ md, int lo, int hi, const int32_t *__restrict__ n_aln, int aln_cap, int max_key)
-{
-	const int i = blockIdx.x * 256 + threadIdx.x;
-	if (i >= n || status[i] != which) return;
-	const int c0 = cls[2 * (size_t)i], c1 = cls[2 * (size_t)i + 1];
-	int k = (int)md[i] - (c0 < c1 ? c0 : c1);
-	if (n_aln[i] >= aln_cap) k = max_key;          // the first pass filled its hit list: a read from a repeat family, the longest searches there are
-	if (k >= lo && k <= hi) ids[atomicAdd(count, 1u)] = i;
-}
-
-extern "C" void nabwa_launch_collect_keyed(int n, const uint8_t *status, int32_t *ids, unsigned int *count, int which,
-										   const uint8_t *cls, const uint8_t *md, int max_key, const int32_t *n_aln, int aln_cap, hipStream_t s)
-{
-	if (n <= 0) return;
-	for (int key = max_key; key >= 0; --key)
-		hipLaunchKernelGGL(collect_keyed_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, status, ids, count, which, cls, md,
-						   key ? key : -0x7fffffff, key == max_key ? 0x7fffffff : key, n_aln, aln_cap, max_key);
-}
-
-// ids of the reads whose status is `which` (NABWA_ST_OVERFLOW after kernel S, NABWA_ST_POOL / NABWA_ST_HITCAP after kernel D)
-extern "C" void nabwa_launch_collect(int n, const uint8_t *status, int32_t *ids, unsigned int *count, int which, hipStream_t s)
-{
-	if (n <= 0) return;
-	hipLaunchKernelGGL(collect_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, status, ids, count, which);
-}
-
-__global__ __launch_bounds__(256) void scatter_wide_kernel(int n2, const int32_t *__restrict__ ids, const int32_t *__restrict__ n_aln2,
-													   const int32_t *__restrict__ max_ent2, const uint8_t *__restrict__ status2,
-													   int32_t *__restrict__ n_aln, int32_t *__restrict__ max_ent,
-													   uint8_t *__restrict__ status, const int32_t *__restrict__ wide_idx)
-{
-	const int q = blockIdx.x * 256 + threadIdx.x;
-	if (q >= n2) return;
-	const int rid = ids[q], j = wide_idx[rid];       /* j: the read's row in the wide result arrays (assign_slots_kernel) */
-	if (status2[j] == NABWA_ST_OK) { n_aln[rid] = n_aln2[j]; max_ent[rid] = max_ent2[j]; status[rid] = NABWA_ST_WIDE; }
-	else { n_aln[rid] = 0; max_ent[rid] = max_ent2[j]; status[rid] = status2[j]; }     /* NABWA_ST_POOL / NABWA_ST_HITCAP: the host decides */
-}
-
-// results of the searches that were run again with longer hit lists (nabwa_batch_sync): the q-th search of the list -> its read; its
-// rows are block + q * cap3, entered in the table of grown row blocks at slot0 + q, which the read's wide_idx names from now on
-__global__ __launch_bounds__(256) void scatter_grown_kernel(int n2, const int32_t *__restrict__ ids, const int32_t *__restrict__ n_aln3,
-															const int32_t *__restrict__ max_ent3, const uint8_t *__restrict__ status3,
-															int32_t *__restrict__ n_aln, int32_t *__restrict__ max_ent, uint8_t *__restrict__ status,
-															int32_t *__restrict__ wide_idx, const uint4 *block, size_t cap3, const uint4 **__restrict__ grown, int slot0)
-{
-	const int q = blockIdx.x * 256 + threadIdx.x;
-	if (q >= n2) return;
-	const int rid = ids[q];
-	max_ent[rid] = max_ent3[q];
-	if (status3[q] == NABWA_ST_OK) { n_aln[rid] = n_aln3[q]; status[rid] = NABWA_ST_GROWN; wide_idx[rid] = slot0 + q; grown[slot0 + q] = block + (size_t)q * cap3; }
-	else { n_aln[rid] = 0; status[rid] = status3[q]; }
-}
-extern "C" void nabwa_launch_scatter_grown(int n2, const int32_t *ids, const int32_t *n_aln3, const int32_t *max_ent3, const uint8_t *status3,
-										   int32_t *n_aln, int32_t *max_ent, uint8_t *status, int32_t *wide_idx, const uint4 *block, size_t cap3,
-										   const uint4 **grown, int slot0, hipStream_t s)
-{
-	if (n2 <= 0) return;
-	hipLaunchKernelGGL(scatter_grown_kernel, dim3((n2 + 255) / 256), dim3(256), 0, s, n2, ids, n_aln3, max_ent3, status3, n_aln, max_ent, status, wide_idx, block, cap3, grown, slot0);
-}
-
-// the reads that go to the wide passes get a row each in the wide result arrays; it stays theirs over the tiers
-__global__ __launch_bounds__(256) void assign_slots_kernel(int n2, const int32_t *__restrict__ ids, int32_t *__restrict__ wide_idx)
-{
-	const int j = blockIdx.x * 256 + threadIdx.x;
-	if (j < n2) wide_idx[ids[j]] = j;
-}
-
-extern "C" void nabwa_launch_assign_slots(int n2, const int32_t *ids, int32_t *wide_idx, hipStream_t s)
-{
-	if (n2 <= 0) return;
-	hipLaunchKernelGGL(assign_slots_kernel, dim3((n2 + 255) / 256), dim3(256), 0, s, n2, ids, wide_idx);
-}
-
-extern "C" void nabwa_launch_scatter_wide(int n2, const int32_t *ids, const int32_t *n_aln2, const int32_t *max_ent2,
-										  const uint8_t *status2, int32_t *n_aln, int32_t *max_ent, uint8_t *status,
-										  int32_t *wide_idx, hipStream_t s)
-{
-	if (n2 <= 0) return;
-	hipLaunchKernelGGL(scatter_wide_kernel, dim3((n2 + 255) / 256), dim3(256), 0, s, n2, ids, n_aln2, max_ent2, status2,
-					   n_aln, max_ent, status, wide_idx);
-}
-
-__device__ __forceinline__ const uint4 *rows_of(int i, const uint4 *aln, int aln_cap, const uint8_t *status,
-												const int32_t *wide_idx, const uint4 *aln2, int aln_cap2, const uint4 *const *grown)
-{
-	const int st = status[i];
-	if (st == NABWA_ST_GROWN) return grown[wide_idx[i]];           /* a hit list that outgrew the wide rows: its own block (nabwa_batch_sync) */
-	return st == NABWA_ST_WIDE ? aln2 + (size_t)wide_idx[i] * aln_cap2 : aln + (size_t)i * aln_cap;
-}
-
-// compaction: rows of read i go to out[row_off[i] ...]
-__global__ __launch_bounds__(256) void gather_kernel(int n, const int32_t *__restrict__ n_aln, const uint32_t *__restrict__ row_off,
-												 const uint4 *__restrict__ aln, int aln_cap, const uint8_t *__restrict__ status,
-												 const int32_t *__restrict__ wide_idx, const uint4 *__restrict__ aln2, int aln_cap2,
-												 const uint4 *const *__restrict__ grown, uint4 *__restrict__ out)
-{
-	const int i = blockIdx.x * 256 + threadIdx.x;
-	if (i >= n) return;
-	const int na = n_aln[i];
-	const uint4 *src = rows_of(i, aln, aln_cap, status, wide_idx, aln2, aln_cap2, grown);
-	uint4 *dst = out + row_off[i];
-	for (int j = 0; j < na; ++j) dst[j] = src[j];
-}
-
-extern "C" void nabwa_launch_gather(int n, const int32_t *n_aln, const uint32_t *row_off, const uint4 *aln, int aln_cap,
-									const uint8_t *status, const int32_t *wide_idx, const uint4 *aln2, int aln_cap2,
-									const uint4 *const *grown, uint4 *out, hipStream_t s)
-{
-	if (n <= 0) return;
-	hipLaunchKernelGGL(gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, n_aln, row_off, aln, aln_cap, status,
-					   wide_idx, aln2, aln_cap2, grown, out);
-}
-
-// order-independent checksum over all hits: sum of a mix of (read, row index, row words)
-__device__ __forceinline__ uint64_t mix64(uint64_t x)
-{
-	x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-	return x;
-}
-
-__global__ __launch_bounds__(256) void checksum_kernel(int n, const int32_t *__restrict__ n_aln, const uint4 *__restrict__ aln,
-												   int aln_cap, const uint8_t *__restrict__ status, const int32_t *__restrict__ wide_idx,
-												   const uint4 *__restrict__ aln2, int aln_cap2, const uint4 *const *__restrict__ grown,
-												   unsigned long long *__restrict__ sum, unsigned long long *__restrict__ rows)
-{
-	const int i = blockIdx.x * 256 + threadIdx.x;
-	uint64_t s = 0, r = 0;
-	if (i < n) {
-		const int na = n_aln[i];
-		const uint4 *src = rows_of(i, aln, aln_cap, status, wide_idx, aln2, aln_cap2, grown);
-		r = (uint64_t)na;
-		s = mix64(((uint64_t)i << 20) ^ (uint64_t)na ^ 0x9e3779b97f4a7c15ULL);
-		for (int j = 0; j < na; ++j) {
-			const uint4 h = src[j];
-			s += mix64(((uint64_t)i << 32 | (uint32_t)j) ^ mix64((uint64_t)h.x << 32 | h.y) ^ mix64((uint64_t)h.z << 32 | h.w) * 3ULL);
-		}
-	}
-	for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o); r += __shfl_down(r, o); }
-	if ((threadIdx.x & 63) == 0) { atomicAdd(sum, (unsigned long long)s); atomicAdd(rows, (unsigned long long)r); }
-}
-
-extern "C" void nabwa_launch_checksum(int n, const int32_t *n_aln, const uint4 *aln, int aln_cap, const uint8_t *status,
-									  const int32_t *wide_idx, const uint4 *aln2, int aln_cap2,
-									  const uint4 *const *grown, unsigned long long *sum, unsigned long long *rows, hipStream_t s)
-{
-	if (n <= 0) return;
-	hipLaunchKernelGGL(checksum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, n_aln, aln, aln_cap, status, wide_idx,
-					   aln2, aln_cap2, grown, sum, rows);
-}
-
-// Work order of the search kernel by kernel W's class of a read = the smaller of its two strands' restart counts, i.e. a
-// lower bound of the differences of its best hit: 0 (an exact occurrence exists), 1, 2+.  A search can take 10^4 dependent
-// trips (tens of ms; the launch cannot end before its longest search does), so the long searches must START first:
-// order 2+, 1, 0.  Class 0 reads run alike and close the launch in lockstep waves (64 reads at a time); the others go lane
-// by lane.  (Tried: class 1 in lockstep waves -- its reads differ too much; a finer order 4+, 3, 2, 1, 0 -- the few hundred
-// longest searches then sit in ONE wave's first block and run one after the other; those reads one per wave, or their waves
-// at raised issue priority -- a trip is no shorter for it.  Mixed into the 2+ class they start in ~650 different waves at once.)
-// cnt: [0..2] class sizes (pass 1), [5..7] cursors (pass 2), [10] = first work item of class 0 (*n_sync of the search
-// kernel).  One wave handles 1024 consecutive reads with one atomic per class.
-#define NABWA_N_CLASS 3
-template <int PASS>
-__global__ __launch_bounds__(256) void partition_kernel(int n, const uint8_t *__restrict__ cls, int32_t *__restrict__ ids, unsigned int *__restrict__ cnt)
-{
-	const unsigned int lane = threadIdx.x & 63u;
-	const long wave = ((long)blockIdx.x * 256 + threadIdx.x) >> 6;
-	const long first = wave * 1024;
-	if (PASS == 2 && blockIdx.x == 0 && threadIdx.x == 0) { unsigned int x = 0; for (int q = 1; q < NABWA_N_CLASS; ++q) x += cnt[q]; cnt[10] = x; }
-	if (first >= n) return;
-	unsigned int num[NABWA_N_CLASS]; int cl[16];
-#pragma unroll
-	for (int q = 0; q < NABWA_N_CLASS; ++q) num[q] = 0;
-#pragma unroll
-	for (int g = 0; g < 16; ++g) {
-		const long i = first + g * 64 + lane;
-		const uint8_t c0 = i < n ? cls[2 * i] : 0, c1 = i < n ? cls[2 * i + 1] : 0;
-		cl[g] = i < n ? (int)(c0 < c1 ? c0 : c1) : -1;
-		if (cl[g] > NABWA_N_CLASS - 1) cl[g] = NABWA_N_CLASS - 1;
-#pragma unroll
-		for (int q = 0; q < NABWA_N_CLASS; ++q) num[q] += (unsigned int)__popcll(__ballot(cl[g] == q));
-	}
-	if (PASS == 1) {
-		if (lane == 0) for (int q = 0; q < NABWA_N_CLASS; ++q) if (num[q]) atomicAdd(cnt + q, num[q]);
-		return;
-	}
-	unsigned int base[NABWA_N_CLASS];
-#pragma unroll
-	for (int q = 0; q < NABWA_N_CLASS; ++q) base[q] = 0;
-	if (lane == 0) {
-		unsigned int start = 0;
-		for (int q = NABWA_N_CLASS - 1; q >= 0; --q) { if (num[q]) base[q] = start + atomicAdd(cnt + 5 + q, num[q]); start += cnt[q]; }
-	}
-#pragma unroll
-	for (int q = 0; q < NABWA_N_CLASS; ++q) base[q] = __shfl(base[q], 0);
-#pragma unroll
-	for (int g = 0; g < 16; ++g) {
-		const long i = first + g * 64 + lane;
-		const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-		for (int q = 0; q < NABWA_N_CLASS; ++q) {
-			const unsigned long long mq = __ballot(cl[g] == q);
-			if (cl[g] == q) ids[base[q] + (unsigned int)__popcll(mq & below)] = (int32_t)i;
-			base[q] += (unsigned int)__popcll(mq);
-		}
-	}
-}
-
-extern "C" void nabwa_launch_partition(int n, const uint8_t *cls, int32_t *ids, unsigned int *cnt, hipStream_t s)
-{
-	if (n <= 0) return;
-	hipLaunchKernelGGL(partition_kernel<1>, dim3((n + 4095) / 4096), dim3(256), 0, s, n, cls, ids, cnt);
-	hipLaunchKernelGGL(partition_kernel<2>, dim3((n + 4095) / 4096), dim3(256), 0, s, n, cls, ids, cnt);
 }

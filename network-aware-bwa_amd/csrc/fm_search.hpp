@@ -2,6 +2,7 @@
 #pragma once
 #include <stdint.h>
 #include "nabwa_dev.hpp"
+#include "search_slots.hpp"
 
 #define NABWA_SEARCH_BLOCK 256
 #define NABWA_ST_OK        0
@@ -40,7 +41,7 @@ struct SearchParams {
 	uint8_t *status;
 	uint4 *aln;
 	int aln_cap;
-	unsigned int *work_counter;               // [0] kernel S, [1] kernel W
+	unsigned int *work_counter;               // WC_* (search_slots.hpp)
 	uint32_t trip_budget;                     // kernel S: trips after which a search is handed on to kernel D (0: never)
 	uint32_t trip_budget_hard;                // ... in a batch most of whose reads have no exact occurrence on either strand (*n_sync > n / 2: the searches are kernel D's kind)
 	int sync_refill;                          // experiment knob (NABWA_SYNC_REFILL): every wave refills only when all its lanes are idle
@@ -48,14 +49,13 @@ struct SearchParams {
 	int w_sync;                               // kernel W: lockstep waves (all reads of the batch have one length)
 	int w_skip_clean;                         // kernel W run again over the reads kernel S handed on: a search that found no hit has not edited its record (gap_shadow, bwtgap.c:81-91) -- n_aln[read] == 0: nothing to rebuild
 	uint8_t *rd_cls;                          // kernel W -> partition: per strand the restarts of its width pass, clipped to 4
-	const unsigned int *n_sync;               // work items from *n_sync on are class-0 reads: their waves run in lockstep (see fm_search_kernel, partition_kernel)
-	unsigned long long *touch_counter;        // non-null: also count the reference algorithm's bucket touches
+	const unsigned int *n_sync;               // slot NCLS_FIRST0 of the class counter block (search_slots.hpp): work items from *n_sync on are class-0 reads, their waves run in lockstep (see fm_search_kernel, partition_kernel)
+	unsigned long long *touch_counter;        // non-null: also count the reference algorithm's bucket touches, and the trips by kind: TS_* (search_slots.hpp)
 	const uint32_t *ixtab;                    // NABWA_IXTAB_WORDS words (device): per index what a lane picks by the strand of its entry -- see below
 	int sure0;                                // kernel S, with rd_cls set (NABWA_SURE0): 0 off; 1: a read one of whose strands occurs exactly stores no entry that cannot be popped and
 	                                          // resolves its 1-mismatch key-form children where they are created; 2: it also stores the surviving ones landed at depth KT;
 	                                          // 3: also the leap -- a text-form entry that is the read's own prefix on a strand whose class byte is 0 is replaced by its hit
-	unsigned long long *s0_stats;             // non-null (NABWA_SURE0_STATS): [0] such reads, [1] key-form children whose level-KT entry was empty, [2] children stored landed, [3] reads handed to kernel D by the safety net,
-	                                          // [4] leaps taken, [5] levels leapt over, [6] proven entries that walked instead (text position < levels left), [7] unused: eight words
+	unsigned long long *s0_stats;             // non-null (NABWA_SURE0_STATS): what became of such reads, S0S_* (search_slots.hpp)
 };
 
 /* The per-index constants a lane of kernel D selects by its entry's strand, as a table the kernel copies into LDS (fm_deep_body.hpp): as

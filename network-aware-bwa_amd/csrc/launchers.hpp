@@ -1,4 +1,4 @@
-// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, fm_deep.hip and bgzf_deflate.hip, declared once.
+// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip and bgzf_deflate.hip, declared once.
 // The defining files and every host unit that calls one include this header, so a parameter list that differs between the two sides
 // is a compile error (C linkage carries no types).  Host side only: the kernel headers (nabwa_dev.hpp, fm_search.hpp, fm_deep.hpp,
 // fm_deep_body.hpp) do not include it -- the CPU emulation of the tests compiles those without HIP.
@@ -19,6 +19,7 @@ void nabwa_launch_fm_search(const SearchParams *P, int n_blocks, hipStream_t s);
 void nabwa_launch_fm_width(const SearchParams *P, int n_blocks, hipStream_t s);
 int nabwa_width_occupancy(void);
 int nabwa_search_occupancy(int ns);
+/* batch_kernels.hip */
 void nabwa_launch_checksum(int n, const int32_t *n_aln, const uint4 *aln, int aln_cap, const uint8_t *status,
 						   const int32_t *wide_idx, const uint4 *aln2, int aln_cap2, const uint4 *const *grown,
 						   unsigned long long *sum, unsigned long long *rows, hipStream_t s);

@@ -130,7 +130,7 @@ static int upload_reads(nabwa_batch *b, const BatchShape &s, const int64_t *off,
 	HIP_CHECK(b->d_md.get(ix, n ? n : 1)); HIP_CHECK(b->d_mg.get(ix, n ? n : 1)); HIP_CHECK(b->d_key.get(ix, (size_t)(n ? n : 1) * 24));
 	b->pack_stride = 2 * ((max_len + 15) / 16 + 2);
 	HIP_CHECK(b->d_pack.get(ix, (size_t)(n ? n : 1) * b->pack_stride * 4));
-	HIP_CHECK(b->d_cls.get(ix, (size_t)(n ? n : 1) * 2)); HIP_CHECK(b->d_perm.get(ix, (size_t)(n ? n : 1) * 4)); HIP_CHECK(b->d_ncls.get(ix, 64));
+	HIP_CHECK(b->d_cls.get(ix, (size_t)(n ? n : 1) * 2)); HIP_CHECK(b->d_perm.get(ix, (size_t)(n ? n : 1) * 4)); HIP_CHECK(b->d_ncls.get(ix, NCLS_WORDS * sizeof(unsigned int)));
 	if (n == 0) { HIP_CHECK(hipMemset(b->d_poff, 0, 8)); return NABWA_OK; }
 	PoolBuf<uint8_t> raw_s, raw_r, d_tab; PoolBuf<int64_t> raw_off, plen; PoolBuf<void> d_tmp; size_t tmp_bytes = 0;
 	StreamDrain drain{ b->stream };
@@ -202,8 +202,8 @@ static int working_buffers(nabwa_batch *b, const BatchShape &s)
 	if (P.sure0 < 0) P.sure0 = 0;
 	if (P.sure0 > 3) P.sure0 = 3;
 	if (env_int("NABWA_SURE0_STATS", 0)) {
-		HIP_CHECK(b->d_s0stats.get(ix, 64));
-		HIP_CHECK(hipMemset(b->d_s0stats, 0, 64));
+		HIP_CHECK(b->d_s0stats.get(ix, S0S_WORDS * sizeof(unsigned long long)));
+		HIP_CHECK(hipMemset(b->d_s0stats, 0, S0S_WORDS * sizeof(unsigned long long)));
 		P.s0_stats = b->d_s0stats;
 	}
 	{
@@ -236,8 +236,8 @@ static int working_buffers(nabwa_batch *b, const BatchShape &s)
 	const size_t n1 = n ? n : 1;
 	HIP_CHECK(b->d_naln.get(ix, n1 * 4)); HIP_CHECK(b->d_maxent.get(ix, n1 * 4)); HIP_CHECK(b->d_wide_idx.get(ix, n1 * 4));
 	HIP_CHECK(b->d_status.get(ix, n1)); HIP_CHECK(b->d_aln.get(ix, n1 * (size_t)P.aln_cap * 16));
-	HIP_CHECK(b->d_counter.get(ix, 16)); HIP_CHECK(b->d_novf.get(ix, 4)); HIP_CHECK(b->d_ovf_ids.get(ix, n1 * 4));
-	HIP_CHECK(b->d_sum.get(ix, 256));
+	HIP_CHECK(b->d_counter.get(ix, WC_WORDS * sizeof(unsigned int))); HIP_CHECK(b->d_novf.get(ix, 4)); HIP_CHECK(b->d_ovf_ids.get(ix, n1 * 4));
+	HIP_CHECK(b->d_sum.get(ix, TS_WORDS * sizeof(unsigned long long)));
 	P.scratch = b->d_scratch; P.n_aln = b->d_naln; P.max_ent = b->d_maxent; P.status = b->d_status; P.aln = b->d_aln;
 	P.work_counter = b->d_counter;
 	return NABWA_OK;
@@ -283,17 +283,17 @@ extern "C" int nabwa_batch_run(nabwa_batch_t *b)
 		for (int t = 0; t < b->n_grown; ++t) HIP_CHECK(b->grown[t].release());
 		b->n_grown = 0; b->grown_used = 0;
 	}
-	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
+	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, WC_WORDS * sizeof(unsigned int), b->stream));
 	HIP_CHECK(hipMemsetAsync(b->d_novf, 0, 4, b->stream));
 	HIP_CHECK(hipEventRecord(b->evw, b->stream));
 	SearchParams PW = b->P; PW.ids = 0; PW.rd_cls = b->class_sort ? b->d_cls : 0;
 	nabwa_launch_fm_width(&PW, b->n_blocks_w, b->stream);
 	if (b->class_sort) {      /* work order of the search: reads with an exact occurrence first, in lockstep waves */
-		HIP_CHECK(hipMemsetAsync(b->d_ncls, 0, 64, b->stream));
+		HIP_CHECK(hipMemsetAsync(b->d_ncls, 0, NCLS_WORDS * sizeof(unsigned int), b->stream));
 		nabwa_launch_partition(b->n, b->d_cls, b->d_perm, b->d_ncls, b->stream);
 	}
 	HIP_CHECK(hipEventRecord(b->ev0, b->stream));
-	SearchParams PS = b->P; PS.ids = b->class_sort ? b->d_perm : 0; PS.n_sync = b->class_sort ? b->d_ncls + 10 : 0;
+	SearchParams PS = b->P; PS.ids = b->class_sort ? b->d_perm : 0; PS.n_sync = b->class_sort ? b->d_ncls + NCLS_FIRST0 : 0;
 	PS.rd_cls = b->class_sort ? b->d_cls : 0;      /* (this launch only: the re-runs over handed-on reads search without the shortcut) */
 	if (!b->deep_only) nabwa_launch_fm_search(&PS, b->n_blocks, b->stream);
 	else {      /* option blocks the first-pass kernel's compact entries cannot hold: every read goes to kernel D */
@@ -322,7 +322,7 @@ void rebuild_widths(nabwa_batch *b, const SearchParams &Q, unsigned int cnt, boo
 	QW.n_aln = b->d_naln; QW.max_ent = b->d_maxent; QW.status = b->d_status; QW.aln = b->d_aln; QW.aln_cap = b->P.aln_cap;
 	long bw2 = (2 * (long)cnt + NABWA_SEARCH_BLOCK - 1) / NABWA_SEARCH_BLOCK;     /* one lane per strand */
 	if (bw2 > b->n_blocks_w) bw2 = b->n_blocks_w;
-	(void)hipMemsetAsync(b->d_counter, 0, 16, b->stream);       /* kernel W draws its work items from counter [1] */
+	(void)hipMemsetAsync(b->d_counter, 0, WC_WORDS * sizeof(unsigned int), b->stream);       /* kernel W draws its work items from WC_WIDTH */
 	nabwa_launch_fm_width(&QW, (int)bw2, b->stream);
 }
 
@@ -355,7 +355,7 @@ static int tier_a_rerun(nabwa_batch *b, unsigned int *cur, bool timing)
 	}
 	Q.scratch = b->d_scratch2; Q.ids = b->d_ovf_ids; Q.n = (int)*cur; Q.n_sync = 0; Q.w_sync = 0;
 	rebuild_widths(b, Q, *cur, false);
-	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
+	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, WC_WORDS * sizeof(unsigned int), b->stream));
 	nabwa_launch_fm_search(&Q, (int)blocks, b->stream);
 	HIP_CHECK(hipGetLastError());
 	unsigned int left = 0;
@@ -396,7 +396,7 @@ extern "C" int nabwa_batch_count_touches(nabwa_batch_t *b, uint64_t *n_bucket, u
 {
 	if (!b || !n_bucket) return nabwa_fail(NABWA_EINVAL, "null argument");
 	HIP_CHECK(hipSetDevice(b->ix->device));
-	HIP_CHECK(hipMemsetAsync(b->d_sum, 0, 256, b->stream));
+	HIP_CHECK(hipMemsetAsync(b->d_sum, 0, TS_WORDS * sizeof(unsigned long long), b->stream));
 	b->P.touch_counter = b->d_sum;
 	/* the reference walks every exact tail row by row: count with the tail jump off (NABWA_TRIP_STATS=jump keeps it
 	 * on to profile the production trips; the touch totals are then not the reference's) */
@@ -408,22 +408,21 @@ extern "C" int nabwa_batch_count_touches(nabwa_batch_t *b, uint64_t *n_bucket, u
 	b->P.touch_counter = 0;
 	b->P.bwt[0].kmer_T = kt0; b->P.bwt[1].kmer_T = kt1; b->P.text_mode = tm0;
 	if (r != NABWA_OK) return r;
-	unsigned long long v[2] = { 0, 0 };
-	HIP_CHECK(hipMemcpy(v, b->d_sum, 16, hipMemcpyDeviceToHost));
-	*n_bucket = v[0];                          /* search kernel (bwt_match_gap) */
-	if (n_bucket_width) *n_bucket_width = v[1];  /* width kernel (bwt_cal_width) */
+	unsigned long long t[TS_WORDS];
+	HIP_CHECK(hipMemcpy(t, b->d_sum, sizeof t, hipMemcpyDeviceToHost));
+	*n_bucket = t[TS_TOUCH_S];                          /* search kernel (bwt_match_gap) */
+	if (n_bucket_width) *n_bucket_width = t[TS_TOUCH_W];  /* width kernel (bwt_cal_width) */
 	if (getenv("NABWA_TRIP_STATS") && b->class_sort) {
-		unsigned int c[12];
-		HIP_CHECK(hipMemcpy(c, b->d_ncls, 48, hipMemcpyDeviceToHost));
-		fprintf(stderr, "[nabwa] read classes by restarts 0 / 1 / 2+: %u / %u / %u\n", c[0], c[1], c[2]);
+		unsigned int c[NCLS_WORDS];
+		HIP_CHECK(hipMemcpy(c, b->d_ncls, sizeof c, hipMemcpyDeviceToHost));
+		fprintf(stderr, "[nabwa] read classes by restarts 0 / 1 / 2+: %u / %u / %u\n", c[NCLS_SIZE + 0], c[NCLS_SIZE + 1], c[NCLS_SIZE + 2]);
 	}
 	if (getenv("NABWA_TRIP_STATS")) {
-		unsigned long long t[32];
-		HIP_CHECK(hipMemcpy(t, b->d_sum, 256, hipMemcpyDeviceToHost));
 		fprintf(stderr, "[nabwa] search kernel: wave-trips %llu; lane-trips: expand %llu exact %llu entry-load %llu spec %llu query %llu two-bucket %llu exited %llu tail-jump %llu text-expand %llu text-tail %llu; longest read %llu trips, %llu reads over 2000 trips, %llu over 500\n",
-				t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], t[15]);
+				t[TS_TRIPS], t[TS_EXPAND], t[TS_EXACT], t[TS_ENT_LOAD], t[TS_SPEC], t[TS_QUERY], t[TS_TWO], t[TS_EXITED], t[TS_JUMP], t[TS_TEXT_EXPAND], t[TS_TEXT_TAIL],
+				t[TS_MAX_TRIPS], t[TS_OVER_2000], t[TS_OVER_500]);
 		fprintf(stderr, "[nabwa] the %llu reads over 8000 trips: %llu trips = expansions key-form %llu, rows two-bucket %llu, rows one-bucket %llu, text %llu (of all: %llu with gaps); pops %llu, tail steps %llu, jumps %llu\n",
-				t[16], t[17], t[18], t[19], t[20], t[21], t[25], t[22], t[23], t[24]);
+				t[TS_LONG_READS], t[TS_LONG_TRIPS], t[TS_LONG_KF], t[TS_LONG_ROW2], t[TS_LONG_ROW1], t[TS_LONG_TEXT], t[TS_LONG_GAP], t[TS_LONG_POP], t[TS_LONG_TAIL], t[TS_LONG_JUMP]);
 	}
 	return NABWA_OK;
 }
@@ -436,7 +435,7 @@ extern "C" int nabwa_batch_width_records(nabwa_batch_t *b, int first, int n, uin
 	if (!b || first < 0 || n < 0 || first + n > b->n || (n && (!w_out || !bid_out))) return nabwa_fail(NABWA_EINVAL, "bad argument");
 	if (n == 0) return NABWA_OK;
 	HIP_CHECK(hipSetDevice(b->ix->device));
-	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
+	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, WC_WORDS * sizeof(unsigned int), b->stream));
 	SearchParams PW = b->P; PW.ids = 0; PW.rd_cls = 0; PW.touch_counter = 0;
 	nabwa_launch_fm_width(&PW, b->n_blocks_w, b->stream);
 	HIP_CHECK(hipGetLastError());
@@ -459,14 +458,14 @@ extern "C" int nabwa_batch_checksum(nabwa_batch_t *b, uint64_t *sum, int64_t *n_
 {
 	if (!b) return nabwa_fail(NABWA_EINVAL, "null batch");
 	HIP_CHECK(hipSetDevice(b->ix->device));
-	unsigned long long h[2] = { 0, 0 };
-	HIP_CHECK(hipMemsetAsync(b->d_sum, 0, 16, b->stream));
+	unsigned long long h[CKS_WORDS] = { 0, 0 };
+	HIP_CHECK(hipMemsetAsync(b->d_sum, 0, sizeof h, b->stream));
 	nabwa_launch_checksum(b->n, b->d_naln, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
-						  b->d_sum, b->d_sum + 1, b->stream);
-	HIP_CHECK(hipMemcpyAsync(h, b->d_sum, 16, hipMemcpyDeviceToHost, b->stream));
+						  b->d_sum + CKS_SUM, b->d_sum + CKS_ROWS, b->stream);
+	HIP_CHECK(hipMemcpyAsync(h, b->d_sum, sizeof h, hipMemcpyDeviceToHost, b->stream));
 	HIP_CHECK(hipStreamSynchronize(b->stream));
-	if (sum) *sum = h[0];
-	if (n_rows) *n_rows = (int64_t)h[1];
+	if (sum) *sum = h[CKS_SUM];
+	if (n_rows) *n_rows = (int64_t)h[CKS_ROWS];
 	return NABWA_OK;
 }
 
@@ -478,47 +477,38 @@ extern "C" int nabwa_batch_config(nabwa_batch_t *b, nabwa_batch_config_t *out)
 	out->deep_only = b->deep_only; out->ns1 = (int32_t)b->NS1; out->ns_wide = (int32_t)b->NS_wide;
 	out->w_sync = b->P.w_sync; out->trip_budget = (int32_t)b->P.trip_budget; out->trip_budget_hard = (int32_t)b->P.trip_budget_hard;
 	out->n_sync = out->hard_budget = -1;
-	for (int q = 0; q < 3; ++q) out->cls[q] = -1;
+	for (int q = 0; q < NCLS_N; ++q) out->cls[q] = -1;
 	if (b->ran && b->class_sort) {
 		HIP_CHECK(hipSetDevice(b->ix->device));
-		unsigned int c[12];
-		HIP_CHECK(hipMemcpyAsync(c, b->d_ncls, 48, hipMemcpyDeviceToHost, b->stream));
+		unsigned int c[NCLS_WORDS];
+		HIP_CHECK(hipMemcpyAsync(c, b->d_ncls, sizeof c, hipMemcpyDeviceToHost, b->stream));
 		HIP_CHECK(hipStreamSynchronize(b->stream));
-		for (int q = 0; q < 3; ++q) out->cls[q] = (int32_t)c[q];
-		out->n_sync = (int32_t)c[10];
+		for (int q = 0; q < NCLS_N; ++q) out->cls[q] = (int32_t)c[NCLS_SIZE + q];
+		out->n_sync = (int32_t)c[NCLS_FIRST0];
 		/* the rule of fm_search_kernel: the hard budget when most reads occur exactly on neither strand */
-		if (!b->deep_only) out->hard_budget = b->P.trip_budget_hard && 2u * c[10] > (uint32_t)b->n ? 1 : 0;
+		if (!b->deep_only) out->hard_budget = b->P.trip_budget_hard && 2u * c[NCLS_FIRST0] > (uint32_t)b->n ? 1 : 0;
 	}
 	out->coop_lanes = b->deep_coop;
 	out->lds_rd = b->deep_cfg ? (int32_t)b->deep_lds_rd : -1;
 	return NABWA_OK;
 }
 
-extern "C" int nabwa_batch_sure0_stats(nabwa_batch_t *b, uint64_t out[4])
+/* the first n_words slots of the sure0 block (S0S_*, search_slots.hpp); zeros when NABWA_SURE0_STATS was not set at batch_create */
+static int sure0_read(nabwa_batch_t *b, uint64_t *out, int n_words)
 {
 	if (!b || !out) return nabwa_fail(NABWA_EINVAL, "null argument");
-	for (int q = 0; q < 4; ++q) out[q] = 0;
+	for (int q = 0; q < n_words; ++q) out[q] = 0;
 	if (!b->d_s0stats) return NABWA_OK;
 	HIP_CHECK(hipSetDevice(b->ix->device));
-	unsigned long long v[4];
-	HIP_CHECK(hipMemcpyAsync(v, b->d_s0stats, 32, hipMemcpyDeviceToHost, b->stream));
+	unsigned long long v[S0S_WORDS];
+	HIP_CHECK(hipMemcpyAsync(v, b->d_s0stats, (size_t)n_words * sizeof v[0], hipMemcpyDeviceToHost, b->stream));
 	HIP_CHECK(hipStreamSynchronize(b->stream));
-	for (int q = 0; q < 4; ++q) out[q] = v[q];
+	for (int q = 0; q < n_words; ++q) out[q] = v[q];
 	return NABWA_OK;
 }
 
-extern "C" int nabwa_batch_sure0_stats_ex(nabwa_batch_t *b, uint64_t out[8])
-{
-	if (!b || !out) return nabwa_fail(NABWA_EINVAL, "null argument");
-	for (int q = 0; q < 8; ++q) out[q] = 0;
-	if (!b->d_s0stats) return NABWA_OK;
-	HIP_CHECK(hipSetDevice(b->ix->device));
-	unsigned long long v[8];
-	HIP_CHECK(hipMemcpyAsync(v, b->d_s0stats, 64, hipMemcpyDeviceToHost, b->stream));
-	HIP_CHECK(hipStreamSynchronize(b->stream));
-	for (int q = 0; q < 8; ++q) out[q] = v[q];
-	return NABWA_OK;
-}
+extern "C" int nabwa_batch_sure0_stats(nabwa_batch_t *b, uint64_t out[4]) { return sure0_read(b, out, 4); }      /* the first entry of the ABI: four words, S0S_READS .. S0S_NET */
+extern "C" int nabwa_batch_sure0_stats_ex(nabwa_batch_t *b, uint64_t out[8]) { return sure0_read(b, out, S0S_WORDS); }
 
 extern "C" int nabwa_batch_fetch(nabwa_batch_t *b, int32_t *n_aln, nabwa_aln1_t *aln_out, int64_t aln_cap, int64_t *n_rows,
 								 int32_t *max_entries)

@@ -86,7 +86,7 @@ static int deep_grow_buffers(nabwa_batch *b, long n_waves)
 		HIP_CHECK(b->d_deep_stage.release());
 		HIP_CHECK(b->d_deep_stage.get(b->ix, stage_ent * 16)); b->deep_stage_ent = stage_ent;
 	}
-	if (!b->d_deep_ctr) HIP_CHECK(b->d_deep_ctr.get(b->ix, 1024));
+	if (!b->d_deep_ctr) HIP_CHECK(b->d_deep_ctr.get(b->ix, DS_WORDS * sizeof(unsigned long long)));
 	return NABWA_OK;
 }
 
@@ -98,7 +98,7 @@ static void deep_fill_params(nabwa_batch *b, DeepParams &D, bool stats)
 	D.S.ids = b->d_ovf_ids; D.S.n_sync = 0; D.S.w_sync = 0; D.S.res_slot = b->d_wide_idx;
 	D.S.n_aln = b->d_naln2; D.S.max_ent = b->d_maxent2; D.S.status = b->d_status2; D.S.aln = b->d_aln2; D.S.aln_cap = b->aln_cap2;
 	D.pages = b->d_pages; D.page_prev = b->d_page_prev; D.n_pages = (uint32_t)b->deep_n_pages;
-	D.page_bump = (unsigned int*)(b->d_deep_ctr + 8);
+	D.page_bump = (unsigned int*)(b->d_deep_ctr + DS_PAGE_BUMP);
 	D.own = b->d_deep_own; D.own_cap = (uint32_t)b->deep_cap_pages; D.stage = b->d_deep_stage; D.stage_k = b->deep_K;
 	D.NS = b->NS_wide; D.lds_rd = b->deep_lds_rd; D.rd_pl = b->deep_rd_pl;
 	D.careful_all = env_int("NABWA_DEEP_CAREFUL", 0); D.max_lanes = env_int("NABWA_DEEP_LANES", 64);
@@ -131,8 +131,8 @@ static int deep_launch(nabwa_batch *b, DeepParams &D, unsigned int n_reads, long
 	const bool grown = !D.S.res_slot;
 	D.S.n = (int)n_reads;
 	rebuild_widths(b, D.S, n_reads, first);
-	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, 16, b->stream));
-	HIP_CHECK(hipMemsetAsync(b->d_deep_ctr, 0, 1024, b->stream));
+	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, WC_WORDS * sizeof(unsigned int), b->stream));
+	HIP_CHECK(hipMemsetAsync(b->d_deep_ctr, 0, DS_WORDS * sizeof(unsigned long long), b->stream));
 	D.S.work_counter = b->d_counter;
 	if (first) HIP_CHECK(hipEventRecord(b->evd0, b->stream));
 	nabwa_launch_fm_deep(&D, (int)waves, b->stream);
@@ -147,25 +147,26 @@ static int deep_launch(nabwa_batch *b, DeepParams &D, unsigned int n_reads, long
 	return recollect(b, grown ? NABWA_ST_HITCAP : NABWA_ST_POOL, left);
 }
 
-/* kernel D's statistics of one launch (st: its 128 counters), as NABWA_TIMING prints them */
+/* kernel D's statistics of one launch (st: its DS_WORDS counters, search_slots.hpp), as NABWA_TIMING prints them */
 static void deep_print_stats(const unsigned long long *st, int hist, bool guaranteed, unsigned int todo, long waves, size_t n_pages, unsigned int n_pool, double secs)
 {
 	fprintf(stderr, "[nabwa] kernel D%s: %u reads on %ld waves (%zu pages of 4 KB, %u handed out), %u left for the guaranteed pass, %.3f s; rounds %llu, chains run %llu / committed %llu, wave-steps %llu, careful rounds %llu, exact tails: %llu rank steps, %llu finished by text; longest read %.3f s / %llu rounds, all reads %.1f wave-s, longest wave %.3f s\n",
-			guaranteed ? " (guaranteed pass)" : "", todo, waves, n_pages, (unsigned int)(st[8] & 0xffffffffu), n_pool, secs, st[0], st[1], st[2], st[3], st[4], st[6], st[7], st[10] * 1e-8, st[11], st[12] * 1e-8, st[13] * 1e-8);
+			guaranteed ? " (guaranteed pass)" : "", todo, waves, n_pages, (unsigned int)(st[DS_PAGE_BUMP] & 0xffffffffu), n_pool, secs, st[DS_ROUNDS], st[DS_CHAINS_RUN], st[DS_CHAINS_DONE], st[DS_STEPS], st[DS_CAREFUL], st[DS_TAIL_RANK], st[DS_TAIL_TEXT],
+			st[DS_MAX_CLK] * 1e-8, st[DS_MAX_ROUNDS], st[DS_SUM_CLK] * 1e-8, st[DS_WAVE_CLK] * 1e-8);
 	fprintf(stderr, "[nabwa] kernel D phases (wave-s): pop %.1f, chains %.1f, exact tails %.1f (%llu turns), commit %.1f, hit bookkeeping %.1f; active lanes per chain step %.1f\n",
-			st[16] * 1e-8, st[17] * 1e-8, st[18] * 1e-8, st[21], st[19] * 1e-8, st[20] * 1e-8, st[3] ? (double)st[22] / (double)st[3] : 0.0);
+			st[DS_PH_POP] * 1e-8, st[DS_PH_CHAIN] * 1e-8, st[DS_PH_TAIL] * 1e-8, st[DS_TAIL_TURNS], st[DS_PH_COMMIT] * 1e-8, st[DS_PH_HIT] * 1e-8, st[DS_STEPS] ? (double)st[DS_LANE_STEPS] / (double)st[DS_STEPS] : 0.0);
 	fprintf(stderr, "[nabwa] kernel D lane-steps %llu: pruned at the pop %llu, expansions %llu (in key form %llu, on two buckets %llu), records %llu, children stored %llu; key-form tails / hits %llu; expansions without a difference allowed: %llu in key form, %llu on one row, %llu on several\n",
-			st[22], st[27], st[28], st[23], st[29], st[25], st[26], st[24], st[30], st[31], st[9]);
+			st[DS_LANE_STEPS], st[DS_PRUNED], st[DS_EXPAND], st[DS_KEY_EXPAND], st[DS_TWO], st[DS_RECORDS], st[DS_CHILDREN], st[DS_KEY_TAIL], st[DS_FORCED_KEY], st[DS_FORCED_ONE], st[DS_FORCED_ROWS]);
 	if (hist == 2) {
 		fprintf(stderr, "[nabwa] kernel D rounds by width (1, 2, 3-4, 5-8, 9-16, 17-32, 33-64 entries):");
-		for (int d = 0; d < 7; ++d) fprintf(stderr, " %llu", st[32 + d]);
+		for (int d = 0; d < DS_HIST2_BINS; ++d) fprintf(stderr, " %llu", st[DS_HIST2_ROUNDS + d]);
 		fprintf(stderr, "; their wave-steps:");
-		for (int d = 0; d < 7; ++d) fprintf(stderr, " %llu", st[64 + d]);
+		for (int d = 0; d < DS_HIST2_BINS; ++d) fprintf(stderr, " %llu", st[DS_HIST2_STEPS + d]);
 		fprintf(stderr, "\n");
 	}
 	if (hist == 1) for (int h = 0; h < 3; ++h) {
 		fprintf(stderr, "[nabwa] kernel D expansions by depth (read symbols consumed), %s:", h == 0 ? "rows, several" : (h == 1 ? "rows, one" : "key form"));
-		for (int d = 0; d < 32; ++d) fprintf(stderr, " %llu", st[32 + 32 * h + d]);
+		for (int d = 0; d < DS_HIST1_BINS; ++d) fprintf(stderr, " %llu", st[DS_HIST1 + DS_HIST1_BINS * h + d]);
 		fprintf(stderr, "\n");
 	}
 }
@@ -293,8 +294,8 @@ int deep_searches(nabwa_batch *b, unsigned int cur, bool timing)
 		if (waves > (long)todo) waves = (long)todo;
 		if (int r = deep_launch(b, D, todo, waves, pass == 0, &n_pool)) return r;
 		if (timing) {
-			unsigned long long st[128];
-			HIP_CHECK(hipMemcpy(st, b->d_deep_ctr, 1024, hipMemcpyDeviceToHost));
+			unsigned long long st[DS_WORDS];
+			HIP_CHECK(hipMemcpy(st, b->d_deep_ctr, sizeof st, hipMemcpyDeviceToHost));
 			deep_print_stats(st, env_int("NABWA_DEEP_HIST", 0), pass == 1, todo, waves, n_pages, n_pool, now_s() - tt0);
 		}
 		if (pass == 0 && dump.path) {

@@ -149,8 +149,9 @@ struct emu_opt { int s_mm, s_gapo, s_gape, mode, indel_end_skip, max_del_occ, ma
 // knobs: [8] 1 = the read's own data in (emulated) LDS;  [0] max_lanes, [1] careful_all, [2] stage_k, [3] n_pages, [4] own_cap, [5] reads per wave (0: one wave takes all), [6] aln_cap,
 // [7] text mode (needs sa0 / sa1: the .sa / .rsa file contents; touches are then not the reference's), [9] depth of the interval tables for key-form entries (0: none; the
 // touch counter is then off, as in the product), [10] coop_lanes (DeepParams)
-// stats: 16 words -- 8 as in DeepParams, [8] the reference's bucket touches in the width passes, [9] in bwt_match_gap, [10] expansions in key form, [11] their tail jumps / hits,
-// [12] forced walks through the table, [13] forced walks on the text.  Returns 0.
+// stats: ES_WORDS = 16 words (search_slots.hpp) -- [0..7] kernel D's slots DS_ROUNDS .. DS_TAIL_TEXT, [8] the reference's bucket touches in the width passes, [9] in bwt_match_gap,
+// [10] expansions in key form, [11] their tail jumps / hits, [12] forced walks through the table, [13] forced walks on the text, [14] wave-wide expansions of one-row chains,
+// [15] the levels they took.  The emulated body fills [0..7] and [10..15] out of its DS_* counts.  Returns 0.
 extern "C" int emu_deep_search(const uint32_t *bwt0, const uint32_t *bwt1, const uint32_t *sa0, const uint32_t *sa1, const emu_opt *opt, int n, const int64_t *off,
 							   const uint8_t *seq, const uint8_t *rseq, int per_read, const int *knobs,
 							   int32_t *n_aln, uint32_t *rows /* n x aln_cap x 4 */, int32_t *max_ent, uint8_t *status,
@@ -236,6 +237,6 @@ extern "C" int emu_deep_search(const uint32_t *bwt0, const uint32_t *bwt1, const
 		else deep_wave_body<true, false, true>(P, (uint32_t*)(((uintptr_t)lds.data() + 15) & ~(uintptr_t)15), (uint32_t)w);
 		counter = (unsigned int)S.n;     /* (the wave's last, failed draw took a number: on the GPU all waves draw until the reads are gone) */
 	}
-	stats[8] = wt; stats[9] = st;
+	stats[ES_TOUCH_W] = wt; stats[ES_TOUCH_S] = st;
 	return 0;
 }

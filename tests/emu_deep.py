@@ -15,7 +15,7 @@ CSRC = os.path.join(T.ROOT, "network-aware-bwa_amd", "csrc")
 def build(asan=False):
     out = os.path.join(EMU_DIR, "libdeep_emu_asan.so" if asan else "libdeep_emu.so")
     srcs = [os.path.join(EMU_DIR, "deep_emu.cpp"), os.path.join(EMU_DIR, "emu_hip.hpp")] + [
-        os.path.join(CSRC, f) for f in ("fm_deep_body.hpp", "wave_spmd.hpp", "nabwa_dev.hpp", "fm_search.hpp")]
+        os.path.join(CSRC, f) for f in ("fm_deep_body.hpp", "wave_spmd.hpp", "nabwa_dev.hpp", "fm_search.hpp", "fm_deep.hpp", "search_slots.hpp")]
     if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs):
         return out
     flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if asan else ["-O2"]

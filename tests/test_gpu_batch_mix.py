@@ -157,7 +157,7 @@ def mix64(x):
 
 
 def host_checksum(n_aln, rows):
-    """what checksum_kernel (fm_search.hip) computes over fetched rows: sum over reads of a mix of (read, count, rows)"""
+    """what checksum_kernel (batch_kernels.hip) computes over fetched rows: sum over reads of a mix of (read, count, rows)"""
     with np.errstate(over="ignore"):
         n_aln = n_aln.astype(np.uint64)
         i = np.arange(len(n_aln), dtype=np.uint64)

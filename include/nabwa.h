@@ -26,6 +26,7 @@ extern "C" {
 #define NABWA_EHITS    -6   /* some reads have more hit rows than the device-side result rows can be grown to (NABWA_ALNCAP2 = 1024 rows, searched
                              again with 16 x, 256 x, 4096 x that within NABWA_HIT_GROW_GB = 8 GB): their n_aln is 0, every other read is resolved
                              and can be fetched */
+#define NABWA_EDATA    -7   /* BGZF input that is not BGZF, is cut short, or does not inflate to what its trailer says (nabwa_bgzf_decompress) */
 
 /* gap_opt_t -- identical layout to the reference's (bwtaln.h:143-153, 64 bytes); it is the
  * block `bwa worker` receives over the wire (bam2bam.c:1260-1263). */
@@ -576,8 +577,24 @@ int nabwa_pairing_typed(nabwa_pe_end_t p[2], int n_hits, uint64_t *hits, const n
  *                             than its slice + 31 bytes.
  * nabwa_bgzf_create / _handle_compress / _destroy: the same with a handle that keeps its stream, its device buffers and its pinned
  *                             staging buffers between calls (they grow to 1024 slices at most; longer inputs go through in chunks).
- *                             One call at a time per handle. */
+ *                             One call at a time per handle.
+ *
+ * The inverse (bgzf_inflate.hip): whole BGZF members back to back in, their inflated bytes out.  Any RFC 1951 payload is read (stored,
+ * fixed and dynamic blocks, several per member), not only what the compressor above writes; every member's length and CRC-32 are checked
+ * against its trailer on the device.
+ * nabwa_bgzf_inflated_size    host only, no device: walks the members' headers; the sum of ISIZE and the number of members (an empty
+ *                             end-of-file block is a member).  NABWA_EDATA for a header that is not BGZF, a BSIZE that points past n, a
+ *                             trailing partial member, or an ISIZE above 0x10000.
+ * nabwa_bgzf_decompress       NABWA_ECAP with *n_out = needed if cap is too small (decided on the host before anything is launched),
+ *                             NABWA_ENODEV without a device, NABWA_EDATA for what nabwa_bgzf_inflated_size refuses and for a member that
+ *                             does not inflate to what its trailer says: nabwa_last_error names the member's index, its byte offset and
+ *                             the reason.  On any error `out` may hold partial bytes.
+ * nabwa_bgzf_handle_decompress the same on a handle of nabwa_bgzf_create (device buffers that grow and stay; inputs that inflate to more
+ *                             than 256 MB go through in rounds of whole members).  One call at a time per handle, compress or decompress. */
 typedef struct nabwa_bgzf nabwa_bgzf_t;
+int nabwa_bgzf_inflated_size(const uint8_t *in, int64_t n, int64_t *n_out, int64_t *n_blocks);
+int nabwa_bgzf_decompress(int device, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
+int nabwa_bgzf_handle_decompress(nabwa_bgzf_t *z, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
 int64_t nabwa_bgzf_bound(int64_t n);
 int nabwa_bgzf_compress(int device, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
 int nabwa_bgzf_create(int device, nabwa_bgzf_t **out);

@@ -17,7 +17,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NABWA_LIB", os.path.join(_HERE, "libnabwa.so"))   # NABWA_LIB: A/B builds
 
-OK, ENODEV, EINVAL, EIO, ENOMEM, ECAP, EHITS = 0, -1, -2, -3, -4, -5, -6
+OK, ENODEV, EINVAL, EIO, ENOMEM, ECAP, EHITS, EDATA = 0, -1, -2, -3, -4, -5, -6, -7
 
 ALN_DT = np.dtype([("info", "<u4"), ("k", "<u4"), ("l", "<u4"), ("score", "<i4")])  # bwt_aln1_t, bwtaln.h:41-45
 
@@ -349,6 +349,9 @@ def lib():
     L.nabwa_bgzf_create.argtypes = [C.c_int, _P]
     L.nabwa_bgzf_handle_compress.argtypes = [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]
     L.nabwa_bgzf_destroy.argtypes = [_P]
+    L.nabwa_bgzf_inflated_size.argtypes = [_P, C.c_int64, _P, _P]
+    L.nabwa_bgzf_decompress.argtypes = [C.c_int, _P, C.c_int64, _P, C.c_int64, _P, _P]
+    L.nabwa_bgzf_handle_decompress.argtypes = [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]
     L.nabwa_bgzf_destroy.restype = None
     _lib = L
     return L
@@ -466,8 +469,26 @@ def bgzf_compress(data, device=0, cap=None):
     return _bgzf_call(lib().nabwa_bgzf_compress, int(device), data, cap)
 
 
+def bgzf_inflated_size(data):
+    """whole BGZF members back to back -> (inflated bytes, members), from their headers alone; needs no device.  NabwaError of code
+    EDATA for input that is not whole BGZF members (nabwa_bgzf_inflated_size)"""
+    a = np.frombuffer(bytes(data), np.uint8)
+    n_out, n_blocks = C.c_int64(), C.c_int64()
+    _chk(lib().nabwa_bgzf_inflated_size(_ptr(a), a.size, C.byref(n_out), C.byref(n_blocks)))
+    return n_out.value, n_blocks.value
+
+
+def bgzf_decompress(data, device=0, cap=None):
+    """whole BGZF members back to back -> their inflated bytes, inflated and checked against each member's CRC-32 and ISIZE on the
+    GPU (nabwa_bgzf_decompress).  cap: the output capacity handed to the library (default: what the headers say); a NabwaError of
+    code ECAP carries the size that would do in .needed, one of code EDATA names the member that is damaged"""
+    if cap is None:
+        cap = bgzf_inflated_size(data)[0]
+    return _bgzf_call(lib().nabwa_bgzf_decompress, int(device), data, cap)
+
+
 class Bgzf:
-    """the compressor as a handle that keeps its stream and buffers between calls (nabwa_bgzf_create)"""
+    """the compressor and the decompressor as a handle that keeps its stream and buffers between calls (nabwa_bgzf_create)"""
 
     def __init__(self, device=0):
         self._h = _P()
@@ -475,6 +496,11 @@ class Bgzf:
 
     def compress(self, data, cap=None):
         return _bgzf_call(lib().nabwa_bgzf_handle_compress, self._h, data, cap)
+
+    def decompress(self, data, cap=None):
+        if cap is None:
+            cap = bgzf_inflated_size(data)[0]
+        return _bgzf_call(lib().nabwa_bgzf_handle_decompress, self._h, data, cap)
 
     def close(self):
         if self._h:

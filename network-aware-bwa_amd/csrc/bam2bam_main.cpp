@@ -177,6 +177,7 @@ struct Options {
 	uint32_t rec_flags = 0;                                    /* NABWA_BAM_*: --only-aligned, --drop-aligned, --debug-bam, --broken-input, --skip-duplicates */
 	const char *prefix = 0, *ofile = 0, *temp_dir = 0, *input = 0;
 	bool bgzf_gpu = false;                                     /* NABWA_BGZF=gpu */
+	bool bgzf_in_gpu = false;                                  /* NABWA_BGZF_IN=gpu */
 };
 /* -1: go on; else the exit status, after the line that says why */
 static int parse_options(int argc, char **argv, Options &o)
@@ -236,6 +237,11 @@ static int parse_options(int argc, char **argv, Options &o)
 	const char *bgzf_env = getenv("NABWA_BGZF");
 	o.bgzf_gpu = bgzf_env && !strcmp(bgzf_env, "gpu");
 	if (bgzf_env && !o.bgzf_gpu && strcmp(bgzf_env, "host")) { fprintf(stderr, "[nabwa_bam2bam] NABWA_BGZF=%s: host or gpu\n", bgzf_env); return 1; }
+	/* NABWA_BGZF_IN: who inflates a BGZF input -- host (default: zlib on host threads) or gpu (the library's decompressor on the first
+	 * GPU); any other gzip stream and a plain file are read on the host under either */
+	const char *bgzf_in_env = getenv("NABWA_BGZF_IN");
+	o.bgzf_in_gpu = bgzf_in_env && !strcmp(bgzf_in_env, "gpu");
+	if (bgzf_in_env && !o.bgzf_in_gpu && strcmp(bgzf_in_env, "host")) { fprintf(stderr, "[nabwa_bam2bam] NABWA_BGZF_IN=%s: host or gpu\n", bgzf_in_env); return 1; }
 	return -1;
 }
 
@@ -470,6 +476,9 @@ int main(int argc, char **argv)
 	const std::vector<int> devices = tool_devices();
 	nabwa_bgzf_t *bgzf = 0;
 	if (opt.bgzf_gpu && nabwa_bgzf_create(devices[0], &bgzf) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] BGZF on the GPU: %s\n", nabwa_last_error()); return 2; }
+	/* the reader's handle is its own: a handle takes one call at a time, and reader and writer are two threads */
+	nabwa_bgzf_t *bgzf_in = 0;
+	if (opt.bgzf_in_gpu && nabwa_bgzf_create(devices[0], &bgzf_in) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] BGZF on the GPU: %s\n", nabwa_last_error()); return 2; }
 	std::vector<nabwa_index_t*> ixs;
 	{
 		std::string err;
@@ -482,6 +491,13 @@ int main(int argc, char **argv)
 	FILE *inf = strcmp(opt.input, "-") ? fopen(opt.input, "rb") : stdin;
 	if (!inf) die(opt.input, "cannot open");
 	BamIn in(inf, opt.input);
+	if (bgzf_in) in.inflater = [bgzf_in](const uint8_t *cmp, size_t from, size_t to, const std::vector<BamIn::Blk> &blk, uint8_t *plain, std::string &why) {
+		const size_t first = blk.front().dst, end = blk.back().dst + blk.back().isize;
+		int64_t n_out = 0, nb = 0;
+		if (nabwa_bgzf_handle_decompress(bgzf_in, cmp + from, (int64_t)(to - from), plain + first, (int64_t)(end - first), &n_out, &nb) == NABWA_OK) return true;
+		why = nabwa_last_error();
+		return false;
+	};
 	const std::string old = read_input_header(in, opt.input);
 	FILE *of = opt.ofile ? fopen(opt.ofile, "wb") : stdout;
 	if (!of) die(opt.ofile, "cannot create");
@@ -508,13 +524,14 @@ int main(int argc, char **argv)
 	if (timing) { double ts = 0; for (double x : P.t_search) ts += x; fprintf(stderr, "[nabwa_bam2bam] timing: search threads (%zu GPU%s) %.3f s busy\n", P.n_dev, P.n_dev > 1 ? "s" : "", ts); }
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: library calls: create %.3f s, pass 1 %.3f s, pass 2 %.3f s, output %.3f s, destroy %.3f s\n", P.t_call[0], P.t_call[1], P.t_call[2], P.t_call[3], P.t_call[4]);
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: reader thread %.3f s busy (%.3f s of it inflate, %s), passes 1 and 2 on this thread %.3f s (+ %.3f s waiting for input; the output thread waited %.3f s for the writer), writer thread %.3f s busy (deflate + write; %s)\n",
-						P.t_read, in.t_inflate, in.bgzf ? "BGZF blocks in parallel" : in.raw ? "not compressed" : "one gzip stream", P.t_lib, P.t_wait_in, P.t_wait_out, P.t_write,
+						P.t_read, in.t_inflate, in.bgzf ? (bgzf_in ? "BGZF blocks on the GPU" : "BGZF blocks in parallel") : in.raw ? "not compressed" : "one gzip stream", P.t_lib, P.t_wait_in, P.t_wait_out, P.t_write,
 						opt.bgzf_gpu ? "BGZF on the GPU" : "zlib level 2 on host threads");
 	fprintf(stderr, "[nabwa_bam2bam] %ld sequences processed\n[nabwa_bam2bam] finished cleanly, shutting down.\n"
 			"[bwa_paired_sw] %lld out of %lld Q%d singletons are mated.\n[bwa_paired_sw] %lld out of %lld Q%d discordant pairs are fixed.\n",
 			P.tot_seqs, (long long)P.n_mapped[1], (long long)P.n_tot[1], 17, (long long)P.n_mapped[0], (long long)P.n_tot[0], 17);
 	out.close();
 	if (bgzf) nabwa_bgzf_destroy(bgzf);
+	if (bgzf_in) nabwa_bgzf_destroy(bgzf_in);
 	nabwa_isize_table_destroy(P.tab);
 	for (nabwa_index_t *p : ixs) nabwa_index_destroy(p);
 	final_rename(opt.ofile, true);

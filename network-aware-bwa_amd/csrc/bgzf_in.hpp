@@ -3,6 +3,7 @@
 // through die() of tool_common.hpp, so the including program defines TOOL (and TOOL_DIE_STATUS) first.
 #pragma once
 #include <zlib.h>
+#include <functional>
 #include "tool_common.hpp"
 
 /* ---------------------------------------------------------------- BAM in: the plain bytes of a BGZF file (bgzf.c: independent
@@ -15,6 +16,11 @@ struct BamIn {
 	z_stream zs;
 	double t_inflate;
 	struct Blk { size_t src, n_src, dst; uint32_t isize, crc; };
+	/* who inflates a fill's BGZF blocks, if not this file's threads: the blocks blk (payloads at cmp + src, output at plain + dst) are
+	 * the whole members cmp[from, to) back to back, and their output is one stretch from plain + blk[0].dst on.  false with a reason
+	 * for blocks that do not inflate to what their trailers say.  The tool sets it (NABWA_BGZF_IN=gpu); this file knows no library. */
+	typedef std::function<bool(const uint8_t *cmp, size_t from, size_t to, const std::vector<Blk> &blk, uint8_t *plain, std::string &why)> Inflater;
+	Inflater inflater;
 
 	BamIn(FILE *f_, const char *name_) : f(f_), name(name_), bgzf(false), raw(false), in_eof(false), z_open(false), lo(0), hi(0), pos(0), t_inflate(0)
 	{
@@ -88,6 +94,13 @@ struct BamIn {
 			}
 			const size_t before = plain.size();
 			plain.resize(out);
+			if (inflater) {
+				std::string why;
+				if (!inflater(cmp.data(), lo, o, blk, plain.data(), why)) die(name, ("a BGZF block does not inflate to what its trailer says: " + why).c_str());
+				lo = o;
+				if (out != before) return true;
+				continue;
+			}
 			int nt = io_threads(); if ((size_t)nt > blk.size()) nt = (int)blk.size();
 			std::vector<int> bad(nt, 0);
 			std::vector<std::thread> th;

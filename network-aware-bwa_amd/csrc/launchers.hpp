@@ -1,4 +1,4 @@
-// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip and bgzf_deflate.hip, declared once.
+// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, bgzf_deflate.hip and bgzf_inflate.hip, declared once.
 // The defining files and every host unit that calls one include this header, so a parameter list that differs between the two sides
 // is a compile error (C linkage carries no types).  Host side only: the kernel headers (nabwa_dev.hpp, fm_search.hpp, fm_deep.hpp,
 // fm_deep_body.hpp) do not include it -- the CPU emulation of the tests compiles those without HIP.
@@ -47,4 +47,7 @@ int nabwa_deep_occupancy(int ns, int lds_rd);
 /* bgzf_deflate.hip: slice k of in[0, n) -> one BGZF block at stage + k * 0x10000, its size in sizes[k]; then the blocks back to back */
 void nabwa_launch_bgzf_deflate(const uint8_t *in, int64_t n, int n_slices, uint8_t *stage, uint32_t *sizes, hipStream_t s);
 void nabwa_launch_bgzf_pack(const uint8_t *stage, const uint32_t *sizes, int n_slices, uint8_t *packed, int64_t *total, hipStream_t s);
+/* bgzf_inflate.hip: member k (blk[k]: payload cmp + src, n_src bytes) -> isize bytes at plain + dst, its status word (bgzf_inflate_body.hpp) in status[k] */
+struct BgzfInBlk;
+void nabwa_launch_bgzf_inflate(const uint8_t *cmp, const struct BgzfInBlk *blk, int n_blk, uint8_t *plain, uint32_t *status, hipStream_t s);
 }

@@ -277,6 +277,30 @@ int nabwa_se_refine(nabwa_index_t *ix, int n, const int64_t *off, const uint8_t 
 int nabwa_se_posn_v(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, const int64_t *off, const int32_t *full_len,
 					const int32_t *n_aln, const nabwa_aln1_t *aln, const uint8_t *n_occ_v, uint64_t *rng48, nabwa_se_t *out);
 
+/* ---- the finishing chains' device path ----------------------------------------------------------
+ * NABWA_FINISH (read at every call of a chain: nabwa_se_refine, nabwa_se_finish, nabwa_se_finish_cs, nabwa_pe_finish* and what is built on
+ * them): unset or `host` = the reference windows, the CIGAR end rules and MD / NM on host threads; `gpu` = on the device, with the 2-bit
+ * reference and its ambiguity holes held in HBM (uploaded by the first call that needs them, l_pac / 4 + 1 bytes, counted in
+ * nabwa_index_device_bytes); anything else: NABWA_EINVAL.  The records are the same either way.  The two per-record functions of
+ * bwa_refine_gapped as batches, for an integrator who keeps the loop of bwase.c:356-423 (which_ref: 0 = the reference of
+ * nabwa_index_attach_reference, 1 = the nucleotide reference of a colour index, nabwa_index_attach_nt_reference): */
+/* Batch form of refine_gapped_core (bwase.c:189-237) with aln_param_bwa: job i refines query qry[qry_off[i]..qry_off[i+1]) (codes 0-4,
+ * alignment orientation) at pos[i] with ext[i] = +gaps on the reverse strand, -gaps on the forward one.  pos is updated; cigar rows are
+ * max_cigar wide, bwa_cigar_t.  NABWA_ECAP if a path needs more operations than max_cigar. */
+int nabwa_refine_gapped_core(nabwa_index_t *ix, int which_ref, int is_end_correct, int n, const int64_t *qry_off, const uint8_t *qry,
+                             const int32_t *ext, uint32_t *pos, int32_t *n_cigar, uint16_t *cigar, int max_cigar);
+/* Batch form of bwa_cal_md1 (bwase.c:253-315): n_cigar[i] == 0 is the ungapped branch.  md: strings back to back, each NUL-terminated,
+ * record i at md_off[i]; NABWA_ECAP with md_off[n] = bytes needed when md_cap is too small. */
+int nabwa_cal_md(nabwa_index_t *ix, int which_ref, int n, const int64_t *qry_off, const uint8_t *qry, const uint32_t *pos,
+                 const int32_t *n_cigar, const uint16_t *cigar, int max_cigar, int32_t *nm, int64_t *md_off, char *md, int64_t md_cap);
+/* Both: NABWA_EINVAL for a null argument, for no attached reference (or no nucleotide reference when which_ref is 1), for a query length
+ * outside 1 .. 0x3fff, an ext outside -0xffff .. 0xffff or a query code above 4 (nabwa_refine_gapped_core), for a CIGAR that does not
+ * consume its query exactly, and for an ungapped nabwa_cal_md record with pos + len > l_pac (the reference reads outside its array there);
+ * NABWA_ENODEV without a device: there is no CPU fallback. */
+/* tests, diagnostics: since the library was loaded -- [0] jobs refined by nabwa_refine_gapped_core or the chains' device path,
+ * [1] records whose MD / NM the device wrote, [2] calls of a chain that took the device path, [3] bytes of reference held in HBM for it */
+void nabwa_finish_counts(uint64_t out[4]);
+
 /* ---- paired-end chain (config 3) ------------------------------------------------------------ */
 /* pe_opt_t (bwtaln.h:158-164), same layout; defaults as bwa_init_pe_opt (bwape.c:27-41) */
 typedef struct {

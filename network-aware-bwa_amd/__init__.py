@@ -248,6 +248,14 @@ def dp_form_counts():
     return list(out)
 
 
+def finish_counts():
+    """the finishing chains' device path since the library was loaded (nabwa_finish_counts): jobs refined on the device, records whose
+    MD / NM the device wrote, chain calls that took the device path (NABWA_FINISH=gpu), bytes of reference held in HBM for it"""
+    out = (C.c_uint64 * 4)()
+    lib().nabwa_finish_counts(out)
+    return list(out)
+
+
 class NabwaError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libnabwa error %d: %s" % (code, msg))
@@ -353,6 +361,11 @@ def lib():
     L.nabwa_bgzf_decompress.argtypes = [C.c_int, _P, C.c_int64, _P, C.c_int64, _P, _P]
     L.nabwa_bgzf_handle_decompress.argtypes = [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]
     L.nabwa_bgzf_destroy.restype = None
+    if hasattr(L, "nabwa_finish_counts"):          # (a library of an earlier build, loaded through NABWA_LIB for an A/B run, has no such entries)
+        L.nabwa_refine_gapped_core.argtypes = [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int]
+        L.nabwa_cal_md.argtypes = [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int64]
+        L.nabwa_finish_counts.argtypes = [_P]
+        L.nabwa_finish_counts.restype = None
     _lib = L
     return L
 
@@ -667,6 +680,48 @@ class Index:
                                    _ptr(np.ascontiguousarray(seq, np.uint8)), _ptr(np.ascontiguousarray(rseq, np.uint8)),
                                    _ptr(n_aln), _ptr(rows), recs, tot, mp))
         return list(tot), list(mp)
+
+    def refine_gapped_core(self, qry, qry_off, ext, pos, is_end_correct=True, which_ref=0, max_cigar=MAX_CIGAR):
+        """refine_gapped_core (reference bwase.c:189-237) for a batch of queries in alignment orientation, on the device
+        (nabwa_refine_gapped_core).  Returns (new positions, list of bwa_cigar_t arrays)."""
+        n = len(qry_off) - 1
+        qry = np.ascontiguousarray(qry, np.uint8)
+        qry_off = np.ascontiguousarray(qry_off, np.int64)
+        ext = np.ascontiguousarray(ext, np.int32)
+        pos = np.array(pos, np.uint32)
+        ncig = np.zeros(max(n, 1), np.int32)
+        cig = np.zeros((max(n, 1), max_cigar), np.uint16)
+        _chk(lib().nabwa_refine_gapped_core(self._h, which_ref, 1 if is_end_correct else 0, n, _ptr(qry_off), _ptr(qry), _ptr(ext), _ptr(pos),
+                                            _ptr(ncig), _ptr(cig), max_cigar))
+        return pos[:n], [cig[i, :ncig[i]].copy() for i in range(n)]
+
+    def cal_md(self, qry, qry_off, pos, cigars, which_ref=0, md_cap=None):
+        """bwa_cal_md1 (reference bwase.c:253-315) for a batch of queries in alignment orientation, on the device (nabwa_cal_md).
+        cigars: per-record bwa_cigar_t arrays, an empty one for the ungapped branch.  md_cap None: sized by a first call.
+        Returns (NM array, list of MD strings)."""
+        n = len(qry_off) - 1
+        qry = np.ascontiguousarray(qry, np.uint8)
+        qry_off = np.ascontiguousarray(qry_off, np.int64)
+        pos = np.ascontiguousarray(pos, np.uint32)
+        width = max([len(c) for c in cigars] + [1])
+        ncig = np.array([len(c) for c in cigars], np.int32)
+        cig = np.zeros((max(n, 1), width), np.uint16)
+        for i, c in enumerate(cigars):
+            cig[i, :len(c)] = c
+        nm = np.zeros(max(n, 1), np.int32)
+        off = np.zeros(n + 1, np.int64)
+
+        def call(cap):
+            md = np.zeros(max(cap, 1), np.uint8)
+            rc = lib().nabwa_cal_md(self._h, which_ref, n, _ptr(qry_off), _ptr(qry), _ptr(pos), _ptr(ncig), _ptr(cig), width, _ptr(nm),
+                                    _ptr(off), _ptr(md), cap)
+            return rc, md
+        rc, md = call(0 if md_cap is None else md_cap)
+        if rc == ECAP and md_cap is None:
+            rc, md = call(int(off[n]))
+        _chk(rc)
+        raw = md.tobytes()
+        return nm[:n], [raw[off[i]:off[i + 1] - 1].decode() for i in range(n)]
 
     def export(self, which, what, first, n):
         """derived index parts for tests (nabwa_index_export): 0 full SA, 1 inverse SA, 2 text bases, 3 interval table, 4 its depth"""

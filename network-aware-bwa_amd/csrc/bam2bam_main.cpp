@@ -242,6 +242,10 @@ static int parse_options(int argc, char **argv, Options &o)
 	const char *bgzf_in_env = getenv("NABWA_BGZF_IN");
 	o.bgzf_in_gpu = bgzf_in_env && !strcmp(bgzf_in_env, "gpu");
 	if (bgzf_in_env && !o.bgzf_in_gpu && strcmp(bgzf_in_env, "host")) { fprintf(stderr, "[nabwa_bam2bam] NABWA_BGZF_IN=%s: host or gpu\n", bgzf_in_env); return 1; }
+	/* NABWA_FINISH: where the finishing chains cut reference windows, apply the CIGAR end rules and write MD / NM (the library reads it at
+	 * every call); a value it would refuse is refused here, before the index is loaded */
+	const char *finish_env = getenv("NABWA_FINISH");
+	if (finish_env && strcmp(finish_env, "gpu") && strcmp(finish_env, "host")) { fprintf(stderr, "[nabwa_bam2bam] NABWA_FINISH=%s: host or gpu\n", finish_env); return 1; }
 	return -1;
 }
 

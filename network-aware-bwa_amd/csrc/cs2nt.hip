@@ -224,6 +224,7 @@ extern "C" int nabwa_index_attach_nt_reference(nabwa_index_t *ix, const char *pr
 	if (e == hipSuccess) e = hipMalloc((void**)&d, R->pac.size());
 	if (e == hipSuccess) e = hipMemcpy(d, R->pac.data(), R->pac.size(), hipMemcpyHostToDevice);
 	if (e != hipSuccess) { if (d) (void)hipFree(d); delete R; return nabwa_hip_fail(e, "uploading the nucleotide pac", __FILE__, __LINE__); }
+	nabwa_finish_drop_reference(ix);      /* the device path's hole table goes with the bases it was made for (finish_gpu.hip) */
 	if (ix->d_ntpac) { (void)hipFree(ix->d_ntpac); ix->bytes -= ix->ntpac_bytes; }
 	delete ix->ref_nt;
 	ix->ref_nt = R; ix->d_ntpac = d; ix->ntpac_bytes = R->pac.size(); ix->bytes += ix->ntpac_bytes;
@@ -311,16 +312,17 @@ int nabwa_cs2nt_records(nabwa_index_t *ix, void *base, size_t stride, int n, con
 /* ------------------------------------------------------------------ the single-end colour chain */
 
 /* MD / NM on the nucleotide pac with the decoded read, then the flags (bwase.c:404-414; no bwa_correct_trimmed, :418-419) */
-static int cs_md_flags(nabwa_index_t *ix, nabwa_se_t *out, int n, const int64_t *off, const uint8_t *nt_seq, const uint8_t *nt_rseq)
+static int cs_md_flags(nabwa_index_t *ix, nabwa_se_t *out, int n, const int64_t *off, const uint8_t *nt_seq, const uint8_t *nt_rseq, FinGpu *gpu)
 {
 	const nabwa_reference *R = ix->ref, *Rn = ix->ref_nt;
 	int md_over = 0;
+	if (gpu && n) if (const int r = gpu->md_records(1, out, sizeof(nabwa_se_t), n, off)) return r;       /* NABWA_FINISH=gpu: MD / NM on the device */
 	host_parallel(host_threads((size_t)n, 4096), (size_t)n, [&](int, size_t lo, size_t hi) {
 		std::vector<uint8_t> fwd;
 		for (size_t i = lo; i < hi; ++i) {
 			nabwa_se_t &s = out[i];
 			if (s.type == 0) { s.flag = 4; continue; }
-			if (!md_and_trim(Rn, s, nt_seq + off[i], nt_rseq + off[i], fwd)) md_over = 1;      /* len == full_len: nothing is trimmed */
+			if (gpu ? !gpu->take_md((int)i, s) : !md_and_trim(Rn, s, nt_seq + off[i], nt_rseq + off[i], fwd)) md_over = 1;      /* len == full_len: nothing is trimmed */
 			se_flags(R, s);
 		}
 	});
@@ -344,13 +346,25 @@ extern "C" int nabwa_se_finish_cs(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 	if (r != NABWA_OK) return r;
 	const double t1 = now_s();
 	size_t j1 = 0, j2 = 0;
-	if ((r = refine_batch(ix, out, sizeof(nabwa_se_t), n, off, seq, rseq, &j1)) != NABWA_OK) return r;
+	/* NABWA_FINISH=gpu: windows, CIGAR rules and MD / NM on the device (finish_gpu.hip): the colour reads for the first refinement,
+	 * the decoded reads for the second and for MD / NM */
+	const int fin_mode = nabwa_finish_mode();
+	if (fin_mode < 0) return nabwa_fail(NABWA_EINVAL, "NABWA_FINISH: host or gpu");
+	std::unique_ptr<FinGpu> gpu;
+	if (fin_mode == 1) {
+		nabwa_finish_count_chain_call();
+		gpu.reset(new FinGpu(ix));
+		if (n && (r = gpu->set_reads(off[n], seq, rseq)) != NABWA_OK) return r;
+	}
+	if ((r = refine_batch(ix, out, sizeof(nabwa_se_t), n, off, seq, rseq, &j1, nullptr, gpu.get())) != NABWA_OK) return r;
 	const double t2 = now_s();
 	if ((r = nabwa_cs2nt_records(ix, out, sizeof(nabwa_se_t), n, off, seq, rseq, qual, nt_seq, nt_rseq, nt_qual, times)) != NABWA_OK) return r;
 	const double t3 = now_s();
-	if ((r = refine_batch(ix, out, sizeof(nabwa_se_t), n, off, nt_seq, nt_rseq, &j2, ix->ref_nt)) != NABWA_OK) return r;
+	if (gpu && n && (r = gpu->set_reads(off[n], nt_seq, nt_rseq)) != NABWA_OK) return r;
+	if ((r = refine_batch(ix, out, sizeof(nabwa_se_t), n, off, nt_seq, nt_rseq, &j2, ix->ref_nt, gpu.get())) != NABWA_OK) return r;
 	const double t4 = now_s();
-	if ((r = cs_md_flags(ix, out, n, off, nt_seq, nt_rseq)) != NABWA_OK) return r;
+	if ((r = cs_md_flags(ix, out, n, off, nt_seq, nt_rseq, gpu.get())) != NABWA_OK) return r;
+	if (gpu) gpu->report("se_finish_cs");
 	if (timing) fprintf(stderr, "[nabwa] se_finish_cs %d reads: posn %.3f s, colour refinement (%zu jobs) %.3f s, decode %.3f s, "
 						"nucleotide refinement (%zu jobs) %.3f s, md/flags %.3f s\n", n, t1 - t0, j1, t2 - t1, t3 - t2, j2, t4 - t3, now_s() - t4);
 	return NABWA_OK;

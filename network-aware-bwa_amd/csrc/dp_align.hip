@@ -44,10 +44,15 @@ struct ArenaUse {                 /* at most 8 kernel buffers */
 		d_ro = take<int64_t>(sz[0]); d_qo = take<int64_t>(sz[1]); d_ref = take<uint8_t>(sz[2]); d_qry = take<uint8_t>(sz[3]);
 		return NABWA_OK;
 	}
-	int upload(int n, const int64_t *ro, const uint8_t *ref, const int64_t *qo, const uint8_t *qry)
+	int upload_offsets(int n, const int64_t *ro, const int64_t *qo)
 	{
 		HIP_CHECK(hipMemcpy(d_ro, ro, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
 		HIP_CHECK(hipMemcpy(d_qo, qo, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+		return NABWA_OK;
+	}
+	int upload(int n, const int64_t *ro, const uint8_t *ref, const int64_t *qo, const uint8_t *qry)
+	{
+		if (const int r = upload_offsets(n, ro, qo)) return r;
 		if (ro[n]) HIP_CHECK(hipMemcpy(d_ref, ref, ro[n], hipMemcpyHostToDevice));
 		if (qo[n]) HIP_CHECK(hipMemcpy(d_qry, qry, qo[n], hipMemcpyHostToDevice));
 		return NABWA_OK;
@@ -66,6 +71,48 @@ extern "C" void nabwa_dp_scratch_release(int device)
 
 /* ------------------------------------------------------------------ batched aln_global_core */
 
+/* One launch of the global alignment kernel on tasks that are, or are about to be, on the device: the arena is reserved and the offsets
+ * uploaded here; `fill` puts the m tasks' sequences at d_ref / d_qry (an upload, or a kernel that writes them there); the kernel is
+ * launched; `take` gets the launch's parameters while the arena is still held -- score, n_cigar and the slot-major operations are device
+ * memory -- and does what it likes with them.  ro / qo start at 0.  tg (may be null): += set-up, fill, kernel, take seconds. */
+int nabwa_dp_global_device(int device, int m, const int64_t *ro, const int64_t *qo, int gap_open, int gap_ext, int gap_end, const int *matrix25,
+						   int band, int max_cigar, const std::function<int(const DpDeviceIO&)> &fill,
+						   const std::function<int(const DpParams&)> &take, double *tg)
+{
+	const bool timing = tg != nullptr;
+	const double tg0 = now_s();
+	int W = 1, H = 1; int64_t maxdiff = 0;
+	for (int i = 0; i < m; ++i) {
+		const int64_t a1 = ro[i + 1] - ro[i], a2 = qo[i + 1] - qo[i];
+		W = std::max<int64_t>(W, a1 + 1);
+		H = std::max<int64_t>(H, a2 + 1);
+		maxdiff = std::max<int64_t>(maxdiff, a1 > a2 ? a1 - a2 : a2 - a1);
+	}
+	const size_t waves = (size_t)((m + 255) / 256) * 4;
+	DpParams P; memset(&P, 0, sizeof(P));
+	ArenaUse A(device);
+	if (const int r = A.reserve(m, ro, qo, { waves * 6 * (size_t)W * 64 * 4, waves * (size_t)H * W * 64, waves * (size_t)(W + H) * 64,
+											 (size_t)m * 4, (size_t)m * 4, (size_t)m * max_cigar * 4 })) return r;
+	P.rows = A.next<int32_t>(); P.tb = A.next<uint8_t>(); P.path = A.next<uint8_t>();
+	P.score = A.next<int32_t>(); P.n_cigar = A.next<int32_t>(); P.cigar = A.next<uint32_t>();
+	const double tg1 = now_s();
+	if (const int r = A.upload_offsets(m, ro, qo)) return r;
+	if (const int r = fill(DpDeviceIO{ A.d_ro, A.d_qo, A.d_ref, A.d_qry })) return r;
+	P.n = m; P.ref_off = A.d_ro; P.qry_off = A.d_qo; P.ref = A.d_ref; P.qry = A.d_qry;
+	P.gap_open = gap_open; P.gap_ext = gap_ext; P.gap_end = gap_end; P.band = band;
+	memcpy(P.matrix, matrix25, sizeof(P.matrix));
+	P.W = W; P.H = H; P.max_cigar = max_cigar;
+	P.wb = (int)std::min<int64_t>(W, 2 * (int64_t)band + maxdiff + 1);
+	const double tg2 = now_s();
+	nabwa_launch_dp_global(&P, 0);
+	HIP_CHECK(hipGetLastError());
+	if (timing) HIP_CHECK(hipDeviceSynchronize());
+	const double tg3 = now_s();
+	if (const int r = take(P)) return r;
+	if (tg) { tg[0] += tg1 - tg0; tg[1] += tg2 - tg1; tg[2] += tg3 - tg2; tg[3] += now_s() - tg3; }
+	return NABWA_OK;
+}
+
 extern "C" int nabwa_global_align(int device, int n, const int64_t *ref_off, const uint8_t *ref, const int64_t *qry_off,
 								  const uint8_t *qry, int gap_open, int gap_ext, int gap_end, const int *matrix25, int band,
 								  int32_t *score, int32_t *n_cigar, uint32_t *cigar32, int max_cigar)
@@ -79,51 +126,33 @@ extern "C" int nabwa_global_align(int device, int n, const int64_t *ref_off, con
 	const bool timing = getenv("NABWA_TIMING") != 0 && n >= 1024;
 	double tg[4] = { 0, 0, 0, 0 };              // set-up, upload, kernel, download
 	for (int c0 = 0; c0 < n; c0 += CHUNK) {
-		const double tg0 = now_s();
 		const int m = std::min(CHUNK, n - c0);
-		int W = 1, H = 1; int64_t maxdiff = 0;
-		for (int i = c0; i < c0 + m; ++i) {
-			const int64_t a1 = ref_off[i + 1] - ref_off[i], a2 = qry_off[i + 1] - qry_off[i];
-			W = std::max<int64_t>(W, a1 + 1);
-			H = std::max<int64_t>(H, a2 + 1);
-			maxdiff = std::max<int64_t>(maxdiff, a1 > a2 ? a1 - a2 : a2 - a1);
-		}
 		std::vector<int64_t> ro(m + 1), qo(m + 1);
 		for (int i = 0; i <= m; ++i) { ro[i] = ref_off[c0 + i] - ref_off[c0]; qo[i] = qry_off[c0 + i] - qry_off[c0]; }
-		const size_t waves = (size_t)((m + 255) / 256) * 4;
-		DpParams P; memset(&P, 0, sizeof(P));
-		ArenaUse A(device);
-		if (const int r = A.reserve(m, ro.data(), qo.data(), { waves * 6 * (size_t)W * 64 * 4, waves * (size_t)H * W * 64, waves * (size_t)(W + H) * 64,
-															  (size_t)m * 4, (size_t)m * 4, (size_t)m * max_cigar * 4 })) return r;
-		P.rows = A.next<int32_t>(); P.tb = A.next<uint8_t>(); P.path = A.next<uint8_t>();
-		P.score = A.next<int32_t>(); P.n_cigar = A.next<int32_t>(); P.cigar = A.next<uint32_t>();
-		const double tg1 = now_s();
-		if (const int r = A.upload(m, ro.data(), ref + ref_off[c0], qo.data(), qry + qry_off[c0])) return r;
-		P.n = m; P.ref_off = A.d_ro; P.qry_off = A.d_qo; P.ref = A.d_ref; P.qry = A.d_qry;
-		P.gap_open = gap_open; P.gap_ext = gap_ext; P.gap_end = gap_end; P.band = band;
-		memcpy(P.matrix, matrix25, sizeof(P.matrix));
-		P.W = W; P.H = H; P.max_cigar = max_cigar;
-		P.wb = (int)std::min<int64_t>(W, 2 * (int64_t)band + maxdiff + 1);
-		const double tg2 = now_s();
-		nabwa_launch_dp_global(&P, 0);
-		HIP_CHECK(hipGetLastError());
-		if (timing) HIP_CHECK(hipDeviceSynchronize());
-		const double tg3 = now_s();
-		HIP_CHECK(hipMemcpy(score + c0, P.score, (size_t)m * 4, hipMemcpyDeviceToHost));
-		HIP_CHECK(hipMemcpy(n_cigar + c0, P.n_cigar, (size_t)m * 4, hipMemcpyDeviceToHost));
-		/* the operations come slot by slot (dp_global_kernel): only the slots in use travel */
-		int slots = 0;
-		for (int i = 0; i < m; ++i) slots = std::max(slots, std::min(n_cigar[c0 + i], max_cigar));
-		if (slots) {
-			std::vector<uint32_t> cs((size_t)slots * m);
-			HIP_CHECK(hipMemcpy(cs.data(), P.cigar, cs.size() * 4, hipMemcpyDeviceToHost));
-			for (int i = 0; i < m; ++i) {
-				uint32_t *dst = cigar32 + (size_t)(c0 + i) * max_cigar;
-				const int k_n = std::min(n_cigar[c0 + i], max_cigar);
-				for (int k = 0; k < k_n; ++k) dst[k] = cs[(size_t)k * m + i];
-			}
-		}
-		tg[0] += tg1 - tg0; tg[1] += tg2 - tg1; tg[2] += tg3 - tg2; tg[3] += now_s() - tg3;
+		const int r = nabwa_dp_global_device(device, m, ro.data(), qo.data(), gap_open, gap_ext, gap_end, matrix25, band, max_cigar,
+			[&](const DpDeviceIO &D) -> int {
+				if (ro[m]) HIP_CHECK(hipMemcpy(D.d_ref, ref + ref_off[c0], ro[m], hipMemcpyHostToDevice));
+				if (qo[m]) HIP_CHECK(hipMemcpy(D.d_qry, qry + qry_off[c0], qo[m], hipMemcpyHostToDevice));
+				return NABWA_OK;
+			},
+			[&](const DpParams &P) -> int {
+				HIP_CHECK(hipMemcpy(score + c0, P.score, (size_t)m * 4, hipMemcpyDeviceToHost));
+				HIP_CHECK(hipMemcpy(n_cigar + c0, P.n_cigar, (size_t)m * 4, hipMemcpyDeviceToHost));
+				/* the operations come slot by slot (dp_global_kernel): only the slots in use travel */
+				int slots = 0;
+				for (int i = 0; i < m; ++i) slots = std::max(slots, std::min(n_cigar[c0 + i], max_cigar));
+				if (slots) {
+					std::vector<uint32_t> cs((size_t)slots * m);
+					HIP_CHECK(hipMemcpy(cs.data(), P.cigar, cs.size() * 4, hipMemcpyDeviceToHost));
+					for (int i = 0; i < m; ++i) {
+						uint32_t *dst = cigar32 + (size_t)(c0 + i) * max_cigar;
+						const int k_n = std::min(n_cigar[c0 + i], max_cigar);
+						for (int k = 0; k < k_n; ++k) dst[k] = cs[(size_t)k * m + i];
+					}
+				}
+				return NABWA_OK;
+			}, timing ? tg : nullptr);
+		if (r != NABWA_OK) return r;
 	}
 	if (timing) fprintf(stderr, "[nabwa] global_align %d tasks: set-up %.4f s, upload %.4f s, kernel %.4f s, download %.4f s\n", n, tg[0], tg[1], tg[2], tg[3]);
 	return NABWA_OK;

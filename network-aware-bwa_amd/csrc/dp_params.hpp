@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <functional>
 
 struct DpParams {
 	int n;
@@ -50,3 +51,10 @@ extern "C" void nabwa_launch_dp_local(const LocParams *P, hipStream_t s);
 extern "C" void nabwa_launch_dp_extend_fwd(const ExtParams *P, hipStream_t s);
 extern "C" int nabwa_dp_local_fits_lds(int W);             /* do a task's two rows and its window fit LDS? else the rows live in HBM */
 extern "C" size_t nabwa_dp_local_rows_bytes(int W);        /* HBM form: bytes per task */
+
+/* dp_align.hip: one launch of the global alignment kernel on sequences that `fill` puts on the device, its results left there for
+ * `take` (finish_gpu.hip refines gapped hits this way, nabwa_global_align itself uploads and downloads) */
+struct DpDeviceIO { int64_t *d_ro, *d_qo; uint8_t *d_ref, *d_qry; };
+int nabwa_dp_global_device(int device, int m, const int64_t *ro, const int64_t *qo, int gap_open, int gap_ext, int gap_end, const int *matrix25,
+						   int band, int max_cigar, const std::function<int(const DpDeviceIO&)> &fill,
+						   const std::function<int(const DpParams&)> &take, double *tg);

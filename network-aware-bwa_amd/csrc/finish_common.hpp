@@ -13,6 +13,7 @@
 #include "../../include/nabwa.h"
 #include "nabwa_internal.hpp"
 #include "host_util.hpp"
+#include "finish_gpu.hpp"
 
 /* ------------------------------------------------------------------ small host pieces */
 
@@ -242,9 +243,11 @@ static inline void se_flags(const nabwa_reference *R, nabwa_se_t &s)
  * of the packed text, laying the reads out in alignment orientation, turning the paths into CIGARs -- runs on slices of the
  * records / jobs in threads.
  * nt_ref (colour space, bwase.c:383-402): the second pass on the nucleotide pac with the decoded reads -- every hit that has a CIGAR
- * and every gapped multi hit again, with is_end_correct = 0: the window starts at pos on both strands and pos is not shifted. */
+ * and every gapped multi hit again, with is_end_correct = 0: the window starts at pos on both strands and pos is not shifted.
+ * gpu (NABWA_FINISH=gpu, finish_gpu.hpp; its reads are seq / rseq): the jobs and their extents are found here as ever, the windows, the
+ * queries and the CIGARs are made on the device -- no pac byte is touched here. */
 static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int n, const int64_t *off, const uint8_t *seq,
-							   const uint8_t *rseq, size_t *n_jobs, const nabwa_reference *nt_ref = nullptr)
+							   const uint8_t *rseq, size_t *n_jobs, const nabwa_reference *nt_ref = nullptr, FinGpu *gpu = nullptr)
 {
 	const nabwa_reference *R = nt_ref ? nt_ref : ix->ref;
 	const bool end_correct = nt_ref == nullptr;
@@ -265,6 +268,31 @@ static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int
 	{ size_t tot = 0; for (auto &v : part) tot += v.size(); jobs.reserve(tot); for (auto &v : part) jobs.insert(jobs.end(), v.begin(), v.end()); }
 	if (n_jobs) *n_jobs = jobs.size();
 	if (jobs.empty()) return NABWA_OK;
+	if (gpu) {
+		const size_t nj = jobs.size();
+		std::vector<FinJob> fj(nj);
+		for (size_t t = 0; t < nj; ++t) {                  /* the windows' extents (bwase.c:197-209): arithmetic only */
+			const RefineJob &J = jobs[t]; FinJob &F = fj[t];
+			memset(&F, 0, sizeof F);
+			F.src_off = off[J.rec]; F.len = J.len; F.ext = J.ext; F.copy = J.strand ? 1 : 0;
+			fin_job_extent(R->l_pac, end_correct, (uint32_t)J.pos, F);
+		}
+		gpu->t_desc += now_s() - tr0;
+		std::vector<uint32_t> p(nj); std::vector<int32_t> nc(nj); std::vector<uint16_t> rows(nj * (size_t)NABWA_MAX_CIGAR);
+		if (const int r = gpu->refine(nt_ref ? 1 : 0, end_correct ? 1 : 0, nj, fj.data(), p.data(), nc.data(), rows.data(), NABWA_MAX_CIGAR)) return r;
+		const double tw = now_s();
+		host_parallel(host_threads(nj, 4096), nj, [&](int, size_t lo_t, size_t hi_t) {
+			for (size_t t = lo_t; t < hi_t; ++t) {
+				const RefineJob &J = jobs[t];
+				nabwa_se_t &s = *rec_at(base, stride, J.rec);
+				const uint16_t *cg = rows.data() + t * (size_t)NABWA_MAX_CIGAR;
+				if (J.multi < 0) { s.pos = p[t]; s.n_cigar = nc[t]; memcpy(s.cigar, cg, 2 * (size_t)nc[t]); }
+				else { s.multi[J.multi].pos = p[t]; s.multi[J.multi].n_cigar = nc[t]; memcpy(s.multi[J.multi].cigar, cg, 2 * (size_t)nc[t]); }
+			}
+		});
+		gpu->t_down += now_s() - tw;
+		return NABWA_OK;
+	}
 	static const int maq[25] = { 11,-19,-19,-19,-13, -19,11,-19,-19,-13, -19,-19,11,-19,-13, -19,-19,-19,11,-13, -13,-13,-13,-13,-13 };  /* aln_sm_maq */
 	const size_t nj = jobs.size();
 	const int ntj = host_threads(nj, 4096);
@@ -340,16 +368,11 @@ static inline int refine_batch(nabwa_index_t *ix, void *base, size_t stride, int
 	return NABWA_OK;
 }
 
-/* MD / NM of a mapped record, then the quality-trimmed tail as a soft clip (bwase.c:399-419, :320-354).
- * `fwd` is scratch for the un-reversed read. */
-static inline bool md_and_trim(const nabwa_reference *R, nabwa_se_t &s, const uint8_t *seq_i, const uint8_t *rseq_i, std::vector<uint8_t> &fwd)
+/* the quality-trimmed tail as a soft clip (bwa_correct_trimmed, bwase.c:320-354); on its own where MD / NM came from the device */
+static inline void correct_trimmed(nabwa_se_t &s)
 {
 	const int len = s.len;
-	const uint8_t *q;
-	if (s.strand) q = rseq_i;
-	else { fwd.resize(len); for (int k = 0; k < len; ++k) fwd[k] = seq_i[len - 1 - k]; q = fwd.data(); }
-	const bool md_fits = make_md(R, s.n_cigar, s.cigar, len, s.pos, q, s.md, NABWA_MAX_MD, &s.nm);
-	if (len != s.full_len) {                                   /* bwa_correct_trimmed */
+	if (len != s.full_len) {
 		const int clip = s.full_len - len;
 		if (s.strand == 0) {
 			if (s.n_cigar && COP(s.cigar[s.n_cigar - 1]) == 3) s.cigar[s.n_cigar - 1] += clip;
@@ -364,5 +387,17 @@ static inline bool md_and_trim(const nabwa_reference *R, nabwa_se_t &s, const ui
 		}
 		s.len = s.full_len;
 	}
+}
+
+/* MD / NM of a mapped record, then the quality-trimmed tail as a soft clip (bwase.c:399-419, :320-354).
+ * `fwd` is scratch for the un-reversed read. */
+static inline bool md_and_trim(const nabwa_reference *R, nabwa_se_t &s, const uint8_t *seq_i, const uint8_t *rseq_i, std::vector<uint8_t> &fwd)
+{
+	const int len = s.len;
+	const uint8_t *q;
+	if (s.strand) q = rseq_i;
+	else { fwd.resize(len); for (int k = 0; k < len; ++k) fwd[k] = seq_i[len - 1 - k]; q = fwd.data(); }
+	const bool md_fits = make_md(R, s.n_cigar, s.cigar, len, s.pos, q, s.md, NABWA_MAX_MD, &s.nm);
+	correct_trimmed(s);
 	return md_fits;
 }

@@ -1,4 +1,4 @@
-// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, bgzf_deflate.hip and bgzf_inflate.hip, declared once.
+// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, bgzf_deflate.hip, bgzf_inflate.hip and finish_kernels.hip, declared once.
 // The defining files and every host unit that calls one include this header, so a parameter list that differs between the two sides
 // is a compile error (C linkage carries no types).  Host side only: the kernel headers (nabwa_dev.hpp, fm_search.hpp, fm_deep.hpp,
 // fm_deep_body.hpp) do not include it -- the CPU emulation of the tests compiles those without HIP.
@@ -50,4 +50,16 @@ void nabwa_launch_bgzf_pack(const uint8_t *stage, const uint32_t *sizes, int n_s
 /* bgzf_inflate.hip: member k (blk[k]: payload cmp + src, n_src bytes) -> isize bytes at plain + dst, its status word (bgzf_inflate_body.hpp) in status[k] */
 struct BgzfInBlk;
 void nabwa_launch_bgzf_inflate(const uint8_t *cmp, const struct BgzfInBlk *blk, int n_blk, uint8_t *plain, uint32_t *status, hipStream_t s);
+/* finish_kernels.hip (finish_body.hpp): job t's window out of the .pac to ref + ro[t] and its query to qry + qo[t]; the alignment kernel's
+ * slot-major operations (n_c32[t] of them at c32[k * n + t]) -> pos, n_cigar and a bwa_cigar_t row max_cigar wide, *n_bad += the paths
+ * that do not fit; MD / NM of record t: first the length and NM, then the string at md + md_off[t] */
+struct FinRef; struct FinJob; struct FinRec;
+void nabwa_launch_refine_window(const uint8_t *pac, const struct FinJob *jobs, int n, const uint8_t *reads0, const uint8_t *reads1, const int64_t *ro,
+								const int64_t *qo, uint8_t *ref, uint8_t *qry, hipStream_t s);
+void nabwa_launch_refine_cigar(const struct FinJob *jobs, int n, int end_correct, const int32_t *n_c32, const uint32_t *c32, int max_cigar,
+							   uint32_t *pos_out, int32_t *n_cigar, uint16_t *rows, unsigned int *n_bad, hipStream_t s);
+void nabwa_launch_md_count(const struct FinRef *R, const struct FinRec *recs, int n, const uint8_t *reads0, const uint8_t *reads1, const uint16_t *cigar,
+						   int32_t *nm, int32_t *len_out, hipStream_t s);
+void nabwa_launch_md_write(const struct FinRef *R, const struct FinRec *recs, int n, const uint8_t *reads0, const uint8_t *reads1, const uint16_t *cigar,
+						   const int64_t *md_off, char *md, hipStream_t s);
 }

@@ -10,6 +10,7 @@
 #include "launchers.hpp"
 #include "nabwa_internal.hpp"
 #include "dev_pool.hpp"
+#include "finish_gpu.hpp"
 
 static int build_one(nabwa_index *ix, int t_, const uint32_t *words, uint64_t n_words, bool on_device,
 					 const uint32_t *sa_words, uint64_t n_sa_words)
@@ -170,6 +171,7 @@ extern "C" void nabwa_index_destroy(nabwa_index_t *ix)
 	(void)hipSetDevice(ix->device);
 	for (int t = 0; t < 2; ++t) { if (ix->bk[t]) (void)hipFree(ix->bk[t]); if (ix->sa[t]) (void)hipFree(ix->sa[t]); if (ix->kmer[t]) (void)hipFree(ix->kmer[t]); if (ix->kmer_top[t]) (void)hipFree(ix->kmer_top[t]);
 		if (ix->sa_full[t]) (void)hipFree(ix->sa_full[t]); if (ix->isa[t]) (void)hipFree(ix->isa[t]); if (ix->text[t]) (void)hipFree(ix->text[t]); }
+	nabwa_finish_drop_reference(ix);
 	pool_destroy(ix->pool);
 	if (ix->d_ntpac) (void)hipFree(ix->d_ntpac);
 	delete ix->ref_nt;

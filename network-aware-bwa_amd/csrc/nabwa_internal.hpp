@@ -2,6 +2,7 @@
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
+#include <mutex>
 #include <string>
 #include <vector>
 #include "../../include/nabwa.h"
@@ -32,6 +33,12 @@ struct nabwa_index {
 	uint8_t *d_ntpac = nullptr;          // ... and those bases in HBM, with their size in bytes
 	uint64_t ntpac_bytes = 0;
 	struct nabwa_dev_pool *pool = nullptr;   // released working buffers of earlier batches, kept for the next one (dev_pool.hpp)
+	/* the finishing chains' device path (finish_gpu.hip): the bases of `ref` and the hole tables of `ref` / `ref_nt` in HBM, uploaded by the
+	 * first call that needs them -- the chains run on several threads, hence the lock -- and counted in `bytes` */
+	std::mutex fin_mu;
+	uint8_t *d_pac = nullptr; uint64_t pac_bytes = 0;
+	void *d_holes[2] = {}; uint64_t holes_bytes[2] = {}; int n_holes_dev[2] = {};
+	bool fin_ready[2] = {};
 };
 
 /* a failed HIP call: "<expr> failed: <hip error> (<file>:<line>)" as the last error, NABWA_ENODEV as the result */

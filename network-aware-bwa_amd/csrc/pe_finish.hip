@@ -460,8 +460,17 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 	t3 = now_s();
 
 	/* ---- D. gap refinement of both ends and their multi hits, one GPU batch (bwa_refine_gapped, bwase.c:356-381) */
+	/* NABWA_FINISH=gpu: windows, CIGAR rules and MD / NM on the device (finish_gpu.hip), the reads uploaded once for both */
+	const int fin_mode = nabwa_finish_mode();
+	if (fin_mode < 0) return nabwa_fail(NABWA_EINVAL, "NABWA_FINISH: host or gpu");
+	std::unique_ptr<FinGpu> gpu;
+	if (fin_mode == 1) {
+		nabwa_finish_count_chain_call();
+		gpu.reset(new FinGpu(ix));
+		if (n) if (const int r = gpu->set_reads(off[n], seq, rseq)) return r;
+	}
 	{
-		int r = refine_batch(ix, out, sizeof(nabwa_pe_t), n, off, seq, rseq, &n_refine);
+		int r = refine_batch(ix, out, sizeof(nabwa_pe_t), n, off, seq, rseq, &n_refine, nullptr, gpu.get());
 		if (r != NABWA_OK) return r;
 	}
 	double t_dec = 0, t_ref2 = 0; size_t n_refine2 = 0;
@@ -471,12 +480,14 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 		int r = nabwa_cs2nt_records(ix, out, sizeof(nabwa_pe_t), n, off, seq, rseq, cs->qual, cs->nt_seq, cs->nt_rseq, cs->nt_qual, cs->times);
 		if (r != NABWA_OK) return r;
 		const double td1 = now_s();
-		r = refine_batch(ix, out, sizeof(nabwa_pe_t), n, off, cs->nt_seq, cs->nt_rseq, &n_refine2, ix->ref_nt);
+		if (gpu && n) if ((r = gpu->set_reads(off[n], cs->nt_seq, cs->nt_rseq)) != NABWA_OK) return r;      /* the decoded reads from here on */
+		r = refine_batch(ix, out, sizeof(nabwa_pe_t), n, off, cs->nt_seq, cs->nt_rseq, &n_refine2, ix->ref_nt, gpu.get());
 		if (r != NABWA_OK) return r;
 		t_dec = td1 - td0; t_ref2 = now_s() - td1;
 		seq = cs->nt_seq; rseq = cs->nt_rseq; Rmd = ix->ref_nt;
 	}
 	t4 = now_s();
+	if (gpu && n) if (const int r = gpu->md_records(cs ? 1 : 0, out, sizeof(nabwa_pe_t), n, off)) return r;
 
 	/* ---- E. MD / NM / trimmed tail per end, then the flag and mate fields (bwase.c:399-419, bam2bam.c:430-525) */
 	int md_over = 0;
@@ -486,10 +497,12 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 			/* (the pieces of a record lie far apart -- head, MD field and tail of a 3 KB record, its window in the packed reference: asked for ahead,
 			 * as in se_finish.hip) */
 			if (pr + 8 < hi) for (int j = 0; j < 2; ++j) { const nabwa_pe_t *const f = &PE(out, pr + 8, j); __builtin_prefetch(f, 1); __builtin_prefetch(f->se.md, 1); __builtin_prefetch(&f->se.flag, 1); __builtin_prefetch(&f->extra_flag, 1); }
-			if (pr + 4 < hi) for (int j = 0; j < 2; ++j) { const nabwa_se_t &f = PE(out, pr + 4, j).se; if (f.type) { const uint8_t *const w = R->pac.data() + (f.pos >> 2); __builtin_prefetch(w); __builtin_prefetch(w + 32); } }
+			if (!gpu && pr + 4 < hi) for (int j = 0; j < 2; ++j) { const nabwa_se_t &f = PE(out, pr + 4, j).se; if (f.type) { const uint8_t *const w = R->pac.data() + (f.pos >> 2); __builtin_prefetch(w); __builtin_prefetch(w + 32); } }
 			for (int j = 0; j < 2; ++j) {
 				nabwa_se_t &s = PE(out, pr, j).se;
-				if (s.type != 0 && !md_and_trim(Rmd, s, seq + off[2 * pr + j], rseq + off[2 * pr + j], fwd)) md_over = 1;
+				if (s.type == 0) continue;
+				if (gpu) { if (!gpu->take_md(2 * pr + j, s)) md_over = 1; correct_trimmed(s); }      /* MD / NM came from the device */
+				else if (!md_and_trim(Rmd, s, seq + off[2 * pr + j], rseq + off[2 * pr + j], fwd)) md_over = 1;
 			}
 			for (int j = 0; j < 2; ++j) {                              /* end 0 first, as bam2bam.c:804-805 */
 				nabwa_pe_t &r = PE(out, pr, j); nabwa_se_t &p = r.se;
@@ -530,6 +543,7 @@ static int pe_finish_impl(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, const n
 	if (timing) fprintf(stderr, "[nabwa] pe_finish %d pairs: pairing (%zu hit rows) %.3f s, multi %.3f s, mate rescue (%zu alignments) %.3f s, "
 						"refinement (%zu jobs) %.3f s, md/flags %.3f s\n", n_pairs, n_hit_rows, t1 - t0, t2 - t1, n_sw, t3 - t2, n_refine, t4 - t3, now_s() - t4);
 	if (timing && cs) fprintf(stderr, "[nabwa] pe_finish colour space: decode %.3f s, nucleotide refinement (%zu jobs) %.3f s\n", t_dec, n_refine2, t_ref2);
+	if (gpu) gpu->report("pe_finish");
 	if (cnt_chg) *cnt_chg = chg.load();
 	return NABWA_OK;
 }

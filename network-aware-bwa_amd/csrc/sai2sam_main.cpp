@@ -508,6 +508,9 @@ static int run(int argc, char *argv[])
 		}
 	}
 	if (optind + 1 + 2 * N_FILES > argc) return usage();
+	/* NABWA_FINISH: where the finishing chains cut reference windows, apply the CIGAR end rules and write MD / NM (the library reads it at
+	 * every call); a value it would refuse is refused here, before any file is opened */
+	if (const char *e = getenv("NABWA_FINISH")) if (strcmp(e, "gpu") && strcmp(e, "host")) fail(std::string("NABWA_FINISH=") + e + ": host or gpu");
 	const char *prefix = argv[optind];
 	const char *fn_sai[2] = { argv[optind + 1], SAI2SAM_PE ? argv[optind + 2] : nullptr };
 	R.fn_rd[0] = argv[optind + 1 + N_FILES]; R.fn_rd[1] = SAI2SAM_PE ? argv[optind + 2 + N_FILES] : nullptr;

@@ -19,6 +19,7 @@
 #include "../../include/nabwa.h"
 #include "nabwa_internal.hpp"
 #include "finish_common.hpp"
+#include "finish_gpu.hpp"
 
 /* ------------------------------------------------------------------ reference annotations */
 
@@ -64,6 +65,7 @@ extern "C" int nabwa_index_attach_reference(nabwa_index_t *ix, const char *prefi
 	if (!ix || !prefix) return nabwa_fail(NABWA_EINVAL, "null argument");
 	nabwa_reference *R = nullptr;
 	if (const int r = nabwa_reference_read(prefix, &R)) return r;
+	nabwa_finish_drop_reference(ix);      /* the device path's copies of the old one (finish_gpu.hip) */
 	delete ix->ref;
 	ix->ref = R;
 	return NABWA_OK;
@@ -82,6 +84,7 @@ extern "C" int nabwa_index_set_reference(nabwa_index_t *ix, int64_t l_pac, uint3
 	for (int i = 0; i < n_holes; ++i) { nabwa_hole h; h.offset = hole_off[i]; h.len = hole_len[i]; h.amb = hole_amb[i]; R->holes.push_back(h); }
 	R->pac.assign(pac, pac + (l_pac + 3) / 4);
 	R->pac.resize(R->pac.size() + 8);
+	nabwa_finish_drop_reference(ix);      /* the device path's copies of the old one (finish_gpu.hip) */
 	delete ix->ref;
 	ix->ref = R;
 	return NABWA_OK;
@@ -255,11 +258,21 @@ int nabwa_se_refine_strided(nabwa_index_t *ix, int n, const int64_t *off, const 
 	const bool timing = getenv("NABWA_TIMING") != 0;
 	const double t2 = now_s();
 	size_t n_jobs = 0;
+	/* NABWA_FINISH=gpu: windows, CIGAR rules and MD / NM on the device (finish_gpu.hip), the reads uploaded once for both */
+	const int fin_mode = nabwa_finish_mode();
+	if (fin_mode < 0) return nabwa_fail(NABWA_EINVAL, "NABWA_FINISH: host or gpu");
+	std::unique_ptr<FinGpu> gpu;
+	if (fin_mode == 1) {
+		nabwa_finish_count_chain_call();
+		gpu.reset(new FinGpu(ix));
+		if (n) if (const int r = gpu->set_reads(off[n], seq, rseq)) return r;
+	}
 	{
-		int r = refine_batch(ix, out_base, stride, n, off, seq, rseq, &n_jobs);
+		int r = refine_batch(ix, out_base, stride, n, off, seq, rseq, &n_jobs, nullptr, gpu.get());
 		if (r != NABWA_OK) return r;
 	}
 	const double t3 = now_s();
+	if (gpu && n) if (const int r = gpu->md_records(0, out_base, stride, n, off)) return r;
 	/* host threads: MD / NM, trimmed tail, flags (bwase.c:253-354, :458-571); records are independent */
 	int md_over = 0;
 	auto phase4 = [&](int lo, int hi) {
@@ -268,16 +281,18 @@ int nabwa_se_refine_strided(nabwa_index_t *ix, int n, const int64_t *off, const 
 			/* what a record needs lies far apart -- its head and its MD field in a 3 KB record, its window in 775 MB of packed reference --, and
 			 * every piece was a cache miss in turn: the record 16 ahead and the window of the record 8 ahead are asked for now */
 			if (i + 16 < hi) { const nabwa_se_t *const f = rec_at(out_base, stride, i + 16); __builtin_prefetch(f); __builtin_prefetch(f->md, 1); __builtin_prefetch(&f->flag, 1); }
-			if (i + 8 < hi) { const nabwa_se_t *const f = rec_at(out_base, stride, i + 8); if (f->type) { const uint8_t *const w = R->pac.data() + (f->pos >> 2); __builtin_prefetch(w); __builtin_prefetch(w + 32); } }
+			if (!gpu && i + 8 < hi) { const nabwa_se_t *const f = rec_at(out_base, stride, i + 8); if (f->type) { const uint8_t *const w = R->pac.data() + (f->pos >> 2); __builtin_prefetch(w); __builtin_prefetch(w + 32); } }
 			nabwa_se_t &s = *rec_at(out_base, stride, i);
 			if (s.type == 0) { s.flag = 4; continue; }
-			if (!md_and_trim(R, s, seq + off[i], rseq + off[i], fwd)) md_over = 1;
+			if (gpu) { if (!gpu->take_md(i, s)) md_over = 1; correct_trimmed(s); }      /* MD / NM came from the device */
+			else if (!md_and_trim(R, s, seq + off[i], rseq + off[i], fwd)) md_over = 1;
 			se_flags(R, s);
 		}
 	};
 	host_parallel(host_threads((size_t)n, 4096), (size_t)n, [&](int, size_t lo, size_t hi) { phase4((int)lo, (int)hi); });
 	if (md_over) return nabwa_fail(NABWA_ECAP, "MD string longer than NABWA_MAX_MD");
 	if (timing) fprintf(stderr, "[nabwa] se_refine %d reads: refinement (%zu jobs) %.3f s, md/flags %.3f s\n", n, n_jobs, t3 - t2, now_s() - t3);
+	if (gpu) gpu->report("se_refine");
 	return NABWA_OK;
 }
 

@@ -1,0 +1,319 @@
+"""The finishing chains' device path (NABWA_FINISH=gpu; csrc/finish_kernels.hip, finish_gpu.hip) on the GPU box:
+ * nabwa_refine_gapped_core and nabwa_cal_md on every case of tests/golden/vectors_refine.npz -- what the reference's bwa_refine_gapped
+   made of the same hits (tests/golden/make_golden_refine.py);
+ * the single-end, paired and colour-space chains and nabwa_bam2bam with the variable unset and with NABWA_FINISH=gpu: every field of
+   every record equal, both equal to the reference's SAM; nabwa_finish_counts moves under `gpu` by exactly the jobs and mapped records of
+   the batch and not at all under `host`;
+ * the reference in HBM is counted in nabwa_index_device_bytes once."""
+import ctypes as C
+import gzip
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import finish_cases as F
+import nabwa_testlib as T
+
+nabwa = importlib.import_module("network-aware-bwa_amd")
+pytestmark = pytest.mark.gpu
+PKG = os.path.dirname(nabwa.LIB_PATH)
+
+
+@pytest.fixture(scope="module")
+def ix():
+    x = nabwa.Index.load(T.TOY, 0, True, True)
+    yield x
+    x.close()
+
+
+def flat(queries):
+    off = np.concatenate([[0], np.cumsum([len(q) for q in queries])]).astype(np.int64)
+    return np.concatenate(queries), off
+
+
+# ------------------------------------------------------------------------------------------------- the two entry points on the fixture
+
+def test_refine_gapped_core_on_every_fixture_case(ix):
+    cs = [c for c in F.cases() if c.gapped]
+    assert len(cs) > 200
+    before = nabwa.finish_counts()
+    qry, off = flat([c.query for c in cs])
+    pos, cigs = ix.refine_gapped_core(qry, off, [c.ext for c in cs], [c.pos for c in cs])
+    bad = [(i, c.tag, int(pos[i]), c.pos_out, T.cigar16_str(cigs[i]), T.cigar16_str(c.cigar)) for i, c in enumerate(cs)
+           if int(pos[i]) != c.pos_out or cigs[i].tolist() != c.cigar.tolist()]
+    assert not bad, (len(bad), bad[:5])
+    assert nabwa.finish_counts()[0] - before[0] == len(cs)
+    # the same split into two calls: a job's answer does not depend on its batch
+    cut = len(cs) // 3
+    for part in (cs[:cut], cs[cut:]):
+        q2, o2 = flat([c.query for c in part])
+        p2, c2 = ix.refine_gapped_core(q2, o2, [c.ext for c in part], [c.pos for c in part])
+        assert [int(x) for x in p2] == [c.pos_out for c in part]
+        assert [x.tolist() for x in c2] == [c.cigar.tolist() for c in part]
+
+
+def test_refine_gapped_core_reports_a_row_that_is_too_narrow(ix):
+    cs = [c for c in F.cases() if c.gapped and len(c.cigar) >= 3][:5]
+    qry, off = flat([c.query for c in cs])
+    with pytest.raises(nabwa.NabwaError) as e:
+        ix.refine_gapped_core(qry, off, [c.ext for c in cs], [c.pos for c in cs], max_cigar=2)
+    assert e.value.code == nabwa.ECAP
+
+
+def test_cal_md_on_every_fixture_case(ix):
+    cs = F.cases()                                               # gapped and ungapped: an empty CIGAR is the ungapped branch
+    before = nabwa.finish_counts()
+    qry, off = flat([c.query for c in cs])
+    nm, md = ix.cal_md(qry, off, [c.pos_out for c in cs], [c.cigar for c in cs])
+    bad = [(i, c.tag, int(nm[i]), c.nm, md[i], c.md) for i, c in enumerate(cs) if int(nm[i]) != c.nm or md[i] != c.md]
+    assert not bad, (len(bad), bad[:5])
+    assert nabwa.finish_counts()[1] - before[1] == 2 * len(cs)  # (the wrapper sizes the buffer with a first call)
+    # one byte short: NABWA_ECAP and the size that is needed; the retry with that size succeeds
+    need = sum(len(c.md) + 1 for c in cs)
+    with pytest.raises(nabwa.NabwaError) as e:
+        ix.cal_md(qry, off, [c.pos_out for c in cs], [c.cigar for c in cs], md_cap=need - 1)
+    assert e.value.code == nabwa.ECAP
+    L = nabwa.lib()
+    n = len(cs)
+    width = max(len(c.cigar) for c in cs)
+    cig = np.zeros((n, width), np.uint16)
+    for i, c in enumerate(cs):
+        cig[i, :len(c.cigar)] = c.cigar
+    ncig = np.array([len(c.cigar) for c in cs], np.int32)
+    pos = np.array([c.pos_out for c in cs], np.uint32)
+    nm2, mo, buf = np.zeros(n, np.int32), np.zeros(n + 1, np.int64), np.zeros(need, np.uint8)
+    args = [ix._h, 0, n, T.ptr(off), T.ptr(qry), T.ptr(pos), T.ptr(ncig), T.ptr(cig), width, T.ptr(nm2), T.ptr(mo), T.ptr(buf)]
+    assert L.nabwa_cal_md(*args, need - 1) == nabwa.ECAP and int(mo[n]) == need
+    assert L.nabwa_cal_md(*args, need) == nabwa.OK
+    assert buf.tobytes() == b"".join(c.md.encode() + b"\0" for c in cs)
+
+
+def test_entry_points_refuse_what_has_no_answer(ix):
+    c = [c for c in F.cases() if not c.gapped][0]
+    qry, off = flat([c.query])
+    with pytest.raises(nabwa.NabwaError) as e:                  # an ungapped record past the end of the text: the reference reads outside its array
+        ix.cal_md(qry, off, [F.L_PAC - c.len + 1], [np.zeros(0, np.uint16)])
+    assert e.value.code == nabwa.EINVAL
+    with pytest.raises(nabwa.NabwaError) as e:                  # no nucleotide reference on a nucleotide index
+        ix.cal_md(qry, off, [1000], [np.zeros(0, np.uint16)], which_ref=1)
+    assert e.value.code == nabwa.EINVAL
+    bare = nabwa.Index.load(T.TOY, 0, True, False)              # no reference attached
+    try:
+        with pytest.raises(nabwa.NabwaError) as e:
+            bare.refine_gapped_core(qry, off, [1], [1000])
+        assert e.value.code == nabwa.EINVAL
+    finally:
+        bare.close()
+
+
+def test_reference_in_hbm_is_counted_once():
+    x = nabwa.Index.load(T.TOY, 0, True, True)
+    try:
+        cs = [c for c in F.cases() if c.gapped][:4]
+        qry, off = flat([c.query for c in cs])
+        b0, held0 = x.device_bytes(), nabwa.finish_counts()[3]
+        x.refine_gapped_core(qry, off, [c.ext for c in cs], [c.pos for c in cs])
+        b1 = x.device_bytes()
+        grew = F.L_PAC // 4 + 1 + 16 * 3                        # the pac, and the table of the toy index's three holes (16 bytes each)
+        assert b1 - b0 == grew and nabwa.finish_counts()[3] - held0 == grew
+        x.refine_gapped_core(qry, off, [c.ext for c in cs], [c.pos for c in cs])
+        x.cal_md(qry, off, [c.pos_out for c in cs], [c.cigar for c in cs])
+        assert x.device_bytes() == b1
+        x.attach_reference(T.TOY)                               # a new reference replaces the copies: gone until the next call needs them
+        assert x.device_bytes() == b0
+        x.cal_md(qry, off, [c.pos_out for c in cs], [c.cigar for c in cs])
+        assert x.device_bytes() == b1
+    finally:
+        x.close()
+    assert nabwa.finish_counts()[3] == held0
+
+
+# ------------------------------------------------------------------------------------------------- the chains
+
+def se_fields(s):
+    return (s.type, s.strand, s.n_mm, s.n_gapo, s.n_gape, s.score, s.sa, s.pos, s.c1, s.c2, s.mapQ, s.seQ, s.len, s.full_len, s.clip_len,
+            tuple(s.cigar[:s.n_cigar]), s.nm, s.md.decode(), s.flag, s.seqid, s.nn, s.rpos, s.xt,
+            tuple((m.pos, m.gap, m.mm, m.strand, tuple(m.cigar[:m.n_cigar])) for m in s.multi[:s.n_multi]))
+
+
+def n_jobs_and_mapped(recs):
+    jobs = sum((1 if s.type not in (0, 3) and s.n_gapo else 0) + sum(1 for m in s.multi[:s.n_multi] if m.gap) for s in recs)
+    return jobs, sum(1 for s in recs if s.type != 0)
+
+
+def set_mode(monkeypatch, mode):
+    if mode is None:
+        monkeypatch.delenv("NABWA_FINISH", raising=False)
+    else:
+        monkeypatch.setenv("NABWA_FINISH", mode)
+
+
+def run_se(ix, name, monkeypatch, mode):
+    set_mode(monkeypatch, mode)
+    opt, _ = T.read_sai(os.path.join(T.GOLDEN, "se_%s.sai" % name))
+    reads = T.read_fastq(os.path.join(T.GOLDEN, "reads_se.fq"))
+    seq, rseq, off, full = T.encode_reads(reads, opt.trim_qual)
+    g = nabwa.GapOpt()
+    C.memmove(C.byref(g), C.byref(opt), 64)
+    hits, _ = ix.cal_sa_reg_gap(g, seq, rseq, off, per_read=False)
+    cut, st, recs, keep = 301, nabwa.srand48_state(11), [], []
+    before = nabwa.finish_counts()
+    for lo, hi in ((0, cut), (cut, len(reads))):
+        o = off[lo:hi + 1] - off[lo]
+        out, st = ix.se_finish(g, seq[off[lo]:off[hi]], rseq[off[lo]:off[hi]], o, full[lo:hi], hits[lo:hi], 3, st)
+        keep.append(out)
+        recs.extend(out[i] for i in range(hi - lo))
+    after = nabwa.finish_counts()
+    return opt, reads, recs, [a - b for a, b in zip(after, before)], keep
+
+
+def check_se_against_sam(opt, reads, recs, sam):
+    names, offs = ["chr1", "chr2", "chr3"], [0, 60000, 100000]
+    for rd, r, gsam in zip(reads, recs, sam):
+        assert gsam["name"] == rd[0] and r.flag == gsam["flag"], rd[0]
+        if r.type == 0:
+            continue
+        assert names[r.seqid] == gsam["rname"] and r.rpos == gsam["pos"] and r.mapQ == gsam["mapq"], rd[0]
+        assert (T.cigar16_str(r.cigar[:r.n_cigar]) if r.n_cigar else "%dM" % r.len) == gsam["cigar"], rd[0]
+        tg = gsam["tags"]
+        assert r.xt.decode() == tg["XT"] and r.nm == tg["NM"] and r.md.decode() == tg["MD"], rd[0]
+        xa = ""
+        for m in r.multi[:r.n_multi]:
+            mc = T.cigar16_str(m.cigar[:m.n_cigar]) if m.n_cigar else "%dM" % r.len
+            sid = max(k for k, o in enumerate(offs) if m.pos >= o)
+            xa += "%s,%s%d,%s,%d;" % (names[sid], "-" if m.strand else "+", m.pos - offs[sid] + 1, mc, m.gap + m.mm)
+        assert xa == tg.get("XA", ""), rd[0]
+
+
+@pytest.mark.parametrize("name", ["default", "adna", "q20"])
+def test_se_chain_is_the_same_on_the_device_path(ix, monkeypatch, name):
+    opt, reads, host, moved_host, _k1 = run_se(ix, name, monkeypatch, None)
+    _, _, gpu, moved_gpu, _k2 = run_se(ix, name, monkeypatch, "gpu")
+    bad = [(reads[i][0], se_fields(a), se_fields(b)) for i, (a, b) in enumerate(zip(host, gpu)) if se_fields(a) != se_fields(b)]
+    assert not bad, (len(bad), bad[:3])
+    sam = T.parse_sam(os.path.join(T.GOLDEN, "se_%s.sam" % name))
+    check_se_against_sam(opt, reads, host, sam)
+    check_se_against_sam(opt, reads, gpu, sam)
+    # the counters: the device path ran where it was asked for, on exactly the batch's jobs and mapped records, and nowhere else
+    jobs, mapped = n_jobs_and_mapped(host)
+    assert jobs > 0 and mapped > 400
+    assert moved_host[:3] == [0, 0, 0]
+    assert moved_gpu[:3] == [jobs, mapped, 2]
+    _, _, again, moved, _k3 = run_se(ix, name, monkeypatch, "host")
+    assert moved[:3] == [0, 0, 0] and [se_fields(a) for a in again] == [se_fields(a) for a in host]
+
+
+def test_chain_refuses_an_unknown_value(ix, monkeypatch):
+    with pytest.raises(nabwa.NabwaError) as e:
+        run_se(ix, "default", monkeypatch, "cpu")
+    assert e.value.code == nabwa.EINVAL
+
+
+def pe_fields(r):
+    return se_fields(r.se) + (r.extra_flag, r.m_seqid, r.am, r.mapQ_paired, r.m_rpos, r.isize)
+
+
+def run_pe(ix, monkeypatch, mode):
+    set_mode(monkeypatch, mode)
+    fq = [T.read_fastq(os.path.join(T.GOLDEN, "reads_pe150_%d.fq" % e)) for e in (1, 2)]
+    sai = [T.read_sai(os.path.join(T.GOLDEN, "pe150_%d.sai" % e)) for e in (1, 2)]
+    n = len(fq[0])
+    inter = [fq[e][i] for i in range(n) for e in range(2)]
+    hits = [sai[e][1][i] for i in range(n) for e in range(2)]
+    seq, rseq, off, full = T.encode_reads(inter)
+    opt = sai[1][0]
+    recs, _ = ix.pe_posn(opt, off, full, hits, nabwa.srand48_state(11))
+    iv = np.load(os.path.join(T.GOLDEN, "vectors_pe150_chain.npz"))["ii_sampe"]
+    ii = nabwa.IsizeInfo(iv[0], iv[1], iv[2], int(iv[3]), int(iv[4]), int(iv[5]))
+    before = nabwa.finish_counts()
+    ix.pe_finish(opt, nabwa.pe_opt_default(), ii, seq, rseq, off, hits, recs)
+    after = nabwa.finish_counts()
+    return recs, 2 * n, [a - b for a, b in zip(after, before)]
+
+
+def test_pe_chain_is_the_same_on_the_device_path(ix, monkeypatch):
+    host, n, moved_host = run_pe(ix, monkeypatch, None)
+    gpu, _, moved_gpu = run_pe(ix, monkeypatch, "gpu")
+    bad = [(i, pe_fields(host[i]), pe_fields(gpu[i])) for i in range(n) if pe_fields(host[i]) != pe_fields(gpu[i])]
+    assert not bad, (len(bad), bad[:3])
+    ends = [host[i].se for i in range(n)]
+    jobs, mapped = n_jobs_and_mapped(ends)
+    assert sum(1 for s in ends if any(m.n_cigar for m in s.multi[:s.n_multi])) > 0          # multi-hit CIGARs are among what is compared
+    assert sum(1 for s in ends if s.type == 3) > 0                                           # and rescued mates: MD / NM without a refinement
+    assert moved_host[:3] == [0, 0, 0] and moved_gpu[:3] == [jobs, mapped, 1]
+    # and both are what the reference's sampe printed
+    sam = T.parse_sam(os.path.join(T.GOLDEN, "pe150_default.sam"))
+    for r, w in enumerate(sam):
+        s = gpu[r].se
+        assert s.flag == w["flag"], r
+        if s.type == 0:
+            continue
+        assert (T.cigar16_str(s.cigar[:s.n_cigar]) if s.n_cigar else "%dM" % s.len) == w["cigar"] and s.rpos == w["pos"], r
+        assert w["tags"]["MD"] == s.md.decode() and w["tags"]["NM"] == s.nm, r
+
+
+def test_md_over_the_field_is_ecap_under_both_settings(ix, monkeypatch):
+    """a positioned record whose every base differs: 300 tokens of two characters do not fit NABWA_MAX_MD"""
+    L = nabwa.lib()
+    L.nabwa_se_refine.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    k = np.arange(1000, 1300)
+    pac = F.toy_pac()
+    base = (pac[k >> 2] >> ((~k & 3) << 1) & 3).astype(np.uint8)
+    q = ((base + 1) & 3).astype(np.uint8)                       # alignment orientation; the record is on the reverse strand: the query is rseq
+    rseq, seq = q, (3 - q).astype(np.uint8)
+    off = np.array([0, 300], np.int64)
+    for mode in (None, "host", "gpu"):
+        set_mode(monkeypatch, mode)
+        rec = (nabwa.SeRec * 1)()
+        rec[0].type, rec[0].strand, rec[0].pos, rec[0].len, rec[0].full_len, rec[0].clip_len = 1, 1, 1000, 300, 300, 300
+        rc = L.nabwa_se_refine(ix._h, 1, T.ptr(off), T.ptr(seq), T.ptr(rseq), rec)
+        assert rc == nabwa.ECAP, (mode, rc)
+        assert b"NABWA_MAX_MD" in L.nabwa_last_error()
+
+
+# ------------------------------------------------------------------------------------------------- the tools
+
+def test_colour_space_chain_is_the_same_on_the_device_path(tmp_path):
+    """nabwa_se_finish_cs through nabwa_samse on the colour golden: the second refinement runs with is_end_correct = 0 on the nucleotide
+    pac (which_ref = 1), and MD / NM come from there"""
+    from test_gpu_sai2sam import INDEX, SAMSE, assert_same_sam, run
+    prefix = str(tmp_path / "toycs")
+    run([INDEX, "-c", "-p", prefix, T.TOY + ".fa"], timeout=600)
+    G = lambda x: os.path.join(T.GOLDEN, x)
+    cmd = [SAMSE, prefix, G("cs_se.sai"), G("reads_cs_se.fq.gz")]
+    out = {}
+    for mode in ("host", "gpu"):
+        r = subprocess.run(cmd, capture_output=True, env=dict(os.environ, NABWA_FINISH=mode, NABWA_TIMING="1"), timeout=300)
+        assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
+        out[mode] = r
+    want = gzip.open(G("cs_se.sam.gz"), "rb").read()
+    assert out["host"].stdout == out["gpu"].stdout
+    assert_same_sam(out["gpu"].stdout, want)
+    assert b"se_finish_cs device path" in out["gpu"].stderr and b"device path" not in out["host"].stderr
+    assert any(b"I" in l.split(b"\t")[5] or b"D" in l.split(b"\t")[5] for l in want.splitlines() if not l.startswith(b"@"))
+
+
+def test_bam2bam_writes_the_same_bytes_on_the_device_path(tmp_path):
+    import bamlib as B
+    from test_gpu_bam import pe_records
+    from test_gpu_bam2bam_cli import EXE, write_bam
+    reads = T.read_fastq(os.path.join(T.GOLDEN, "reads_se.fq"))[:40]
+    singles = [B.make_record(n, s, q, 4) for n, s, q in reads]
+    pairs, _ = pe_records()
+    inp, outp = str(tmp_path / "in.bam"), str(tmp_path / "out.bam")
+    write_bam(inp, singles + pairs[:120] + singles[:10], True)
+    got = {}
+    for mode in (None, "gpu"):
+        env = dict(os.environ, NABWA_BAM_BATCH="16", NABWA_TIMING="1")
+        env.pop("NABWA_FINISH", None)
+        if mode:
+            env["NABWA_FINISH"] = mode
+        r = subprocess.run([EXE, "-g", T.TOY, "-f", outp + "_", inp], capture_output=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
+        got[mode] = (gzip.decompress(open(outp, "rb").read()), r.stderr)
+        os.remove(outp)
+    assert got[None][0] == got["gpu"][0] and len(got["gpu"][0]) > 10000
+    assert b"device path" in got["gpu"][1] and b"device path" not in got[None][1]

@@ -90,7 +90,20 @@ int nabwa_cal_sa_reg_gap(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, c
 						 int32_t *max_entries);
 
 /* Device-resident variant for pipelines and for bench.py: upload once, run many times.
- * A batch owns the device copies of the reads, the per-lane search scratch and the outputs. */
+ * A batch owns the device copies of the reads, the per-lane search scratch and the outputs.
+ *
+ * NABWA_DEDUP (read by nabwa_batch_create, and so by everything built on it: nabwa_cal_sa_reg_gap, nabwa_bwa_cal_sa_reg_gap,
+ * nabwa_bam_batch_search, the worker core, nabwa_aln, nabwa_bam2bam): unset or 0 -- every read is searched; 1 -- reads of the batch that are
+ * equal in length and in every byte of seq and of rseq are found on the device and searched once; any other value is NABWA_EINVAL before any
+ * device work.  What the caller sees is byte for byte what it sees without the switch: nabwa_batch_fetch (n_aln[], max_entries[], the rows in
+ * the caller's read order, NABWA_ECAP with *n_rows the caller's total), nabwa_batch_checksum, nabwa_batch_width_records (first and n are the
+ * caller's read indices) and nabwa_batch_config's n, min_len and max_len speak of the n reads given.  The diagnostics count the work done, that
+ * is the reads searched: nabwa_batch_count_touches, *n_second_pass of nabwa_batch_sync, nabwa_batch_sure0_stats*, and cls[], n_sync and
+ * hard_budget of nabwa_batch_config.  A batch without two equal reads, and one of no reads, is the batch it is without the switch.
+ * NABWA_DEDUP_HASH_BITS=k (tests; 0..64, default 64, else NABWA_EINVAL; read only with NABWA_DEDUP=1): group the reads by the low k bits of
+ * their hash only.  Reads that share a group and differ are searched on their own (the bytes are compared before two reads merge), so the
+ * results do not change; with 0 every read shares one group.
+ * With NABWA_TIMING the stage writes one line per batch to stderr: reads given, reads searched, collisions, its time by HIP events. */
 typedef struct nabwa_batch nabwa_batch_t;
 int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, const int64_t *off,
 					   const uint8_t *seq, const uint8_t *rseq, int per_read, nabwa_batch_t **out);
@@ -139,6 +152,10 @@ int nabwa_batch_sure0_stats(nabwa_batch_t *b, uint64_t out[4]);
  * that occurs exactly, replaced by its hit), out[5] levels leapt over, out[6] such entries that walked instead because their text position was
  * short of the levels left (expected 0), out[7] 0. */
 int nabwa_batch_sure0_stats_ex(nabwa_batch_t *b, uint64_t out[8]);
+/* what NABWA_DEDUP did for this batch: out[0] reads given, out[1] reads searched, out[2] reads that shared a hash with an earlier read of the
+ * batch but differ from the first read of that hash (each is searched on its own and counts in out[1]), out[3] 1 when the batch was created
+ * with the switch on, else 0.  Without the switch: { n, n, 0, 0 }. */
+int nabwa_batch_dedup_stats(nabwa_batch_t *b, uint64_t out[4]);
 void nabwa_batch_destroy(nabwa_batch_t *b);
 
 /* ---- paired-end host pieces (config 3) --------------------------------------------------------- */

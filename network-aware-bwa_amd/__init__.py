@@ -316,6 +316,9 @@ def lib():
     if hasattr(L, "nabwa_batch_sure0_stats_ex"):
         L.nabwa_batch_sure0_stats_ex.restype = C.c_int
         L.nabwa_batch_sure0_stats_ex.argtypes = [_P, _P]
+    if hasattr(L, "nabwa_batch_dedup_stats"):
+        L.nabwa_batch_dedup_stats.restype = C.c_int
+        L.nabwa_batch_dedup_stats.argtypes = [_P, _P]
     L.nabwa_dp_form_counts.argtypes = [_P, C.c_int]
     L.nabwa_dp_form_counts.restype = None
     L.nabwa_batch_destroy.argtypes = [_P]
@@ -881,6 +884,13 @@ class Batch:
         (nabwa_batch_sure0_stats_ex; NABWA_SURE0=3)"""
         out = (C.c_uint64 * 8)()
         _chk(lib().nabwa_batch_sure0_stats_ex(self._h, out))
+        return [int(x) for x in out]
+
+    def dedup_stats(self):
+        """[reads given, reads searched, reads whose hash met that of an earlier read they differ from, 1 if the batch was created with
+        NABWA_DEDUP=1 else 0] (nabwa_batch_dedup_stats); without the switch [n, n, 0, 0]"""
+        out = (C.c_uint64 * 4)()
+        _chk(lib().nabwa_batch_dedup_stats(self._h, out))
         return [int(x) for x in out]
 
     def close(self):

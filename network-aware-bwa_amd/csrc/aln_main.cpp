@@ -359,6 +359,7 @@ int main(int argc, char *argv[])
 			k = l;
 		}
 	const char *prefix = argv[optind], *reads = argv[optind + 1];
+	if (!tool_dedup_ok()) return 1;      /* NABWA_DEDUP: the search batches read it (include/nabwa.h); a bad value ends the run before the index is loaded */
 
 	// ---- the reads: nothing is written before they can be opened
 	Source src; BamReader bam;

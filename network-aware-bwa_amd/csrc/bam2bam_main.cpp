@@ -246,6 +246,7 @@ static int parse_options(int argc, char **argv, Options &o)
 	 * every call); a value it would refuse is refused here, before the index is loaded */
 	const char *finish_env = getenv("NABWA_FINISH");
 	if (finish_env && strcmp(finish_env, "gpu") && strcmp(finish_env, "host")) { fprintf(stderr, "[nabwa_bam2bam] NABWA_FINISH=%s: host or gpu\n", finish_env); return 1; }
+	if (!tool_dedup_ok()) return 1;      /* NABWA_DEDUP: the search batches read it (include/nabwa.h) */
 	return -1;
 }
 

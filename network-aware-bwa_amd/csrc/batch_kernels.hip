@@ -201,26 +201,28 @@ __device__ __forceinline__ const uint4 *rows_of(int i, const uint4 *aln, int aln
 	return st == NABWA_ST_WIDE ? aln2 + (size_t)wide_idx[i] * aln_cap2 : aln + (size_t)i * aln_cap;
 }
 
-// compaction: rows of read i go to out[row_off[i] ...]
-__global__ __launch_bounds__(256) void gather_kernel(int n, const int32_t *__restrict__ n_aln, const uint32_t *__restrict__ row_off,
+// compaction: rows of read i go to out[row_off[i] ...].  map: null, or the read whose rows read i takes (NABWA_DEDUP: n and row_off are the
+// caller's, n_aln and the rows those of the reads searched)
+__global__ __launch_bounds__(256) void gather_kernel(int n, const int32_t *__restrict__ map, const int32_t *__restrict__ n_aln, const uint32_t *__restrict__ row_off,
 												 const uint4 *__restrict__ aln, int aln_cap, const uint8_t *__restrict__ status,
 												 const int32_t *__restrict__ wide_idx, const uint4 *__restrict__ aln2, int aln_cap2,
 												 const uint4 *const *__restrict__ grown, uint4 *__restrict__ out)
 {
 	const int i = blockIdx.x * 256 + threadIdx.x;
 	if (i >= n) return;
-	const int na = n_aln[i];
-	const uint4 *src = rows_of(i, aln, aln_cap, status, wide_idx, aln2, aln_cap2, grown);
+	const int rd = map ? map[i] : i;
+	const int na = n_aln[rd];
+	const uint4 *src = rows_of(rd, aln, aln_cap, status, wide_idx, aln2, aln_cap2, grown);
 	uint4 *dst = out + row_off[i];
 	for (int j = 0; j < na; ++j) dst[j] = src[j];
 }
 
-extern "C" void nabwa_launch_gather(int n, const int32_t *n_aln, const uint32_t *row_off, const uint4 *aln, int aln_cap,
+extern "C" void nabwa_launch_gather(int n, const int32_t *map, const int32_t *n_aln, const uint32_t *row_off, const uint4 *aln, int aln_cap,
 									const uint8_t *status, const int32_t *wide_idx, const uint4 *aln2, int aln_cap2,
 									const uint4 *const *grown, uint4 *out, hipStream_t s)
 {
 	if (n <= 0) return;
-	hipLaunchKernelGGL(gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, n_aln, row_off, aln, aln_cap, status,
+	hipLaunchKernelGGL(gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, map, n_aln, row_off, aln, aln_cap, status,
 					   wide_idx, aln2, aln_cap2, grown, out);
 }
 
@@ -231,7 +233,8 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x)
 	return x;
 }
 
-__global__ __launch_bounds__(256) void checksum_kernel(int n, const int32_t *__restrict__ n_aln, const uint4 *__restrict__ aln,
+// (map as in gather_kernel: read i, the caller's, is summed with the rows of read map[i])
+__global__ __launch_bounds__(256) void checksum_kernel(int n, const int32_t *__restrict__ map, const int32_t *__restrict__ n_aln, const uint4 *__restrict__ aln,
 												   int aln_cap, const uint8_t *__restrict__ status, const int32_t *__restrict__ wide_idx,
 												   const uint4 *__restrict__ aln2, int aln_cap2, const uint4 *const *__restrict__ grown,
 												   unsigned long long *__restrict__ sum, unsigned long long *__restrict__ rows)
@@ -239,8 +242,9 @@ __global__ __launch_bounds__(256) void checksum_kernel(int n, const int32_t *__r
 	const int i = blockIdx.x * 256 + threadIdx.x;
 	uint64_t s = 0, r = 0;
 	if (i < n) {
-		const int na = n_aln[i];
-		const uint4 *src = rows_of(i, aln, aln_cap, status, wide_idx, aln2, aln_cap2, grown);
+		const int rd = map ? map[i] : i;
+		const int na = n_aln[rd];
+		const uint4 *src = rows_of(rd, aln, aln_cap, status, wide_idx, aln2, aln_cap2, grown);
 		r = (uint64_t)na;
 		s = mix64(((uint64_t)i << 20) ^ (uint64_t)na ^ 0x9e3779b97f4a7c15ULL);
 		for (int j = 0; j < na; ++j) {
@@ -252,12 +256,12 @@ __global__ __launch_bounds__(256) void checksum_kernel(int n, const int32_t *__r
 	if ((threadIdx.x & 63) == 0) { atomicAdd(sum, (unsigned long long)s); atomicAdd(rows, (unsigned long long)r); }
 }
 
-extern "C" void nabwa_launch_checksum(int n, const int32_t *n_aln, const uint4 *aln, int aln_cap, const uint8_t *status,
+extern "C" void nabwa_launch_checksum(int n, const int32_t *map, const int32_t *n_aln, const uint4 *aln, int aln_cap, const uint8_t *status,
 									  const int32_t *wide_idx, const uint4 *aln2, int aln_cap2,
 									  const uint4 *const *grown, unsigned long long *sum, unsigned long long *rows, hipStream_t s)
 {
 	if (n <= 0) return;
-	hipLaunchKernelGGL(checksum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, n_aln, aln, aln_cap, status, wide_idx,
+	hipLaunchKernelGGL(checksum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, map, n_aln, aln, aln_cap, status, wide_idx,
 					   aln2, aln_cap2, grown, sum, rows);
 }
 

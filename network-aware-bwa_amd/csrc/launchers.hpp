@@ -1,4 +1,4 @@
-// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, bgzf_deflate.hip, bgzf_inflate.hip and finish_kernels.hip, declared once.
+// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, dedup_kernels.hip, bgzf_deflate.hip, bgzf_inflate.hip and finish_kernels.hip, declared once.
 // The defining files and every host unit that calls one include this header, so a parameter list that differs between the two sides
 // is a compile error (C linkage carries no types).  Host side only: the kernel headers (nabwa_dev.hpp, fm_search.hpp, fm_deep.hpp,
 // fm_deep_body.hpp) do not include it -- the CPU emulation of the tests compiles those without HIP.
@@ -20,7 +20,8 @@ void nabwa_launch_fm_width(const SearchParams *P, int n_blocks, hipStream_t s);
 int nabwa_width_occupancy(void);
 int nabwa_search_occupancy(int ns);
 /* batch_kernels.hip */
-void nabwa_launch_checksum(int n, const int32_t *n_aln, const uint4 *aln, int aln_cap, const uint8_t *status,
+/* map (checksum, gather): null, or for each of the n reads the read whose results it takes (NABWA_DEDUP: the caller's read -> the read searched) */
+void nabwa_launch_checksum(int n, const int32_t *map, const int32_t *n_aln, const uint4 *aln, int aln_cap, const uint8_t *status,
 						   const int32_t *wide_idx, const uint4 *aln2, int aln_cap2, const uint4 *const *grown,
 						   unsigned long long *sum, unsigned long long *rows, hipStream_t s);
 void nabwa_launch_collect(int n, const uint8_t *status, int32_t *ids, unsigned int *count, int which, hipStream_t s);
@@ -33,7 +34,7 @@ void nabwa_launch_scatter_grown(int n2, const int32_t *ids, const int32_t *n_aln
 void nabwa_launch_scatter_wide(int n2, const int32_t *ids, const int32_t *n_aln2, const int32_t *max_ent2,
 							   const uint8_t *status2, int32_t *n_aln, int32_t *max_ent, uint8_t *status,
 							   int32_t *wide_idx, hipStream_t s);
-void nabwa_launch_gather(int n, const int32_t *n_aln, const uint32_t *row_off, const uint4 *aln, int aln_cap,
+void nabwa_launch_gather(int n, const int32_t *map, const int32_t *n_aln, const uint32_t *row_off, const uint4 *aln, int aln_cap,
 						 const uint8_t *status, const int32_t *wide_idx, const uint4 *aln2, int aln_cap2,
 						 const uint4 *const *grown, uint4 *out, hipStream_t s);
 void nabwa_launch_partition(int n, const uint8_t *cls, int32_t *ids, unsigned int *cnt, hipStream_t s);
@@ -41,6 +42,16 @@ void nabwa_launch_padded_len(int n, const int64_t *off, int64_t *plen, hipStream
 void nabwa_launch_pad_reads(int n, const uint8_t *seq, const uint8_t *rseq, const int64_t *off, const int64_t *poff,
 							uint8_t *pseq, uint8_t *prseq, int32_t *rd_len, uint32_t *rd_key, int T, int seed_len, uint32_t *rd_pack, int pack_stride,
 							const uint8_t *md_tab, const uint8_t *mg_tab, uint8_t *rd_md, uint8_t *rd_mg, hipStream_t s);
+/* dedup_kernels.hip (dedup_body.hpp): the duplicate-read stage of a batch, in the order nabwa_batch.hip runs it.  16 lanes per read in hash, verify
+ * and compact; no kernel reads seq / rseq at or beyond off[n] or writes the compact buffers at or beyond coff[n_u] */
+void nabwa_launch_dedup_hash(int n, const uint8_t *seq, const uint8_t *rseq, const int64_t *off, uint64_t mask, uint64_t *keys, uint32_t *ids, hipStream_t s);
+void nabwa_launch_dedup_heads(int n, const uint64_t *keys, uint32_t *head, hipStream_t s);
+void nabwa_launch_dedup_verify(int n, const uint8_t *seq, const uint8_t *rseq, const int64_t *off, const uint32_t *ids, const uint32_t *head,
+							   int32_t *rep, uint32_t *flag, unsigned int *n_coll, hipStream_t s);
+void nabwa_launch_dedup_map(int n, const int32_t *rep, const uint32_t *inner, const int64_t *off, int32_t *map, int64_t *clen, unsigned int *stat, hipStream_t s);
+void nabwa_launch_dedup_compact(int n, const uint8_t *seq, const uint8_t *rseq, const int64_t *off, const int32_t *rep, const uint32_t *inner,
+								const int64_t *coff, uint8_t *cseq, uint8_t *crseq, hipStream_t s);
+void nabwa_launch_dedup_expand(int n, const int32_t *map, const int32_t *n_aln, const int32_t *max_ent, int32_t *n_aln_out, int32_t *max_ent_out, hipStream_t s);
 /* fm_deep.hip */
 void nabwa_launch_fm_deep(const DeepParams *P, int n_waves, hipStream_t s);
 int nabwa_deep_occupancy(int ns, int lds_rd);

@@ -118,27 +118,116 @@ static int derive_options(const nabwa_gap_opt_t *opt, int n, const int64_t *off,
 	return NABWA_OK;
 }
 
-// ---- step 2: the reads, uploaded as given, then re-laid out on the device with 16-byte aligned starts
-static int upload_reads(nabwa_batch *b, const BatchShape &s, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, bool timing, double tc0)
+// ---- step 2a, NABWA_DEDUP=1 only: search each distinct read of the batch once.  In: the raw reads of the caller's n_given reads in HBM.
+// Out, when some reads are equal in length and in the bytes of both strands: raw_s / raw_r / raw_off hold the n_u distinct reads (the first
+// of each set of equal reads, in the caller's order), b->n = n_u, and b->d_map takes each of the caller's reads to the one searched for
+// it.  Out, when all reads differ: nothing is changed and no map is kept.
+//   hash (dedup_kernels.hip) -> radix sort of (hash, read), stable: a run of equal hashes lists its reads in ascending order -> run
+//   starts by an inclusive max-scan -> every read against the first read of its run, byte for byte: equal reads merge, the others (their
+//   hashes collided) stay reads of their own, so no result rests on the hash -> exclusive sum of the representatives' flags: their inner
+//   indices -> one download (n_u, collisions) -> exclusive sum of their lengths: the compact starts -> their bytes copied.
+// bits: how many low bits of the hash the sort sees (NABWA_DEDUP_HASH_BITS, a test knob: with 0 every read lands in one run).
+// Everything runs on the batch's stream; the temporaries, about 40 bytes per read beside the compact copy of the reads, are back in the
+// pool before the working buffers are taken.
+namespace { struct DedupMax { __host__ __device__ uint32_t operator()(uint32_t a, uint32_t c) const { return a > c ? a : c; } }; }
+
+static int dedup_reads(nabwa_batch *b, int bits, PoolBuf<uint8_t> &raw_s, PoolBuf<uint8_t> &raw_r, PoolBuf<int64_t> &raw_off, size_t nb, bool timing)
 {
 	nabwa_index *ix = b->ix;
-	const int n = b->n, max_len = s.max_len;
-	const size_t nb = (size_t)off[n] > 0 ? (size_t)off[n] : 1, pnb = (size_t)s.padded_total + 64;
+	const int n = b->n_given;
+	hipStream_t st = b->stream;
+	PoolBuf<uint64_t> kA, kB; PoolBuf<uint32_t> vA, vB, head, flag, inner; PoolBuf<int32_t> rep, map; PoolBuf<unsigned int> d_stat;
+	PoolBuf<int64_t> coff; PoolBuf<uint8_t> c_s, c_r; PoolBuf<void> d_tmp;
+	DevEvent e0, e1;
+	StreamDrain drain{ st };
+	const size_t n1 = (size_t)n + 1;
+	HIP_CHECK(kA.get(ix, n1 * 8)); HIP_CHECK(kB.get(ix, n1 * 8)); HIP_CHECK(vA.get(ix, n1 * 4)); HIP_CHECK(vB.get(ix, n1 * 4));
+	HIP_CHECK(head.get(ix, n1 * 4)); HIP_CHECK(rep.get(ix, n1 * 4)); HIP_CHECK(flag.get(ix, n1 * 4)); HIP_CHECK(inner.get(ix, n1 * 4));
+	HIP_CHECK(map.get(ix, n1 * 4)); HIP_CHECK(d_stat.get(ix, 8));
+	int64_t *const clen = (int64_t*)kA.p;      /* the sort's key buffers are free once the run starts are known: the representatives' lengths go there */
+	/* one scratch buffer for the sort and the three scans: the largest of their needs */
+	size_t tmp_bytes = 16, need = 0;
+	hipcub::DoubleBuffer<uint64_t> dk(kA.p, kB.p); hipcub::DoubleBuffer<uint32_t> dv(vA.p, vB.p);
+	HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, dk, dv, n, 0, 64, st)); if (need > tmp_bytes) tmp_bytes = need;
+	HIP_CHECK(hipcub::DeviceScan::InclusiveScan(nullptr, need, head.p, head.p, DedupMax(), n, st)); if (need > tmp_bytes) tmp_bytes = need;
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, flag.p, inner.p, n + 1, st)); if (need > tmp_bytes) tmp_bytes = need;
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, clen, clen, n + 1, st)); if (need > tmp_bytes) tmp_bytes = need;
+	HIP_CHECK(d_tmp.get(ix, tmp_bytes));
+	if (timing) { HIP_CHECK(hipEventCreate(&e0.e)); HIP_CHECK(hipEventCreate(&e1.e)); HIP_CHECK(hipEventRecord(e0, st)); }
+	HIP_CHECK(hipMemsetAsync(d_stat, 0, 8, st));
+	nabwa_launch_dedup_hash(n, raw_s, raw_r, raw_off, bits >= 64 ? ~0ull : (1ull << bits) - 1ull, kA, vA, st);
+	need = tmp_bytes;
+	HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, need, dk, dv, n, 0, 64, st));
+	nabwa_launch_dedup_heads(n, dk.Current(), head, st);
+	need = tmp_bytes;
+	HIP_CHECK(hipcub::DeviceScan::InclusiveScan(d_tmp.p, need, head.p, head.p, DedupMax(), n, st));
+	nabwa_launch_dedup_verify(n, raw_s, raw_r, raw_off, dv.Current(), head, rep, flag, d_stat, st);
+	need = tmp_bytes;
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, need, flag.p, inner.p, n + 1, st));
+	nabwa_launch_dedup_map(n, rep, inner, raw_off, map, clen, d_stat, st);
+	unsigned int stat[2] = { 0, 0 };      /* collisions, distinct reads */
+	HIP_CHECK(hipMemcpyAsync(stat, d_stat, 8, hipMemcpyDeviceToHost, st));
+	HIP_CHECK(hipStreamSynchronize(st));
+	HIP_CHECK(hipGetLastError());
+	const int n_u = (int)stat[1];
+	if (n_u < 1 || n_u > n) return nabwa_fail(NABWA_EIO, "NABWA_DEDUP: the stage counted more distinct reads than reads, or none");
+	b->dedup_coll = stat[0];
+	if (n_u < n) {
+		HIP_CHECK(coff.get(ix, ((size_t)n_u + 1) * 8)); HIP_CHECK(c_s.get(ix, nb)); HIP_CHECK(c_r.get(ix, nb));
+		need = tmp_bytes;
+		HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, need, clen, coff.p, n_u + 1, st));
+		nabwa_launch_dedup_compact(n, raw_s, raw_r, raw_off, rep, inner, coff, c_s, c_r, st);
+	}
+	if (timing) HIP_CHECK(hipEventRecord(e1, st));
+	HIP_CHECK(hipStreamSynchronize(st));
+	HIP_CHECK(hipGetLastError());
+	if (timing) {
+		float ms = 0.f;
+		HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+		fprintf(stderr, "[nabwa] dedup: %d reads given, %d searched, %u hash collisions, stage %.3f ms\n", n, n_u, stat[0], ms);
+	}
+	if (n_u < n) {      /* (the stream is idle: the buffers these replace go back to the pool) */
+		raw_s = std::move(c_s); raw_r = std::move(c_r); raw_off = std::move(coff);
+		b->d_map = std::move(map);
+		b->n = n_u;
+	}
+	return NABWA_OK;
+}
+
+// ---- step 2: the reads, uploaded as given, then re-laid out on the device with 16-byte aligned starts
+// dedup_bits: -1, or with NABWA_DEDUP=1 the hash bits of dedup_reads, which then runs between the upload and the re-layout
+static int upload_reads(nabwa_batch *b, const BatchShape &s, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, bool timing, double tc0, int dedup_bits)
+{
+	nabwa_index *ix = b->ix;
+	const int n_given = b->n_given, max_len = s.max_len;
+	const size_t nb = (size_t)off[n_given] > 0 ? (size_t)off[n_given] : 1, pnb = (size_t)s.padded_total + 64;
 	if ((uint64_t)pnb >= (1ull << 32)) return nabwa_fail(NABWA_EINVAL, "batch holds 4 Gi padded bases or more: split it (lane state keeps a 32-bit read offset)");
-	HIP_CHECK(b->d_seq.get(ix, pnb)); HIP_CHECK(b->d_rseq.get(ix, pnb));
-	HIP_CHECK(b->d_poff.get(ix, (size_t)(n + 1) * 8)); HIP_CHECK(b->d_len.get(ix, (size_t)(n ? n : 1) * 4));
-	HIP_CHECK(b->d_md.get(ix, n ? n : 1)); HIP_CHECK(b->d_mg.get(ix, n ? n : 1)); HIP_CHECK(b->d_key.get(ix, (size_t)(n ? n : 1) * 24));
-	b->pack_stride = 2 * ((max_len + 15) / 16 + 2);
-	HIP_CHECK(b->d_pack.get(ix, (size_t)(n ? n : 1) * b->pack_stride * 4));
-	HIP_CHECK(b->d_cls.get(ix, (size_t)(n ? n : 1) * 2)); HIP_CHECK(b->d_perm.get(ix, (size_t)(n ? n : 1) * 4)); HIP_CHECK(b->d_ncls.get(ix, NCLS_WORDS * sizeof(unsigned int)));
-	if (n == 0) { HIP_CHECK(hipMemset(b->d_poff, 0, 8)); return NABWA_OK; }
+	/* the batch's read buffers, for n reads; with NABWA_DEDUP=1 they are taken once the distinct reads are counted (d_seq / d_rseq keep the
+	 * caller's padded total, which the host knows; the distinct reads need no more) */
+	auto read_buffers = [&](int n) -> int {
+		HIP_CHECK(b->d_seq.get(ix, pnb)); HIP_CHECK(b->d_rseq.get(ix, pnb));
+		HIP_CHECK(b->d_poff.get(ix, (size_t)(n + 1) * 8)); HIP_CHECK(b->d_len.get(ix, (size_t)(n ? n : 1) * 4));
+		HIP_CHECK(b->d_md.get(ix, n ? n : 1)); HIP_CHECK(b->d_mg.get(ix, n ? n : 1)); HIP_CHECK(b->d_key.get(ix, (size_t)(n ? n : 1) * 24));
+		b->pack_stride = 2 * ((max_len + 15) / 16 + 2);
+		HIP_CHECK(b->d_pack.get(ix, (size_t)(n ? n : 1) * b->pack_stride * 4));
+		HIP_CHECK(b->d_cls.get(ix, (size_t)(n ? n : 1) * 2)); HIP_CHECK(b->d_perm.get(ix, (size_t)(n ? n : 1) * 4)); HIP_CHECK(b->d_ncls.get(ix, NCLS_WORDS * sizeof(unsigned int)));
+		return NABWA_OK;
+	};
+	const bool dedup = dedup_bits >= 0 && n_given > 0;
+	if (!dedup) if (int r = read_buffers(n_given)) return r;
+	if (n_given == 0) { HIP_CHECK(hipMemset(b->d_poff, 0, 8)); return NABWA_OK; }
 	PoolBuf<uint8_t> raw_s, raw_r, d_tab; PoolBuf<int64_t> raw_off, plen; PoolBuf<void> d_tmp; size_t tmp_bytes = 0;
 	StreamDrain drain{ b->stream };
-	HIP_CHECK(raw_s.get(ix, nb)); HIP_CHECK(raw_r.get(ix, nb)); HIP_CHECK(raw_off.get(ix, (size_t)(n + 1) * 8));
-	const UploadJob jobs[3] = { { raw_s, seq, (size_t)off[n] }, { raw_r, rseq, (size_t)off[n] }, { raw_off, off, (size_t)(n + 1) * 8 } };
+	HIP_CHECK(raw_s.get(ix, nb)); HIP_CHECK(raw_r.get(ix, nb)); HIP_CHECK(raw_off.get(ix, (size_t)(n_given + 1) * 8));
+	const UploadJob jobs[3] = { { raw_s, seq, (size_t)off[n_given] }, { raw_r, rseq, (size_t)off[n_given] }, { raw_off, off, (size_t)(n_given + 1) * 8 } };
 	const double tu0 = now_s();
 	HIP_CHECK(staged_upload(ix, jobs, 3));
-	if (timing) fprintf(stderr, "[nabwa] upload of %.2f GB: %.3f s (%.3f s into batch_create)\n", 2e-9 * (double)off[n], now_s() - tu0, tu0 - tc0);
+	if (timing) fprintf(stderr, "[nabwa] upload of %.2f GB: %.3f s (%.3f s into batch_create)\n", 2e-9 * (double)off[n_given], now_s() - tu0, tu0 - tc0);
+	if (dedup) {
+		if (int r = dedup_reads(b, dedup_bits, raw_s, raw_r, raw_off, nb, timing)) return r;
+		if (int r = read_buffers(b->n)) return r;
+	}
+	const int n = b->n;      /* the reads searched from here on */
 	// padded starts: exclusive scan of the padded lengths, on the device
 	HIP_CHECK(plen.get(ix, (size_t)(n + 1) * 8));
 	nabwa_launch_padded_len(n, raw_off, plen, b->stream);
@@ -250,12 +339,27 @@ extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 	HIP_CHECK(hipSetDevice(ix->device));
 	const bool timing = getenv("NABWA_TIMING") != 0;
 	const double tc0 = now_s();
+	/* NABWA_DEDUP: unset or 0 -- every read is searched; 1 -- each distinct read once (dedup_reads).  NABWA_DEDUP_HASH_BITS (tests): the low
+	 * bits of the hash that group the reads, 0..64 */
+	int dedup_bits = -1;
+	if (const char *e = getenv("NABWA_DEDUP")) {
+		if (strcmp(e, "0") && strcmp(e, "1")) return nabwa_fail(NABWA_EINVAL, "NABWA_DEDUP: 0 or 1");
+		if (e[0] == '1') {
+			dedup_bits = 64;
+			if (const char *k = getenv("NABWA_DEDUP_HASH_BITS")) {
+				char *end = 0;
+				const long v = strtol(k, &end, 10);
+				if (end == k || *end || v < 0 || v > 64) return nabwa_fail(NABWA_EINVAL, "NABWA_DEDUP_HASH_BITS: 0..64");
+				dedup_bits = (int)v;
+			}
+		}
+	}
 	BatchShape s;
-	if (int r = derive_options(opt, n, off, per_read, s)) return r;
+	if (int r = derive_options(opt, n, off, per_read, s)) return r;      /* (on the caller's reads, whatever NABWA_DEDUP says: the lengths that occur are the same) */
 
 	const double tc1 = now_s();
 	std::unique_ptr<nabwa_batch, void (*)(nabwa_batch*)> b(new nabwa_batch(), nabwa_batch_destroy);      /* a half-built batch goes the way of a whole one */
-	b->ix = ix; b->opt = *opt; b->n = n; b->deep_only = s.deep_only ? 1 : 0;
+	b->ix = ix; b->opt = *opt; b->n = b->n_given = n; b->dedup_on = dedup_bits >= 0; b->deep_only = s.deep_only ? 1 : 0;
 	b->max_len = s.max_len; b->min_len = n ? s.min_len : 0; b->NS1 = s.NS1; b->NS_wide = s.NS; b->deep_coop = -1;
 	/* a stream that does not synchronise with the legacy default stream: the finishing chains of another batch (bwt_sa batches, the
 	 * alignment kernels: default stream, synchronous copies) run from another thread while this batch's search kernels do; everything in
@@ -263,7 +367,7 @@ extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 	if (env_int("NABWA_STREAM_BLOCKING", 0)) HIP_CHECK(hipStreamCreate(&b->stream.s));
 	else HIP_CHECK(hipStreamCreateWithFlags(&b->stream.s, hipStreamNonBlocking));
 	for (DevEvent *e : { &b->ev0, &b->ev1, &b->evw, &b->evd0, &b->evd1 }) HIP_CHECK(hipEventCreate(&e->e));
-	if (int r = upload_reads(b.get(), s, off, seq, rseq, timing, tc0)) return r;
+	if (int r = upload_reads(b.get(), s, off, seq, rseq, timing, tc0, dedup_bits)) return r;
 
 	const double tc2 = now_s();
 	if (int r = working_buffers(b.get(), s)) return r;
@@ -432,19 +536,23 @@ extern "C" int nabwa_batch_count_touches(nabwa_batch_t *b, uint64_t *n_bucket, u
  * (:126-130; only for reads longer than the seed).  Runs kernel W alone on a fresh record.  Rows are max_len + 1 wide. */
 extern "C" int nabwa_batch_width_records(nabwa_batch_t *b, int first, int n, uint32_t *w_out, uint8_t *bid_out, uint8_t *seed_bid_out)
 {
-	if (!b || first < 0 || n < 0 || first + n > b->n || (n && (!w_out || !bid_out))) return nabwa_fail(NABWA_EINVAL, "bad argument");
+	if (!b || first < 0 || n < 0 || first + n > b->n_given || (n && (!w_out || !bid_out))) return nabwa_fail(NABWA_EINVAL, "bad argument");
 	if (n == 0) return NABWA_OK;
 	HIP_CHECK(hipSetDevice(b->ix->device));
 	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, WC_WORDS * sizeof(unsigned int), b->stream));
 	SearchParams PW = b->P; PW.ids = 0; PW.rd_cls = 0; PW.touch_counter = 0;
 	nabwa_launch_fm_width(&PW, b->n_blocks_w, b->stream);
 	HIP_CHECK(hipGetLastError());
-	std::vector<uint8_t> rec((size_t)n * b->P.wstride);
-	HIP_CHECK(hipMemcpyAsync(rec.data(), b->d_wdata + (size_t)first * b->P.wstride, rec.size(), hipMemcpyDeviceToHost, b->stream));
+	/* first and n are the caller's read indices: with a map (NABWA_DEDUP) the records of all reads searched come down and are picked from */
+	std::vector<int32_t> src(b->d_map ? (size_t)n : 0);
+	const size_t rec0 = b->d_map ? 0 : (size_t)first, n_rec = b->d_map ? (size_t)b->n : (size_t)n;
+	std::vector<uint8_t> rec(n_rec * b->P.wstride);
+	if (b->d_map) HIP_CHECK(hipMemcpyAsync(src.data(), b->d_map + first, (size_t)n * 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipMemcpyAsync(rec.data(), b->d_wdata + rec0 * b->P.wstride, rec.size(), hipMemcpyDeviceToHost, b->stream));
 	HIP_CHECK(hipStreamSynchronize(b->stream));
 	const int W = b->max_len + 1, SW = b->opt.seed_len + 1;
 	for (int i = 0; i < n; ++i) {
-		const uint8_t *r = rec.data() + (size_t)i * b->P.wstride;
+		const uint8_t *r = rec.data() + (size_t)(b->d_map ? src[i] : i) * b->P.wstride;
 		for (int x = 0; x < 2; ++x) {
 			memcpy(w_out + ((size_t)i * 2 + x) * W, (const uint32_t*)r + x * b->P.WL, 4 * (size_t)W);
 			memcpy(bid_out + ((size_t)i * 2 + x) * W, r + b->P.woff_bid + x * b->P.WLB, (size_t)W);
@@ -460,7 +568,7 @@ extern "C" int nabwa_batch_checksum(nabwa_batch_t *b, uint64_t *sum, int64_t *n_
 	HIP_CHECK(hipSetDevice(b->ix->device));
 	unsigned long long h[CKS_WORDS] = { 0, 0 };
 	HIP_CHECK(hipMemsetAsync(b->d_sum, 0, sizeof h, b->stream));
-	nabwa_launch_checksum(b->n, b->d_naln, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
+	nabwa_launch_checksum(b->n_given, b->d_map, b->d_naln, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
 						  b->d_sum + CKS_SUM, b->d_sum + CKS_ROWS, b->stream);
 	HIP_CHECK(hipMemcpyAsync(h, b->d_sum, sizeof h, hipMemcpyDeviceToHost, b->stream));
 	HIP_CHECK(hipStreamSynchronize(b->stream));
@@ -473,7 +581,7 @@ extern "C" int nabwa_batch_config(nabwa_batch_t *b, nabwa_batch_config_t *out)
 {
 	if (!b || !out) return nabwa_fail(NABWA_EINVAL, "null argument");
 	memset(out, 0, sizeof(*out));
-	out->n = b->n; out->min_len = b->min_len; out->max_len = b->max_len;
+	out->n = b->n_given; out->min_len = b->min_len; out->max_len = b->max_len;
 	out->deep_only = b->deep_only; out->ns1 = (int32_t)b->NS1; out->ns_wide = (int32_t)b->NS_wide;
 	out->w_sync = b->P.w_sync; out->trip_budget = (int32_t)b->P.trip_budget; out->trip_budget_hard = (int32_t)b->P.trip_budget_hard;
 	out->n_sync = out->hard_budget = -1;
@@ -507,6 +615,14 @@ static int sure0_read(nabwa_batch_t *b, uint64_t *out, int n_words)
 	return NABWA_OK;
 }
 
+/* NABWA_DEDUP: reads given, reads searched, reads whose hash met an earlier read's that they differ from (searched themselves), the switch */
+extern "C" int nabwa_batch_dedup_stats(nabwa_batch_t *b, uint64_t out[4])
+{
+	if (!b || !out) return nabwa_fail(NABWA_EINVAL, "null argument");
+	out[0] = (uint64_t)b->n_given; out[1] = (uint64_t)b->n; out[2] = b->dedup_coll; out[3] = b->dedup_on ? 1 : 0;
+	return NABWA_OK;
+}
+
 extern "C" int nabwa_batch_sure0_stats(nabwa_batch_t *b, uint64_t out[4]) { return sure0_read(b, out, 4); }      /* the first entry of the ABI: four words, S0S_READS .. S0S_NET */
 extern "C" int nabwa_batch_sure0_stats_ex(nabwa_batch_t *b, uint64_t out[8]) { return sure0_read(b, out, S0S_WORDS); }
 
@@ -518,17 +634,25 @@ extern "C" int nabwa_batch_fetch(nabwa_batch_t *b, int32_t *n_aln, nabwa_aln1_t 
 	if (n_rows) *n_rows = 0;
 	if (b->n == 0) return NABWA_OK;
 	// device-side compaction: exclusive scan of n_aln, then gather rows
-	PoolBuf<uint32_t> d_off; PoolBuf<void> d_tmp; size_t tmp_bytes = 0; PoolBuf<uint4> d_rows;
+	PoolBuf<uint32_t> d_off; PoolBuf<void> d_tmp; size_t tmp_bytes = 0; PoolBuf<uint4> d_rows; PoolBuf<int32_t> d_cnt;
 	StreamDrain drain{ b->stream };
-	HIP_CHECK(d_off.get(b->ix, (size_t)(b->n + 1) * 4));
-	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const uint32_t*)b->d_naln.p, d_off.p, b->n, b->stream));
+	const int n = b->n_given;
+	/* with a map (NABWA_DEDUP) the caller's reads take the counts, max_entries and rows of the reads searched for them */
+	const int32_t *naln = b->d_naln, *maxent = b->d_maxent;
+	if (b->d_map) {
+		HIP_CHECK(d_cnt.get(b->ix, (size_t)n * 8));
+		nabwa_launch_dedup_expand(n, b->d_map, b->d_naln, b->d_maxent, d_cnt, d_cnt + n, b->stream);
+		naln = d_cnt; maxent = d_cnt + n;
+	}
+	HIP_CHECK(d_off.get(b->ix, (size_t)(n + 1) * 4));
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const uint32_t*)naln, d_off.p, n, b->stream));
 	HIP_CHECK(d_tmp.get(b->ix, tmp_bytes ? tmp_bytes : 16));
-	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, (const uint32_t*)b->d_naln.p, d_off.p, b->n, b->stream));
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, (const uint32_t*)naln, d_off.p, n, b->stream));
 	uint32_t last_off = 0; int32_t last_n = 0;
-	HIP_CHECK(hipMemcpyAsync(&last_off, d_off + (b->n - 1), 4, hipMemcpyDeviceToHost, b->stream));
-	HIP_CHECK(hipMemcpyAsync(&last_n, b->d_naln + (b->n - 1), 4, hipMemcpyDeviceToHost, b->stream));
-	HIP_CHECK(hipMemcpyAsync(n_aln, b->d_naln, (size_t)b->n * 4, hipMemcpyDeviceToHost, b->stream));
-	if (max_entries) HIP_CHECK(hipMemcpyAsync(max_entries, b->d_maxent, (size_t)b->n * 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipMemcpyAsync(&last_off, d_off + (n - 1), 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipMemcpyAsync(&last_n, naln + (n - 1), 4, hipMemcpyDeviceToHost, b->stream));
+	HIP_CHECK(hipMemcpyAsync(n_aln, naln, (size_t)n * 4, hipMemcpyDeviceToHost, b->stream));
+	if (max_entries) HIP_CHECK(hipMemcpyAsync(max_entries, maxent, (size_t)n * 4, hipMemcpyDeviceToHost, b->stream));
 	HIP_CHECK(hipStreamSynchronize(b->stream));
 	const int64_t total = (int64_t)last_off + last_n;
 	if (n_rows) *n_rows = total;
@@ -536,12 +660,12 @@ extern "C" int nabwa_batch_fetch(nabwa_batch_t *b, int32_t *n_aln, nabwa_aln1_t 
 	if (total > aln_cap || (total && !aln_out)) rc = nabwa_fail(NABWA_ECAP, "aln_cap too small");
 	else if (total) {
 		HIP_CHECK(d_rows.get(b->ix, (size_t)total * 16));
-		nabwa_launch_gather(b->n, b->d_naln, d_off, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
+		nabwa_launch_gather(n, b->d_map, b->d_naln, d_off, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
 							d_rows, b->stream);
 		HIP_CHECK(hipMemcpyAsync(aln_out, d_rows, (size_t)total * 16, hipMemcpyDeviceToHost, b->stream));
 		HIP_CHECK(hipStreamSynchronize(b->stream));
 		HIP_CHECK(d_rows.release());
 	}
-	HIP_CHECK(d_off.release()); HIP_CHECK(d_tmp.release());
+	HIP_CHECK(d_off.release()); HIP_CHECK(d_tmp.release()); HIP_CHECK(d_cnt.release());
 	return rc;
 }

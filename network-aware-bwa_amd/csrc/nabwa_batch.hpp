@@ -11,12 +11,16 @@
 struct nabwa_batch {
 	nabwa_index *ix = nullptr;
 	nabwa_gap_opt_t opt = {};
-	int n = 0;
+	int n = 0;                       // the reads searched: what every kernel and buffer of the search counts by
+	/* NABWA_DEDUP=1 (nabwa_batch.hip: dedup_reads): n_given is the caller's count, n the distinct reads among them; d_map, when held, takes
+	 * a caller's read to the read searched for it (n_given entries).  No map: n == n_given and the batch is what it is without the switch */
+	int n_given = 0, dedup_on = 0; unsigned int dedup_coll = 0;
 	DevStream stream;
 	DevEvent ev0, ev1, evw;
 	float last_ms = 0.f;
 	// device inputs
 	PoolBuf<uint8_t> d_seq, d_rseq, d_md, d_mg; PoolBuf<int64_t> d_poff; PoolBuf<int32_t> d_len; PoolBuf<uint32_t> d_key, d_pack; int pack_stride = 0;
+	PoolBuf<int32_t> d_map;
 	PoolBuf<unsigned long long> d_s0stats; PoolBuf<uint8_t> d_cls; PoolBuf<int32_t> d_perm; PoolBuf<unsigned int> d_ncls; int max_len = 0;
 	// first pass
 	SearchParams P = {}; int class_sort = 0; uint32_t NS_wide = 0; int n_blocks = 0, n_blocks_w = 0; PoolBuf<uint8_t> d_scratch, d_wdata, d_nN; float last_ms_w = 0.f;

@@ -50,6 +50,21 @@ static inline int env_int(const char *name, int dflt, int lo)
 	return x < lo ? lo : x > 0x7fffffff ? 0x7fffffff : (int)x;
 }
 
+/* NABWA_DEDUP / NABWA_DEDUP_HASH_BITS as nabwa_batch_create reads them (include/nabwa.h): a value it would refuse is refused by the tool
+ * before the index is loaded.  False after the line that says so; the caller leaves with status 1 */
+static inline bool tool_dedup_ok()
+{
+	const char *e = getenv("NABWA_DEDUP");
+	if (!e || !strcmp(e, "0")) return true;
+	if (strcmp(e, "1")) { fprintf(stderr, "[" TOOL "] NABWA_DEDUP=%s: 0 or 1\n", e); return false; }
+	if (const char *k = getenv("NABWA_DEDUP_HASH_BITS")) {
+		char *end = 0;
+		const long v = strtol(k, &end, 10);
+		if (end == k || *end || v < 0 || v > 64) { fprintf(stderr, "[" TOOL "] NABWA_DEDUP_HASH_BITS=%s: 0..64\n", k); return false; }
+	}
+	return true;
+}
+
 /* threads of the BGZF block work, in and out: the cores, at most 16 (host_threads() without NABWA_HOST_THREADS, which these never read) */
 static inline int io_threads() { int nt = (int)std::thread::hardware_concurrency(); if (nt < 1) nt = 1; if (nt > 16) nt = 16; return nt; }
 

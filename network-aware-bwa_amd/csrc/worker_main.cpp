@@ -201,6 +201,7 @@ int main(int argc, char **argv)
 	if (optind != argc || port <= 0 || port > 65533) return usage(nthreads, host, port, minutes);
 	if (nthreads < 1) nthreads = 1;
 	if (nthreads > 64) { fprintf(stderr, "[nabwa_worker] -t %d: at most 64 connections\n", nthreads); return 1; }
+	if (!tool_dedup_ok()) return 1;      /* NABWA_DEDUP: the worker core's search batches read it (include/nabwa.h) */
 	const double t_start = now_s();
 
 	Zmq z{};

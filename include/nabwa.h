@@ -103,7 +103,21 @@ int nabwa_cal_sa_reg_gap(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, c
  * NABWA_DEDUP_HASH_BITS=k (tests; 0..64, default 64, else NABWA_EINVAL; read only with NABWA_DEDUP=1): group the reads by the low k bits of
  * their hash only.  Reads that share a group and differ are searched on their own (the bytes are compared before two reads merge), so the
  * results do not change; with 0 every read shares one group.
- * With NABWA_TIMING the stage writes one line per batch to stderr: reads given, reads searched, collisions, its time by HIP events. */
+ * With NABWA_TIMING the stage writes one line per batch to stderr: reads given, reads searched, collisions, its time by HIP events.
+ *
+ * NABWA_DEDUP_CACHE=<MiB> (read with NABWA_DEDUP=1, by the same entries): unset or 0 -- a batch knows nothing of earlier batches;
+ * a positive number -- the index keeps, in at most that many MiB of device memory (made by the first batch that asks, out of the index's pool,
+ * counted in nabwa_index_device_bytes, freed with the index; one per index, so one per replica), the results of the reads its batches searched,
+ * and a later batch takes the results of a read it finds there instead of searching it.  A read is found only when its length, every byte of
+ * seq and of rseq and its effective max_diff and max_gapo equal an entry's; entries are never moved or evicted, and once the cache is full
+ * nothing more is entered while lookups go on.  The cache holds results of one option block at a time (every field of nabwa_gap_opt_t but
+ * n_threads and trim_qual): a batch with another block empties it first when no live batch holds results from it, and goes without it
+ * otherwise.  A batch that was served reads holds the cache until nabwa_batch_destroy.  What the caller sees is byte for byte what it sees
+ * without the variable, with one exception: nabwa_batch_width_records returns NABWA_EINVAL for a range that holds a served read (kernel W never
+ * saw it).  The diagnostics count the reads searched, as with NABWA_DEDUP; a batch all of whose reads are served searches none.
+ * NABWA_EINVAL before any device work: a value that is no number or negative, a positive value without NABWA_DEDUP=1, and, for the batch that
+ * makes the cache, more MiB than the device has free.  NABWA_DEDUP_HASH_BITS also narrows the key the table is probed by (the comparison does
+ * not change); NABWA_DEDUP_CACHE_ROWS=<n> (default 1024, never below NABWA_ALNCAP1): reads with more hit rows are not entered. */
 typedef struct nabwa_batch nabwa_batch_t;
 int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt, int n, const int64_t *off,
 					   const uint8_t *seq, const uint8_t *rseq, int per_read, nabwa_batch_t **out);
@@ -124,7 +138,8 @@ int nabwa_batch_count_touches(nabwa_batch_t *b, uint64_t *n_bucket, uint64_t *n_
 int nabwa_batch_fetch(nabwa_batch_t *b, int32_t *n_aln, nabwa_aln1_t *aln_out, int64_t aln_cap, int64_t *n_rows,
 					  int32_t *max_entries);
 /* tests: what kernel W computes (the four bwt_cal_width passes, bwtaln.c:52-76,123-130) for reads [first, first + n): rows of
- * max_len + 1 widths and bound bytes (min(bid, 127) | (w[p-1] == w[p]) << 7) per read and strand; seed bounds seed_len + 1 wide */
+ * max_len + 1 widths and bound bytes (min(bid, 127) | (w[p-1] == w[p]) << 7) per read and strand; seed bounds seed_len + 1 wide.
+ * NABWA_EINVAL when the range holds a read served from the read cache (NABWA_DEDUP_CACHE): kernel W never saw it, there are no records */
 int nabwa_batch_width_records(nabwa_batch_t *b, int first, int n, uint32_t *w_out, uint8_t *bid_out, uint8_t *seed_bid_out);
 /* order-independent 64-bit checksum of (read id, row index, row) over all hits, computed on the device */
 int nabwa_batch_checksum(nabwa_batch_t *b, uint64_t *sum, int64_t *n_rows);
@@ -156,6 +171,18 @@ int nabwa_batch_sure0_stats_ex(nabwa_batch_t *b, uint64_t out[8]);
  * batch but differ from the first read of that hash (each is searched on its own and counts in out[1]), out[3] 1 when the batch was created
  * with the switch on, else 0.  Without the switch: { n, n, 0, 0 }. */
 int nabwa_batch_dedup_stats(nabwa_batch_t *b, uint64_t out[4]);
+/* the same four values, then what NABWA_DEDUP_CACHE did: out[4] distinct reads served from the index's read cache (out[1] counts the others),
+ * out[5] reads entered into it by nabwa_batch_sync, out[6] reads not entered (the cache full, more rows than the cap, a search that did not
+ * complete, or the cache emptied for another option block meanwhile), out[7] 1 when the batch went without the cache because live batches
+ * held results of another option block.  All 0 without the variable. */
+int nabwa_batch_dedup_stats_ex(nabwa_batch_t *b, uint64_t out[8]);
+/* the index's read cache (NABWA_DEDUP_CACHE): out[0] device bytes reserved, out[1] bytes of the entries written, out[2] entries, out[3] table
+ * slots, out[4] reads looked up, out[5] reads served, out[6] times it was emptied for another option block, out[7] batches that went without
+ * it.  All 0 while no batch has asked for a cache. */
+int nabwa_index_dedup_cache_stats(nabwa_index_t *ix, uint64_t out[8]);
+/* empties the read cache (its memory and its counts of lookups, flushes and bypasses stay); NABWA_EINVAL while a live batch holds reads
+ * served from it */
+int nabwa_index_dedup_cache_clear(nabwa_index_t *ix);
 void nabwa_batch_destroy(nabwa_batch_t *b);
 
 /* ---- paired-end host pieces (config 3) --------------------------------------------------------- */

@@ -319,6 +319,13 @@ def lib():
     if hasattr(L, "nabwa_batch_dedup_stats"):
         L.nabwa_batch_dedup_stats.restype = C.c_int
         L.nabwa_batch_dedup_stats.argtypes = [_P, _P]
+    for f in ("nabwa_batch_dedup_stats_ex", "nabwa_index_dedup_cache_stats"):
+        if hasattr(L, f):
+            getattr(L, f).restype = C.c_int
+            getattr(L, f).argtypes = [_P, _P]
+    if hasattr(L, "nabwa_index_dedup_cache_clear"):
+        L.nabwa_index_dedup_cache_clear.restype = C.c_int
+        L.nabwa_index_dedup_cache_clear.argtypes = [_P]
     L.nabwa_dp_form_counts.argtypes = [_P, C.c_int]
     L.nabwa_dp_form_counts.restype = None
     L.nabwa_batch_destroy.argtypes = [_P]
@@ -738,6 +745,17 @@ class Index:
     def device_bytes(self):
         return lib().nabwa_index_device_bytes(self._h)
 
+    def dedup_cache_stats(self):
+        """the index's read cache (NABWA_DEDUP_CACHE): [device bytes reserved, bytes of the entries written, entries, table slots, reads looked up,
+        reads served, times emptied for another option block, batches that went without it] (nabwa_index_dedup_cache_stats); all 0 without one"""
+        out = (C.c_uint64 * 8)()
+        _chk(lib().nabwa_index_dedup_cache_stats(self._h, out))
+        return [int(x) for x in out]
+
+    def dedup_cache_clear(self):
+        """empty the read cache (nabwa_index_dedup_cache_clear); NabwaError EINVAL while a live batch holds reads served from it"""
+        _chk(lib().nabwa_index_dedup_cache_clear(self._h))
+
     def close(self):
         if self._h:
             lib().nabwa_index_destroy(self._h)
@@ -891,6 +909,13 @@ class Batch:
         NABWA_DEDUP=1 else 0] (nabwa_batch_dedup_stats); without the switch [n, n, 0, 0]"""
         out = (C.c_uint64 * 4)()
         _chk(lib().nabwa_batch_dedup_stats(self._h, out))
+        return [int(x) for x in out]
+
+    def dedup_stats_ex(self):
+        """dedup_stats()'s four values, then what NABWA_DEDUP_CACHE did: [distinct reads served from the index's read cache, reads entered into
+        it, reads not entered (cache full, over the row cap), 1 if the batch went without the cache] (nabwa_batch_dedup_stats_ex)"""
+        out = (C.c_uint64 * 8)()
+        _chk(lib().nabwa_batch_dedup_stats_ex(self._h, out))
         return [int(x) for x in out]
 
     def close(self):

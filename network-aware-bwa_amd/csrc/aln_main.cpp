@@ -317,7 +317,7 @@ static int usage(const nabwa_gap_opt_t *o)
 		fprintf(stderr, "         -%c %-5s %s%s\n", d.letter, d.arg ? d.arg : "", d.help, dflt);
 	}
 	fprintf(stderr, "\n");
-	fprintf(stderr, "Environment: NABWA_DEVICES (GPUs to use, e.g. 0,1,2,3; default NABWA_DEVICE or 0), NABWA_ALN_BATCH (reads per GPU batch, 4194304),\n             NABWA_ALN_THREADS (parser threads for plain input, 8)\n\n");
+	fprintf(stderr, "Environment: NABWA_DEVICES (GPUs to use, e.g. 0,1,2,3; default NABWA_DEVICE or 0), NABWA_ALN_BATCH (reads per GPU batch, 4194304),\n             NABWA_ALN_THREADS (parser threads for plain input, 8),\n             NABWA_DEDUP (1: search each distinct read of a batch once), NABWA_DEDUP_CACHE (MiB of GPU memory, with NABWA_DEDUP=1: remember the reads\n             searched and serve their copies in later batches without a search; default 0, off)\n\n");
 	return 1;
 }
 
@@ -458,6 +458,7 @@ int main(int argc, char *argv[])
 	reader.join();
 	if (src.n_tot && opt.trim_qual >= 1) fprintf(stderr, "[nabwa_aln] %.1f%% bases are trimmed.\n", 100.0 * src.n_trimmed / src.n_tot);
 	src.fx.close(); bam.close();
+	tool_dedup_cache_summary(ixs);
 	for (nabwa_index_t *p : ixs) nabwa_index_destroy(p);
 	if (fflush(out) != 0) status = status ? status : 2;
 	if (out != stdout) fclose(out);

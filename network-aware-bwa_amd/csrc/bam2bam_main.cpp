@@ -538,6 +538,7 @@ int main(int argc, char **argv)
 	if (bgzf) nabwa_bgzf_destroy(bgzf);
 	if (bgzf_in) nabwa_bgzf_destroy(bgzf_in);
 	nabwa_isize_table_destroy(P.tab);
+	tool_dedup_cache_summary(ixs);
 	for (nabwa_index_t *p : ixs) nabwa_index_destroy(p);
 	final_rename(opt.ofile, true);
 	return 0;

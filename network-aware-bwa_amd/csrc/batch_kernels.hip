@@ -2,6 +2,7 @@
 // class, the lists of reads handed on, the scatter of their results, row compaction and the checksum.
 #include "nabwa_dev.hpp"
 #include "fm_search.hpp"
+#include "dedup_cache_body.hpp"
 #include "launchers.hpp"
 
 // re-lay the reads out with every read starting on a 16-byte boundary (register windows load 16 bases), and form
@@ -202,8 +203,10 @@ __device__ __forceinline__ const uint4 *rows_of(int i, const uint4 *aln, int aln
 }
 
 // compaction: rows of read i go to out[row_off[i] ...].  map: null, or the read whose rows read i takes (NABWA_DEDUP: n and row_off are the
-// caller's, n_aln and the rows those of the reads searched)
-__global__ __launch_bounds__(256) void gather_kernel(int n, const int32_t *__restrict__ map, const int32_t *__restrict__ n_aln, const uint32_t *__restrict__ row_off,
+// caller's, n_aln and the rows those of the reads searched); a negative map value -1 - k: the rows of the cache entry at arena + 16 * cent[k]
+// (NABWA_DEDUP_CACHE, dedup_cache_body.hpp)
+__global__ __launch_bounds__(256) void gather_kernel(int n, const int32_t *__restrict__ map, const uint32_t *__restrict__ cent, const uint8_t *__restrict__ arena,
+												 const int32_t *__restrict__ n_aln, const uint32_t *__restrict__ row_off,
 												 const uint4 *__restrict__ aln, int aln_cap, const uint8_t *__restrict__ status,
 												 const int32_t *__restrict__ wide_idx, const uint4 *__restrict__ aln2, int aln_cap2,
 												 const uint4 *const *__restrict__ grown, uint4 *__restrict__ out)
@@ -211,18 +214,19 @@ __global__ __launch_bounds__(256) void gather_kernel(int n, const int32_t *__res
 	const int i = blockIdx.x * 256 + threadIdx.x;
 	if (i >= n) return;
 	const int rd = map ? map[i] : i;
-	const int na = n_aln[rd];
-	const uint4 *src = rows_of(rd, aln, aln_cap, status, wide_idx, aln2, aln_cap2, grown);
+	const uint8_t *e = rd < 0 ? arena + (size_t)cent[-1 - rd] * 16 : 0;
+	const int na = e ? dcache_n_aln(e) : n_aln[rd];
+	const uint4 *src = e ? dcache_rows(e) : rows_of(rd, aln, aln_cap, status, wide_idx, aln2, aln_cap2, grown);
 	uint4 *dst = out + row_off[i];
 	for (int j = 0; j < na; ++j) dst[j] = src[j];
 }
 
-extern "C" void nabwa_launch_gather(int n, const int32_t *map, const int32_t *n_aln, const uint32_t *row_off, const uint4 *aln, int aln_cap,
+extern "C" void nabwa_launch_gather(int n, const int32_t *map, const uint32_t *cent, const uint8_t *arena, const int32_t *n_aln, const uint32_t *row_off, const uint4 *aln, int aln_cap,
 									const uint8_t *status, const int32_t *wide_idx, const uint4 *aln2, int aln_cap2,
 									const uint4 *const *grown, uint4 *out, hipStream_t s)
 {
 	if (n <= 0) return;
-	hipLaunchKernelGGL(gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, map, n_aln, row_off, aln, aln_cap, status,
+	hipLaunchKernelGGL(gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, map, cent, arena, n_aln, row_off, aln, aln_cap, status,
 					   wide_idx, aln2, aln_cap2, grown, out);
 }
 
@@ -233,8 +237,9 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x)
 	return x;
 }
 
-// (map as in gather_kernel: read i, the caller's, is summed with the rows of read map[i])
-__global__ __launch_bounds__(256) void checksum_kernel(int n, const int32_t *__restrict__ map, const int32_t *__restrict__ n_aln, const uint4 *__restrict__ aln,
+// (map, cent and arena as in gather_kernel: read i, the caller's, is summed with the rows of read map[i] or of its cache entry)
+__global__ __launch_bounds__(256) void checksum_kernel(int n, const int32_t *__restrict__ map, const uint32_t *__restrict__ cent, const uint8_t *__restrict__ arena,
+												   const int32_t *__restrict__ n_aln, const uint4 *__restrict__ aln,
 												   int aln_cap, const uint8_t *__restrict__ status, const int32_t *__restrict__ wide_idx,
 												   const uint4 *__restrict__ aln2, int aln_cap2, const uint4 *const *__restrict__ grown,
 												   unsigned long long *__restrict__ sum, unsigned long long *__restrict__ rows)
@@ -243,8 +248,9 @@ __global__ __launch_bounds__(256) void checksum_kernel(int n, const int32_t *__r
 	uint64_t s = 0, r = 0;
 	if (i < n) {
 		const int rd = map ? map[i] : i;
-		const int na = n_aln[rd];
-		const uint4 *src = rows_of(rd, aln, aln_cap, status, wide_idx, aln2, aln_cap2, grown);
+		const uint8_t *e = rd < 0 ? arena + (size_t)cent[-1 - rd] * 16 : 0;
+		const int na = e ? dcache_n_aln(e) : n_aln[rd];
+		const uint4 *src = e ? dcache_rows(e) : rows_of(rd, aln, aln_cap, status, wide_idx, aln2, aln_cap2, grown);
 		r = (uint64_t)na;
 		s = mix64(((uint64_t)i << 20) ^ (uint64_t)na ^ 0x9e3779b97f4a7c15ULL);
 		for (int j = 0; j < na; ++j) {
@@ -256,12 +262,12 @@ __global__ __launch_bounds__(256) void checksum_kernel(int n, const int32_t *__r
 	if ((threadIdx.x & 63) == 0) { atomicAdd(sum, (unsigned long long)s); atomicAdd(rows, (unsigned long long)r); }
 }
 
-extern "C" void nabwa_launch_checksum(int n, const int32_t *map, const int32_t *n_aln, const uint4 *aln, int aln_cap, const uint8_t *status,
+extern "C" void nabwa_launch_checksum(int n, const int32_t *map, const uint32_t *cent, const uint8_t *arena, const int32_t *n_aln, const uint4 *aln, int aln_cap, const uint8_t *status,
 									  const int32_t *wide_idx, const uint4 *aln2, int aln_cap2,
 									  const uint4 *const *grown, unsigned long long *sum, unsigned long long *rows, hipStream_t s)
 {
 	if (n <= 0) return;
-	hipLaunchKernelGGL(checksum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, map, n_aln, aln, aln_cap, status, wide_idx,
+	hipLaunchKernelGGL(checksum_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, map, cent, arena, n_aln, aln, aln_cap, status, wide_idx,
 					   aln2, aln_cap2, grown, sum, rows);
 }
 

@@ -3,7 +3,7 @@
 // read of its run, number the representatives, and copy their bytes into compact raw buffers.  On the way out (nabwa_batch_fetch) the
 // counts of the caller's reads are taken through the map.  The bodies are in dedup_body.hpp.
 #include "nabwa_dev.hpp"
-#include "dedup_body.hpp"
+#include "dedup_cache_body.hpp"
 #include "launchers.hpp"
 
 // 16 lanes per read (one thread per read walking bytes: 62 ms for 10 M reads, pad_reads_kernel).  keys[i] = the low bits of read i's hash
@@ -89,12 +89,17 @@ __global__ __launch_bounds__(256) void dedup_compact_kernel(int n, const uint8_t
 	}
 }
 
-// the counts and max_entries of the caller's reads: those of the reads searched, through the map
+// the counts and max_entries of the caller's reads: those of the reads searched, through the map; a negative map value -1 - k names served
+// read k, whose entry lies at arena + 16 * cent[k] (NABWA_DEDUP_CACHE, dedup_cache_body.hpp)
 __global__ __launch_bounds__(256) void dedup_expand_kernel(int n, const int32_t *__restrict__ map, const int32_t *__restrict__ n_aln, const int32_t *__restrict__ max_ent,
+														   const uint32_t *__restrict__ cent, const uint8_t *__restrict__ arena,
 														   int32_t *__restrict__ n_aln_out, int32_t *__restrict__ max_ent_out)
 {
 	const int i = blockIdx.x * 256 + threadIdx.x;
-	if (i < n) { const int s = map[i]; n_aln_out[i] = n_aln[s]; max_ent_out[i] = max_ent[s]; }
+	if (i >= n) return;
+	const int s = map[i];
+	if (s >= 0) { n_aln_out[i] = n_aln[s]; max_ent_out[i] = max_ent[s]; }
+	else { const uint8_t *e = arena + (size_t)cent[-1 - s] * 16; n_aln_out[i] = dcache_n_aln(e); max_ent_out[i] = dcache_max_ent(e); }
 }
 
 extern "C" void nabwa_launch_dedup_hash(int n, const uint8_t *seq, const uint8_t *rseq, const int64_t *off, uint64_t mask, uint64_t *keys, uint32_t *ids, hipStream_t s)
@@ -129,8 +134,9 @@ extern "C" void nabwa_launch_dedup_compact(int n, const uint8_t *seq, const uint
 	hipLaunchKernelGGL(dedup_compact_kernel, dim3((n + 15) / 16), dim3(256), 0, s, n, seq, rseq, off, rep, inner, coff, cseq, crseq);
 }
 
-extern "C" void nabwa_launch_dedup_expand(int n, const int32_t *map, const int32_t *n_aln, const int32_t *max_ent, int32_t *n_aln_out, int32_t *max_ent_out, hipStream_t s)
+extern "C" void nabwa_launch_dedup_expand(int n, const int32_t *map, const int32_t *n_aln, const int32_t *max_ent, const uint32_t *cent, const uint8_t *arena,
+										  int32_t *n_aln_out, int32_t *max_ent_out, hipStream_t s)
 {
 	if (n <= 0) return;
-	hipLaunchKernelGGL(dedup_expand_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, map, n_aln, max_ent, n_aln_out, max_ent_out);
+	hipLaunchKernelGGL(dedup_expand_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, map, n_aln, max_ent, cent, arena, n_aln_out, max_ent_out);
 }

@@ -1,4 +1,4 @@
-// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, dedup_kernels.hip, bgzf_deflate.hip, bgzf_inflate.hip and finish_kernels.hip, declared once.
+// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, dedup_kernels.hip, dedup_cache_kernels.hip, bgzf_deflate.hip, bgzf_inflate.hip and finish_kernels.hip, declared once.
 // The defining files and every host unit that calls one include this header, so a parameter list that differs between the two sides
 // is a compile error (C linkage carries no types).  Host side only: the kernel headers (nabwa_dev.hpp, fm_search.hpp, fm_deep.hpp,
 // fm_deep_body.hpp) do not include it -- the CPU emulation of the tests compiles those without HIP.
@@ -20,8 +20,9 @@ void nabwa_launch_fm_width(const SearchParams *P, int n_blocks, hipStream_t s);
 int nabwa_width_occupancy(void);
 int nabwa_search_occupancy(int ns);
 /* batch_kernels.hip */
-/* map (checksum, gather): null, or for each of the n reads the read whose results it takes (NABWA_DEDUP: the caller's read -> the read searched) */
-void nabwa_launch_checksum(int n, const int32_t *map, const int32_t *n_aln, const uint4 *aln, int aln_cap, const uint8_t *status,
+/* map (checksum, gather): null, or for each of the n reads the read whose results it takes (NABWA_DEDUP: the caller's read -> the read searched);
+ * a map value -1 - k: served read k of NABWA_DEDUP_CACHE, whose entry (dedup_cache_body.hpp) lies at arena + 16 * cent[k] */
+void nabwa_launch_checksum(int n, const int32_t *map, const uint32_t *cent, const uint8_t *arena, const int32_t *n_aln, const uint4 *aln, int aln_cap, const uint8_t *status,
 						   const int32_t *wide_idx, const uint4 *aln2, int aln_cap2, const uint4 *const *grown,
 						   unsigned long long *sum, unsigned long long *rows, hipStream_t s);
 void nabwa_launch_collect(int n, const uint8_t *status, int32_t *ids, unsigned int *count, int which, hipStream_t s);
@@ -34,7 +35,7 @@ void nabwa_launch_scatter_grown(int n2, const int32_t *ids, const int32_t *n_aln
 void nabwa_launch_scatter_wide(int n2, const int32_t *ids, const int32_t *n_aln2, const int32_t *max_ent2,
 							   const uint8_t *status2, int32_t *n_aln, int32_t *max_ent, uint8_t *status,
 							   int32_t *wide_idx, hipStream_t s);
-void nabwa_launch_gather(int n, const int32_t *map, const int32_t *n_aln, const uint32_t *row_off, const uint4 *aln, int aln_cap,
+void nabwa_launch_gather(int n, const int32_t *map, const uint32_t *cent, const uint8_t *arena, const int32_t *n_aln, const uint32_t *row_off, const uint4 *aln, int aln_cap,
 						 const uint8_t *status, const int32_t *wide_idx, const uint4 *aln2, int aln_cap2,
 						 const uint4 *const *grown, uint4 *out, hipStream_t s);
 void nabwa_launch_partition(int n, const uint8_t *cls, int32_t *ids, unsigned int *cnt, hipStream_t s);
@@ -51,7 +52,20 @@ void nabwa_launch_dedup_verify(int n, const uint8_t *seq, const uint8_t *rseq, c
 void nabwa_launch_dedup_map(int n, const int32_t *rep, const uint32_t *inner, const int64_t *off, int32_t *map, int64_t *clen, unsigned int *stat, hipStream_t s);
 void nabwa_launch_dedup_compact(int n, const uint8_t *seq, const uint8_t *rseq, const int64_t *off, const int32_t *rep, const uint32_t *inner,
 								const int64_t *coff, uint8_t *cseq, uint8_t *crseq, hipStream_t s);
-void nabwa_launch_dedup_expand(int n, const int32_t *map, const int32_t *n_aln, const int32_t *max_ent, int32_t *n_aln_out, int32_t *max_ent_out, hipStream_t s);
+void nabwa_launch_dedup_expand(int n, const int32_t *map, const int32_t *n_aln, const int32_t *max_ent, const uint32_t *cent, const uint8_t *arena,
+							   int32_t *n_aln_out, int32_t *max_ent_out, hipStream_t s);
+/* dedup_cache_kernels.hip (dedup_cache_body.hpp): the cross-batch read cache of NABWA_DEDUP_CACHE.  lookup / map / remap run in nabwa_batch.hip's cache_lookup over the
+ * n distinct reads of a batch, insert in cache_insert over the reads searched; 16 lanes per read in lookup and insert.  No kernel reads seq / rseq at or beyond off[n],
+ * reads an entry beyond its size or writes the arena at or beyond arena_bytes */
+void nabwa_launch_dcache_lookup(int n, const uint8_t *seq, const uint8_t *rseq, const int64_t *off, const uint64_t *hash, const uint8_t *md_tab, const uint8_t *mg_tab,
+								const unsigned long long *slots, uint32_t n_slots, uint64_t mask, const uint8_t *arena, uint32_t *found, uint32_t *flag, hipStream_t s);
+void nabwa_launch_dcache_map(int n, const uint32_t *found, const uint32_t *inner, const int64_t *off, int32_t *rep, int32_t *newidx, int64_t *clen, uint32_t *cent,
+							 unsigned int *stat, hipStream_t s);
+void nabwa_launch_dcache_remap(int n, const int32_t *old, const int32_t *newidx, int32_t *map, hipStream_t s);
+void nabwa_launch_dcache_insert(int n, const uint8_t *seq, const uint8_t *rseq, const int64_t *poff, const int32_t *len, const uint8_t *rd_md, const uint8_t *rd_mg,
+								const uint8_t *status, const int32_t *n_aln, const int32_t *max_ent, const uint4 *aln, int aln_cap, const int32_t *wide_idx,
+								const uint4 *aln2, int aln_cap2, const uint4 *const *grown, int row_cap, uint64_t mask,
+								unsigned long long *slots, uint32_t n_slots, uint8_t *arena, uint64_t arena_bytes, unsigned long long *ctr, hipStream_t s);
 /* fm_deep.hip */
 void nabwa_launch_fm_deep(const DeepParams *P, int n_waves, hipStream_t s);
 int nabwa_deep_occupancy(int ns, int lds_rd);

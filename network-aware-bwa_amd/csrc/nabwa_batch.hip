@@ -6,9 +6,11 @@
 #include <stdlib.h>
 #include <string.h>
 #include <memory>
+#include <mutex>
 #include <vector>
 #include "../../include/nabwa.h"
 #include "nabwa_batch.hpp"
+#include "dedup_cache_body.hpp"
 #include "host_util.hpp"
 
 static void layout(SearchParams &P, uint32_t cap, int max_len, int seed_len, uint32_t NS)
@@ -30,6 +32,7 @@ extern "C" void nabwa_batch_destroy(nabwa_batch_t *b)
 	if (!b) return;
 	(void)hipSetDevice(b->ix->device);
 	if (b->stream) (void)hipStreamSynchronize(b->stream);      /* the buffers go back to the pool, not to the driver: nothing may still use them */
+	if (b->cache_pinned) { std::lock_guard<std::mutex> lk(b->cache->mu); --b->cache->pins; }      /* its references into the read cache go with it */
 	delete b;
 }
 
@@ -194,6 +197,90 @@ static int dedup_reads(nabwa_batch *b, int bits, PoolBuf<uint8_t> &raw_s, PoolBu
 	return NABWA_OK;
 }
 
+// ---- step 2b, NABWA_DEDUP_CACHE only: the distinct reads that an earlier batch on this index searched under the same options are served from
+// the index's read cache.  In: raw_s / raw_r / raw_off hold the b->n pairwise distinct reads dedup_reads left, b->d_map (or
+// none) takes the caller's reads to them.  Out, when n_served > 0 of them were found: the raw buffers hold the others, in order, b->n is
+// their number (0: nothing is left to search), b->d_cent names the entries and b->d_map takes a caller's read to a read searched (>= 0) or to
+// served read -1 - value; the cache is pinned.  Out, when none was found: nothing is changed.
+//   the option signature decides first: the cache's -> use it; another and no live batch holds references -> empty the cache (a flush), then
+//   use it; another and references are held -> this batch goes without the cache (a bypass)
+//   hash of every read (all 64 bits) -> probe and compare (dedup_cache_kernels.hip) -> exclusive sum of the flags of the reads to search ->
+//   their numbers and lengths, the served reads' entries -> one download (reads to search) -> compact starts -> their bytes; the map
+// The cache's mutex is held from the first launch until the stream is idle.
+static uint64_t option_signature(const nabwa_gap_opt_t *o)
+{
+	uint32_t fnr; memcpy(&fnr, &o->fnr, 4);
+	const uint32_t w[14] = { (uint32_t)o->s_mm, (uint32_t)o->s_gapo, (uint32_t)o->s_gape, (uint32_t)o->mode, (uint32_t)o->indel_end_skip, (uint32_t)o->max_del_occ,
+							 (uint32_t)o->max_entries, fnr, (uint32_t)o->max_diff, (uint32_t)o->max_gapo, (uint32_t)o->max_gape, (uint32_t)o->max_seed_diff,
+							 (uint32_t)o->seed_len, (uint32_t)o->max_top2 };      /* every field that reaches the search: not n_threads, not trim_qual (the reads come trimmed) */
+	uint64_t h = 0xcbf29ce484222325ULL;
+	for (uint32_t x : w) for (int k = 0; k < 4; ++k) { h ^= (x >> (8 * k)) & 0xffu; h *= 0x100000001b3ULL; }
+	return h;
+}
+
+static int cache_lookup(nabwa_batch *b, const BatchShape &s, PoolBuf<uint8_t> &raw_s, PoolBuf<uint8_t> &raw_r, PoolBuf<int64_t> &raw_off, size_t nb, bool timing)
+{
+	nabwa_index *ix = b->ix;
+	nabwa_dedup_cache *c = b->cache;
+	const int n = b->n, max_len = s.max_len;
+	hipStream_t st = b->stream;
+	std::lock_guard<std::mutex> lk(c->mu);
+	if (c->has_sig && c->sig != b->cache_sig) {
+		if (c->pins) { ++c->bypasses; b->cache = nullptr; b->cache_bypass = 1; return NABWA_OK; }
+		if (int r = nabwa_dcache_reset(ix, c)) return r;
+		++c->flushes;
+	}
+	c->sig = b->cache_sig; c->has_sig = true;
+	PoolBuf<uint64_t> hash; PoolBuf<uint32_t> ids, found, flag, inner, cent; PoolBuf<int32_t> rep, newidx, map; PoolBuf<int64_t> clen, coff; PoolBuf<unsigned int> d_stat;
+	PoolBuf<uint8_t> d_tab, c_s, c_r; PoolBuf<void> d_tmp;
+	DevEvent e0, e1;
+	StreamDrain drain{ st };
+	const size_t n1 = (size_t)n + 1;
+	HIP_CHECK(hash.get(ix, n1 * 8)); HIP_CHECK(ids.get(ix, n1 * 4)); HIP_CHECK(found.get(ix, n1 * 4)); HIP_CHECK(flag.get(ix, n1 * 4)); HIP_CHECK(inner.get(ix, n1 * 4));
+	HIP_CHECK(cent.get(ix, n1 * 4)); HIP_CHECK(rep.get(ix, n1 * 4)); HIP_CHECK(newidx.get(ix, n1 * 4)); HIP_CHECK(clen.get(ix, n1 * 8)); HIP_CHECK(d_stat.get(ix, 8));
+	HIP_CHECK(d_tab.get(ix, 2 * (size_t)(max_len + 1)));
+	size_t tmp_bytes = 16, need = 0;
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, flag.p, inner.p, n + 1, st)); if (need > tmp_bytes) tmp_bytes = need;
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, need, clen.p, clen.p, n + 1, st)); if (need > tmp_bytes) tmp_bytes = need;
+	HIP_CHECK(d_tmp.get(ix, tmp_bytes));
+	HIP_CHECK(hipEventCreate(&e0.e)); HIP_CHECK(hipEventCreate(&e1.e)); HIP_CHECK(hipEventRecord(e0, st));
+	HIP_CHECK(hipMemcpyAsync(d_tab, s.md_tab.data(), max_len + 1, hipMemcpyHostToDevice, st));
+	HIP_CHECK(hipMemcpyAsync(d_tab + max_len + 1, s.mg_tab.data(), max_len + 1, hipMemcpyHostToDevice, st));
+	nabwa_launch_dedup_hash(n, raw_s, raw_r, raw_off, ~0ull, hash, ids, st);
+	nabwa_launch_dcache_lookup(n, raw_s, raw_r, raw_off, hash, d_tab, d_tab + max_len + 1, c->d_slots, c->n_slots, b->cache_mask, c->d_arena, found, flag, st);
+	need = tmp_bytes;
+	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, need, flag.p, inner.p, n + 1, st));
+	nabwa_launch_dcache_map(n, found, inner, raw_off, rep, newidx, clen, cent, d_stat, st);
+	unsigned int n_search = 0;
+	HIP_CHECK(hipMemcpyAsync(&n_search, d_stat, 4, hipMemcpyDeviceToHost, st));
+	HIP_CHECK(hipStreamSynchronize(st));
+	HIP_CHECK(hipGetLastError());
+	if ((int)n_search < 0 || (int)n_search > n) return nabwa_fail(NABWA_EIO, "NABWA_DEDUP_CACHE: the lookup counted more reads to search than reads");
+	const int n_s = (int)n_search, n_served = n - n_s;
+	c->lookups += (uint64_t)n; c->served += (uint64_t)n_served;
+	if (n_served) {
+		HIP_CHECK(coff.get(ix, ((size_t)n_s + 1) * 8)); HIP_CHECK(c_s.get(ix, nb)); HIP_CHECK(c_r.get(ix, nb)); HIP_CHECK(map.get(ix, (size_t)b->n_given * 4));
+		if (n_s) {
+			need = tmp_bytes;
+			HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, need, clen.p, coff.p, n_s + 1, st));
+			nabwa_launch_dedup_compact(n, raw_s, raw_r, raw_off, rep, inner, coff, c_s, c_r, st);
+		} else HIP_CHECK(hipMemsetAsync(coff, 0, 8, st));
+		nabwa_launch_dcache_remap(b->n_given, b->d_map, newidx, map, st);
+	}
+	HIP_CHECK(hipEventRecord(e1, st));
+	HIP_CHECK(hipStreamSynchronize(st));
+	HIP_CHECK(hipGetLastError());
+	HIP_CHECK(hipEventElapsedTime(&b->cache_lookup_ms, e0, e1));
+	if (timing) fprintf(stderr, "[nabwa] dedup cache: %d reads looked up, %d to search, %d served, stage %.3f ms\n", n, n_s, n_served, b->cache_lookup_ms);
+	if (n_served) {      /* (the stream is idle: the buffers these replace go back to the pool) */
+		raw_s = std::move(c_s); raw_r = std::move(c_r); raw_off = std::move(coff);
+		b->d_map = std::move(map); b->d_cent = std::move(cent);
+		b->n = n_s; b->n_served = n_served;
+		++c->pins; b->cache_pinned = 1;
+	}
+	return NABWA_OK;
+}
+
 // ---- step 2: the reads, uploaded as given, then re-laid out on the device with 16-byte aligned starts
 // dedup_bits: -1, or with NABWA_DEDUP=1 the hash bits of dedup_reads, which then runs between the upload and the re-layout
 static int upload_reads(nabwa_batch *b, const BatchShape &s, const int64_t *off, const uint8_t *seq, const uint8_t *rseq, bool timing, double tc0, int dedup_bits)
@@ -225,6 +312,7 @@ static int upload_reads(nabwa_batch *b, const BatchShape &s, const int64_t *off,
 	if (timing) fprintf(stderr, "[nabwa] upload of %.2f GB: %.3f s (%.3f s into batch_create)\n", 2e-9 * (double)off[n_given], now_s() - tu0, tu0 - tc0);
 	if (dedup) {
 		if (int r = dedup_reads(b, dedup_bits, raw_s, raw_r, raw_off, nb, timing)) return r;
+		if (b->cache) if (int r = cache_lookup(b, s, raw_s, raw_r, raw_off, nb, timing)) return r;
 		if (int r = read_buffers(b->n)) return r;
 	}
 	const int n = b->n;      /* the reads searched from here on */
@@ -354,6 +442,16 @@ extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 			}
 		}
 	}
+	/* NABWA_DEDUP_CACHE: unset or 0 -- no batch remembers another's reads; a number of MiB -- the distinct reads NABWA_DEDUP=1 leaves are looked up
+	 * in the index's read cache before the search and entered into it after (cache_lookup, cache_insert); the first batch to ask makes the cache */
+	nabwa_dedup_cache *cache = nullptr;
+	if (const char *e = getenv("NABWA_DEDUP_CACHE")) {
+		char *end = 0;
+		const long v = strtol(e, &end, 10);
+		if (end == e || *end || v < 0) return nabwa_fail(NABWA_EINVAL, "NABWA_DEDUP_CACHE: a number of MiB, 0 for off");
+		if (v > 0 && dedup_bits < 0) return nabwa_fail(NABWA_EINVAL, "NABWA_DEDUP_CACHE needs NABWA_DEDUP=1: the cache sits behind the in-batch stage");
+		if (v > 0) if (int r = nabwa_dcache_get(ix, v, &cache)) return r;
+	}
 	BatchShape s;
 	if (int r = derive_options(opt, n, off, per_read, s)) return r;      /* (on the caller's reads, whatever NABWA_DEDUP says: the lengths that occur are the same) */
 
@@ -361,6 +459,7 @@ extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 	std::unique_ptr<nabwa_batch, void (*)(nabwa_batch*)> b(new nabwa_batch(), nabwa_batch_destroy);      /* a half-built batch goes the way of a whole one */
 	b->ix = ix; b->opt = *opt; b->n = b->n_given = n; b->dedup_on = dedup_bits >= 0; b->deep_only = s.deep_only ? 1 : 0;
 	b->max_len = s.max_len; b->min_len = n ? s.min_len : 0; b->NS1 = s.NS1; b->NS_wide = s.NS; b->deep_coop = -1;
+	if (cache) { b->cache = cache; b->cache_on = 1; b->cache_sig = option_signature(opt); b->cache_mask = dedup_bits >= 64 ? ~0ull : (1ull << dedup_bits) - 1ull; }
 	/* a stream that does not synchronise with the legacy default stream: the finishing chains of another batch (bwt_sa batches, the
 	 * alignment kernels: default stream, synchronous copies) run from another thread while this batch's search kernels do; everything in
 	 * this file orders its own work on b->stream explicitly.  NABWA_STREAM_BLOCKING=1: the old kind, for comparison. */
@@ -469,12 +568,54 @@ static int tier_a_rerun(nabwa_batch *b, unsigned int *cur, bool timing)
 	return NABWA_OK;
 }
 
+/* NABWA_DEDUP_CACHE: the reads this batch searched, their results final, into the index's read cache -- once per batch, however often it runs.
+ * A read enters when its search is complete, it has at most row_cap rows (NABWA_DEDUP_CACHE_ROWS, default 1024 -- the default capacity of
+ * the wide rows: an entry stays within 16 KiB of rows --, never below the narrow row capacity NABWA_ALNCAP1), a slot of its chain is free within the probe bound and the arena has room (dedup_cache_kernels.hip).  A cache that
+ * was emptied for another option block since this batch looked up takes nothing from it.  The cache's mutex is held until the stream is idle. */
+static int cache_insert(nabwa_batch *b)
+{
+	nabwa_dedup_cache *c = b->cache;
+	hipStream_t st = b->stream;
+	std::lock_guard<std::mutex> lk(c->mu);
+	b->cache_inserted = 1;
+	if (!c->has_sig) { c->sig = b->cache_sig; c->has_sig = true; }      /* (cleared since the lookup) */
+	if (c->sig != b->cache_sig) { b->n_not_inserted = (uint64_t)b->n; return NABWA_OK; }
+	int row_cap = env_int("NABWA_DEDUP_CACHE_ROWS", 1024);
+	if (row_cap < b->P.aln_cap) row_cap = b->P.aln_cap;
+	unsigned long long c0[DC_WORDS], c1[DC_WORDS];
+	DevEvent e0, e1;
+	StreamDrain drain{ st };
+	HIP_CHECK(hipEventCreate(&e0.e)); HIP_CHECK(hipEventCreate(&e1.e)); HIP_CHECK(hipEventRecord(e0, st));
+	HIP_CHECK(hipMemcpyAsync(c0, c->d_ctr, sizeof c0, hipMemcpyDeviceToHost, st));
+	nabwa_launch_dcache_insert(b->n, b->d_seq, b->d_rseq, b->d_poff, b->d_len, b->d_md, b->d_mg, b->d_status, b->d_naln, b->d_maxent, b->d_aln, b->P.aln_cap, b->d_wide_idx,
+							   b->d_aln2, b->aln_cap2, b->d_grown_tab, row_cap, b->cache_mask, c->d_slots, c->n_slots, c->d_arena, c->arena_bytes, c->d_ctr, st);
+	HIP_CHECK(hipMemcpyAsync(c1, c->d_ctr, sizeof c1, hipMemcpyDeviceToHost, st));
+	HIP_CHECK(hipEventRecord(e1, st));
+	HIP_CHECK(hipStreamSynchronize(st));
+	HIP_CHECK(hipGetLastError());
+	HIP_CHECK(hipEventElapsedTime(&b->cache_insert_ms, e0, e1));
+	c->used = c1[DC_USED]; c->entries = c1[DC_ENTRIES];
+	b->n_inserted = c1[DC_ENTRIES] - c0[DC_ENTRIES];
+	b->n_not_inserted = (c1[DC_FULL] - c0[DC_FULL]) + (c1[DC_SKIPPED] - c0[DC_SKIPPED]);
+	if (getenv("NABWA_TIMING")) fprintf(stderr, "[nabwa] dedup cache: %d reads searched, %llu entered, %llu not (cache full or over %d rows), stage %.3f ms; %llu entries, %llu bytes\n",
+										b->n, (unsigned long long)b->n_inserted, (unsigned long long)b->n_not_inserted, row_cap, b->cache_insert_ms, c1[DC_ENTRIES], c1[DC_USED]);
+	return NABWA_OK;
+}
+
+static int sync_searches(nabwa_batch_t *b, int *n_second_pass);
+
 extern "C" int nabwa_batch_sync(nabwa_batch_t *b, int *n_second_pass)
 {
 	if (!b) return nabwa_fail(NABWA_EINVAL, "null batch");
 	HIP_CHECK(hipSetDevice(b->ix->device));
 	if (n_second_pass) *n_second_pass = 0;
 	if (b->n == 0) return NABWA_OK;
+	if (int r = sync_searches(b, n_second_pass)) return r;
+	return b->cache && b->ran && !b->cache_inserted ? cache_insert(b) : NABWA_OK;
+}
+
+static int sync_searches(nabwa_batch_t *b, int *n_second_pass)
+{
 	unsigned int novf = 0;
 	HIP_CHECK(hipMemcpyAsync(&novf, b->d_novf, 4, hipMemcpyDeviceToHost, b->stream));
 	HIP_CHECK(hipStreamSynchronize(b->stream));
@@ -539,6 +680,12 @@ extern "C" int nabwa_batch_width_records(nabwa_batch_t *b, int first, int n, uin
 	if (!b || first < 0 || n < 0 || first + n > b->n_given || (n && (!w_out || !bid_out))) return nabwa_fail(NABWA_EINVAL, "bad argument");
 	if (n == 0) return NABWA_OK;
 	HIP_CHECK(hipSetDevice(b->ix->device));
+	if (b->n_served) {      /* kernel W never saw a read served from the read cache: no records to give */
+		std::vector<int32_t> m((size_t)n);
+		HIP_CHECK(hipMemcpyAsync(m.data(), b->d_map + first, (size_t)n * 4, hipMemcpyDeviceToHost, b->stream));
+		HIP_CHECK(hipStreamSynchronize(b->stream));
+		for (int32_t v : m) if (v < 0) return nabwa_fail(NABWA_EINVAL, "nabwa_batch_width_records: the range holds a read served from the read cache (NABWA_DEDUP_CACHE), which has no width records");
+	}
 	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, WC_WORDS * sizeof(unsigned int), b->stream));
 	SearchParams PW = b->P; PW.ids = 0; PW.rd_cls = 0; PW.touch_counter = 0;
 	nabwa_launch_fm_width(&PW, b->n_blocks_w, b->stream);
@@ -568,7 +715,7 @@ extern "C" int nabwa_batch_checksum(nabwa_batch_t *b, uint64_t *sum, int64_t *n_
 	HIP_CHECK(hipSetDevice(b->ix->device));
 	unsigned long long h[CKS_WORDS] = { 0, 0 };
 	HIP_CHECK(hipMemsetAsync(b->d_sum, 0, sizeof h, b->stream));
-	nabwa_launch_checksum(b->n_given, b->d_map, b->d_naln, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
+	nabwa_launch_checksum(b->n_given, b->d_map, b->d_cent, b->cache ? b->cache->d_arena : nullptr, b->d_naln, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
 						  b->d_sum + CKS_SUM, b->d_sum + CKS_ROWS, b->stream);
 	HIP_CHECK(hipMemcpyAsync(h, b->d_sum, sizeof h, hipMemcpyDeviceToHost, b->stream));
 	HIP_CHECK(hipStreamSynchronize(b->stream));
@@ -623,6 +770,15 @@ extern "C" int nabwa_batch_dedup_stats(nabwa_batch_t *b, uint64_t out[4])
 	return NABWA_OK;
 }
 
+/* the same four, then NABWA_DEDUP_CACHE: distinct reads served from the read cache, reads entered into it, reads not entered (cache full, over
+ * the row cap, or the cache emptied for other options meanwhile), 1 if the batch went without the cache because of its option block */
+extern "C" int nabwa_batch_dedup_stats_ex(nabwa_batch_t *b, uint64_t out[8])
+{
+	if (int r = nabwa_batch_dedup_stats(b, out)) return r;
+	out[4] = (uint64_t)b->n_served; out[5] = b->n_inserted; out[6] = b->n_not_inserted; out[7] = b->cache_bypass ? 1 : 0;
+	return NABWA_OK;
+}
+
 extern "C" int nabwa_batch_sure0_stats(nabwa_batch_t *b, uint64_t out[4]) { return sure0_read(b, out, 4); }      /* the first entry of the ABI: four words, S0S_READS .. S0S_NET */
 extern "C" int nabwa_batch_sure0_stats_ex(nabwa_batch_t *b, uint64_t out[8]) { return sure0_read(b, out, S0S_WORDS); }
 
@@ -632,7 +788,7 @@ extern "C" int nabwa_batch_fetch(nabwa_batch_t *b, int32_t *n_aln, nabwa_aln1_t 
 	if (!b || !n_aln) return nabwa_fail(NABWA_EINVAL, "null argument");
 	HIP_CHECK(hipSetDevice(b->ix->device));
 	if (n_rows) *n_rows = 0;
-	if (b->n == 0) return NABWA_OK;
+	if (b->n_given == 0) return NABWA_OK;      /* (b->n == 0 alone: every read is served from the read cache, and has rows to fetch) */
 	// device-side compaction: exclusive scan of n_aln, then gather rows
 	PoolBuf<uint32_t> d_off; PoolBuf<void> d_tmp; size_t tmp_bytes = 0; PoolBuf<uint4> d_rows; PoolBuf<int32_t> d_cnt;
 	StreamDrain drain{ b->stream };
@@ -641,7 +797,7 @@ extern "C" int nabwa_batch_fetch(nabwa_batch_t *b, int32_t *n_aln, nabwa_aln1_t 
 	const int32_t *naln = b->d_naln, *maxent = b->d_maxent;
 	if (b->d_map) {
 		HIP_CHECK(d_cnt.get(b->ix, (size_t)n * 8));
-		nabwa_launch_dedup_expand(n, b->d_map, b->d_naln, b->d_maxent, d_cnt, d_cnt + n, b->stream);
+		nabwa_launch_dedup_expand(n, b->d_map, b->d_naln, b->d_maxent, b->d_cent, b->cache ? b->cache->d_arena : nullptr, d_cnt, d_cnt + n, b->stream);
 		naln = d_cnt; maxent = d_cnt + n;
 	}
 	HIP_CHECK(d_off.get(b->ix, (size_t)(n + 1) * 4));
@@ -660,7 +816,7 @@ extern "C" int nabwa_batch_fetch(nabwa_batch_t *b, int32_t *n_aln, nabwa_aln1_t 
 	if (total > aln_cap || (total && !aln_out)) rc = nabwa_fail(NABWA_ECAP, "aln_cap too small");
 	else if (total) {
 		HIP_CHECK(d_rows.get(b->ix, (size_t)total * 16));
-		nabwa_launch_gather(n, b->d_map, b->d_naln, d_off, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
+		nabwa_launch_gather(n, b->d_map, b->d_cent, b->cache ? b->cache->d_arena : nullptr, b->d_naln, d_off, b->d_aln, b->P.aln_cap, b->d_status, b->d_wide_idx, b->d_aln2, b->aln_cap2, b->d_grown_tab,
 							d_rows, b->stream);
 		HIP_CHECK(hipMemcpyAsync(aln_out, d_rows, (size_t)total * 16, hipMemcpyDeviceToHost, b->stream));
 		HIP_CHECK(hipStreamSynchronize(b->stream));

@@ -21,6 +21,14 @@ struct nabwa_batch {
 	// device inputs
 	PoolBuf<uint8_t> d_seq, d_rseq, d_md, d_mg; PoolBuf<int64_t> d_poff; PoolBuf<int32_t> d_len; PoolBuf<uint32_t> d_key, d_pack; int pack_stride = 0;
 	PoolBuf<int32_t> d_map;
+	/* NABWA_DEDUP_CACHE (nabwa_batch.hip: cache_lookup, cache_insert): cache is the index's read cache while this batch looks up in it and
+	 * inserts into it (null: off, or bypassed).  n_served of the distinct reads were found there and are not searched: n counts the others, a
+	 * d_map value -1 - k stands for served read k, and d_cent[k] is its entry's arena offset / 16.  A batch with served reads pins the cache
+	 * until it is destroyed.  cache_mask: the probe key's bits (NABWA_DEDUP_HASH_BITS) */
+	nabwa_dedup_cache *cache = nullptr; uint64_t cache_sig = 0, cache_mask = ~0ull;
+	int cache_on = 0, cache_bypass = 0, cache_pinned = 0, cache_inserted = 0, n_served = 0;
+	uint64_t n_inserted = 0, n_not_inserted = 0; float cache_lookup_ms = 0.f, cache_insert_ms = 0.f;
+	PoolBuf<uint32_t> d_cent;
 	PoolBuf<unsigned long long> d_s0stats; PoolBuf<uint8_t> d_cls; PoolBuf<int32_t> d_perm; PoolBuf<unsigned int> d_ncls; int max_len = 0;
 	// first pass
 	SearchParams P = {}; int class_sort = 0; uint32_t NS_wide = 0; int n_blocks = 0, n_blocks_w = 0; PoolBuf<uint8_t> d_scratch, d_wdata, d_nN; float last_ms_w = 0.f;

@@ -4,10 +4,12 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <string>
 #include <vector>
 #include "../../include/nabwa.h"
 #include "launchers.hpp"
+#include "dedup_cache_body.hpp"
 #include "nabwa_internal.hpp"
 #include "dev_pool.hpp"
 #include "finish_gpu.hpp"
@@ -172,6 +174,12 @@ extern "C" void nabwa_index_destroy(nabwa_index_t *ix)
 	for (int t = 0; t < 2; ++t) { if (ix->bk[t]) (void)hipFree(ix->bk[t]); if (ix->sa[t]) (void)hipFree(ix->sa[t]); if (ix->kmer[t]) (void)hipFree(ix->kmer[t]); if (ix->kmer_top[t]) (void)hipFree(ix->kmer_top[t]);
 		if (ix->sa_full[t]) (void)hipFree(ix->sa_full[t]); if (ix->isa[t]) (void)hipFree(ix->isa[t]); if (ix->text[t]) (void)hipFree(ix->text[t]); }
 	nabwa_finish_drop_reference(ix);
+	if (nabwa_dedup_cache *c = ix->dcache) {      /* (pool buffers: back to the pool, which goes next) */
+		if (c->d_slots) (void)pool_free(ix, c->d_slots);
+		if (c->d_arena) (void)pool_free(ix, c->d_arena);
+		if (c->d_ctr) (void)pool_free(ix, c->d_ctr);
+		delete c;
+	}
 	pool_destroy(ix->pool);
 	if (ix->d_ntpac) (void)hipFree(ix->d_ntpac);
 	delete ix->ref_nt;
@@ -211,6 +219,81 @@ extern "C" int nabwa_index_export(const nabwa_index_t *ix, int which, int what, 
 
 extern "C" uint32_t nabwa_index_seq_len(const nabwa_index_t *ix, int which) { return ix->bwt[which & 1].seq_len; }
 extern "C" uint64_t nabwa_index_device_bytes(const nabwa_index_t *ix) { return ix->bytes; }
+
+/* ------------------------------------------------------------------ the read cache of NABWA_DEDUP_CACHE */
+
+/* A budget of B bytes: the table takes the largest power of two of slots within B / 8 bytes (at least 1024 slots), the arena the rest.  An entry
+ * of a 100 bp read with one row is 272 bytes, of a 30 bp read 112: with entries of 128 bytes and more the table is at most half full when
+ * the arena is. */
+int nabwa_dcache_get(nabwa_index *ix, long mib, nabwa_dedup_cache **out)
+{
+	std::lock_guard<std::mutex> lk(ix->dcache_mu);
+	if (ix->dcache) { *out = ix->dcache; return NABWA_OK; }
+	uint64_t budget = (uint64_t)mib << 20;
+	size_t free_b = 0, total_b = 0;
+	HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+	{ std::lock_guard<std::mutex> pk(ix->pool->mu); free_b += ix->pool->idle_bytes; }      /* (the pool gives its idle buffers back when an allocation fails) */
+	if (budget > free_b) {
+		char why[160]; snprintf(why, sizeof why, "NABWA_DEDUP_CACHE=%ld: more MiB than the device has free (%zu)", mib, free_b >> 20);
+		return nabwa_fail(NABWA_EINVAL, "%s", why);
+	}
+	if (budget > (65535ull << 20)) budget = 65535ull << 20;      /* a batch names an entry by its arena offset / 16 in 32 bits */
+	uint32_t n_slots = 1024;
+	while ((uint64_t)n_slots * 2 * 8 <= budget / 8 && n_slots < (1u << 30)) n_slots *= 2;
+	const uint64_t ctr_bytes = DC_WORDS * sizeof(unsigned long long);
+	const uint64_t arena_bytes = (budget - (uint64_t)n_slots * 8 - ctr_bytes) & ~(uint64_t)15;
+	std::unique_ptr<nabwa_dedup_cache> c(new nabwa_dedup_cache());
+	hipError_t e = pool_malloc(ix, (void**)&c->d_slots, (size_t)n_slots * 8);
+	if (e == hipSuccess) e = pool_malloc(ix, (void**)&c->d_arena, arena_bytes);
+	if (e == hipSuccess) e = pool_malloc(ix, (void**)&c->d_ctr, ctr_bytes);
+	if (e == hipSuccess) e = hipMemset(c->d_slots, 0, (size_t)n_slots * 8);
+	if (e == hipSuccess) e = hipMemset(c->d_ctr, 0, ctr_bytes);
+	if (e != hipSuccess) {
+		if (c->d_slots) (void)pool_free(ix, c->d_slots);
+		if (c->d_arena) (void)pool_free(ix, c->d_arena);
+		if (c->d_ctr) (void)pool_free(ix, c->d_ctr);
+		return nabwa_hip_fail(e, "the device memory of NABWA_DEDUP_CACHE", __FILE__, __LINE__);
+	}
+	c->n_slots = n_slots; c->arena_bytes = arena_bytes; c->reserved = (uint64_t)n_slots * 8 + arena_bytes + ctr_bytes;
+	ix->bytes += c->reserved;
+	*out = ix->dcache = c.release();
+	return NABWA_OK;
+}
+
+int nabwa_dcache_reset(nabwa_index *ix, nabwa_dedup_cache *c)
+{
+	(void)ix;
+	HIP_CHECK(hipMemset(c->d_slots, 0, (size_t)c->n_slots * 8));      /* (the null stream: every lookup and insert stage has drained its own) */
+	HIP_CHECK(hipMemset(c->d_ctr, 0, DC_WORDS * sizeof(unsigned long long)));
+	HIP_CHECK(hipStreamSynchronize(0));
+	c->has_sig = false; c->used = c->entries = 0;
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_index_dedup_cache_stats(nabwa_index_t *ix, uint64_t out[8])
+{
+	if (!ix || !out) return nabwa_fail(NABWA_EINVAL, "null argument");
+	for (int q = 0; q < 8; ++q) out[q] = 0;
+	nabwa_dedup_cache *c;
+	{ std::lock_guard<std::mutex> lk(ix->dcache_mu); c = ix->dcache; }
+	if (!c) return NABWA_OK;
+	std::lock_guard<std::mutex> lk(c->mu);
+	out[0] = c->reserved; out[1] = c->used; out[2] = c->entries; out[3] = c->n_slots;
+	out[4] = c->lookups; out[5] = c->served; out[6] = c->flushes; out[7] = c->bypasses;
+	return NABWA_OK;
+}
+
+extern "C" int nabwa_index_dedup_cache_clear(nabwa_index_t *ix)
+{
+	if (!ix) return nabwa_fail(NABWA_EINVAL, "null argument");
+	nabwa_dedup_cache *c;
+	{ std::lock_guard<std::mutex> lk(ix->dcache_mu); c = ix->dcache; }
+	if (!c) return NABWA_OK;
+	HIP_CHECK(hipSetDevice(ix->device));
+	std::lock_guard<std::mutex> lk(c->mu);
+	if (c->pins) return nabwa_fail(NABWA_EINVAL, "nabwa_index_dedup_cache_clear: live batches hold reads served from the cache");
+	return nabwa_dcache_reset(ix, c);
+}
 
 /* ------------------------------------------------------------------ bwt_sa / occ batches */
 

@@ -19,6 +19,21 @@ struct nabwa_reference {          // bntseq_t + the packed reference (bntseq.h:5
 	std::vector<uint8_t> pac;     // 2 bits per base, 4 bases per byte, first base in the top bits (bwtaln.h:33)
 };
 
+/* The cross-batch read cache of NABWA_DEDUP_CACHE (layout and protocol: dedup_cache_body.hpp).  One per index, made by the first batch
+ * that asks for it, out of the index's pool, freed with the index.  mu covers every lookup stage and every insert stage of the batches on this
+ * index including the drain of their stream, so no lookup kernel runs beside an insert kernel; it also guards everything below. */
+struct nabwa_dedup_cache {
+	std::mutex mu;
+	unsigned long long *d_slots = nullptr; uint32_t n_slots = 0;     /* the table */
+	uint8_t *d_arena = nullptr; uint64_t arena_bytes = 0;             /* the entries, append-only */
+	unsigned long long *d_ctr = nullptr;                              /* DC_* counters */
+	uint64_t reserved = 0;                                            /* device bytes of the three */
+	bool has_sig = false; uint64_t sig = 0;                           /* the option signature the entries were made under */
+	int pins = 0;                                                     /* live batches that hold references into the arena */
+	uint64_t used = 0, entries = 0;                                   /* as of the last insert stage */
+	uint64_t lookups = 0, served = 0, flushes = 0, bypasses = 0;
+};
+
 struct nabwa_index {
 	int device = 0;
 	DevBwt bwt[2] = {};
@@ -39,7 +54,14 @@ struct nabwa_index {
 	uint8_t *d_pac = nullptr; uint64_t pac_bytes = 0;
 	void *d_holes[2] = {}; uint64_t holes_bytes[2] = {}; int n_holes_dev[2] = {};
 	bool fin_ready[2] = {};
+	std::mutex dcache_mu;                      /* guards the pointer below while the first batches make the cache */
+	nabwa_dedup_cache *dcache = nullptr;
 };
+
+/* nabwa_index.hip: the index's read cache of at most `mib` MiB, made on first use (NABWA_EINVAL when that is more than the device has free; a
+ * later call returns the cache there is, whatever its size); emptied -- the caller holds c->mu and the cache has no pins */
+int nabwa_dcache_get(nabwa_index *ix, long mib, nabwa_dedup_cache **out);
+int nabwa_dcache_reset(nabwa_index *ix, nabwa_dedup_cache *c);
 
 /* a failed HIP call: "<expr> failed: <hip error> (<file>:<line>)" as the last error, NABWA_ENODEV as the result */
 static inline int nabwa_hip_fail(hipError_t e, const char *expr, const char *file, int line)

@@ -55,14 +55,33 @@ static inline int env_int(const char *name, int dflt, int lo)
 static inline bool tool_dedup_ok()
 {
 	const char *e = getenv("NABWA_DEDUP");
-	if (!e || !strcmp(e, "0")) return true;
-	if (strcmp(e, "1")) { fprintf(stderr, "[" TOOL "] NABWA_DEDUP=%s: 0 or 1\n", e); return false; }
-	if (const char *k = getenv("NABWA_DEDUP_HASH_BITS")) {
+	const bool on = e && strcmp(e, "0");
+	if (on && strcmp(e, "1")) { fprintf(stderr, "[" TOOL "] NABWA_DEDUP=%s: 0 or 1\n", e); return false; }
+	if (const char *k = on ? getenv("NABWA_DEDUP_HASH_BITS") : 0) {
 		char *end = 0;
 		const long v = strtol(k, &end, 10);
 		if (end == k || *end || v < 0 || v > 64) { fprintf(stderr, "[" TOOL "] NABWA_DEDUP_HASH_BITS=%s: 0..64\n", k); return false; }
 	}
+	/* NABWA_DEDUP_CACHE: a number of MiB, and a positive one only behind NABWA_DEDUP=1 (whether the device has that much free is the library's to say) */
+	if (const char *k = getenv("NABWA_DEDUP_CACHE")) {
+		char *end = 0;
+		const long v = strtol(k, &end, 10);
+		if (end == k || *end || v < 0) { fprintf(stderr, "[" TOOL "] NABWA_DEDUP_CACHE=%s: a number of MiB, 0 for off\n", k); return false; }
+		if (v > 0 && !on) { fprintf(stderr, "[" TOOL "] NABWA_DEDUP_CACHE=%s needs NABWA_DEDUP=1\n", k); return false; }
+	}
 	return true;
+}
+
+/* the one line a tool ends with when NABWA_DEDUP_CACHE was on: the read caches of its index replicas, summed */
+static inline void tool_dedup_cache_summary(const std::vector<nabwa_index_t*> &ixs)
+{
+	uint64_t sum[8] = { 0 };
+	for (nabwa_index_t *ix : ixs) {
+		uint64_t v[8];
+		if (ix && nabwa_index_dedup_cache_stats(ix, v) == NABWA_OK) for (int q = 0; q < 8; ++q) sum[q] += v[q];
+	}
+	if (sum[0]) fprintf(stderr, "[" TOOL "] dedup cache: %llu reads given, %llu searched, %llu served, %llu entries, %llu of %llu bytes\n", (unsigned long long)sum[4],
+						(unsigned long long)(sum[4] - sum[5]), (unsigned long long)sum[5], (unsigned long long)sum[2], (unsigned long long)sum[1], (unsigned long long)sum[0]);
 }
 
 /* threads of the BGZF block work, in and out: the cores, at most 16 (host_threads() without NABWA_HOST_THREADS, which these never read) */

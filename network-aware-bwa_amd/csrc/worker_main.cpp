@@ -305,6 +305,7 @@ int main(int argc, char **argv)
 	fprintf(stderr, "[nabwa_worker] records: %llu positioned, %llu finished, %llu bounced (no estimates), %llu passed through; %.1f s\n",
 			(unsigned long long)cnt[0], (unsigned long long)cnt[1], (unsigned long long)cnt[2], (unsigned long long)cnt[3], now_s() - t_start);
 	nabwa_worker_destroy(w);
+	tool_dedup_cache_summary({ ix });
 	nabwa_index_destroy(ix);
 	return status;
 }

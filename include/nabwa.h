@@ -646,6 +646,12 @@ int nabwa_pairing_typed(nabwa_pe_end_t p[2], int n_hits, uint64_t *hits, const n
  * nabwa_bgzf_create / _handle_compress / _destroy: the same with a handle that keeps its stream, its device buffers and its pinned
  *                             staging buffers between calls (they grow to 1024 slices at most; longer inputs go through in chunks).
  *                             One call at a time per handle.
+ * nabwa_bgzf_compress_ex / nabwa_bgzf_handle_compress_ex: the same with the codes to write; the two entries above are these with
+ *                             NABWA_BGZF_CODES_FIXED and give the bytes they always gave.  NABWA_BGZF_CODES_DYNAMIC: the slices and their
+ *                             tokens are the same, and a block may be stored, fixed or dynamic (BTYPE 10: codes of at most 15 bits built
+ *                             from the slice's own histogram on the device).  It is dynamic where that is strictly shorter and the fixed
+ *                             mode's block byte for byte where not, so no block is larger than the fixed mode's of the same slice, and
+ *                             nabwa_bgzf_bound and the slice + 31 bytes hold.  Any other value of codes is NABWA_EINVAL.
  *
  * The inverse (bgzf_inflate.hip): whole BGZF members back to back in, their inflated bytes out.  Any RFC 1951 payload is read (stored,
  * fixed and dynamic blocks, several per member), not only what the compressor above writes; every member's length and CRC-32 are checked
@@ -668,6 +674,10 @@ int nabwa_bgzf_compress(int device, const uint8_t *in, int64_t n, uint8_t *out, 
 int nabwa_bgzf_create(int device, nabwa_bgzf_t **out);
 int nabwa_bgzf_handle_compress(nabwa_bgzf_t *z, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
 void nabwa_bgzf_destroy(nabwa_bgzf_t *z);
+#define NABWA_BGZF_CODES_FIXED    0
+#define NABWA_BGZF_CODES_DYNAMIC  1
+int nabwa_bgzf_compress_ex(int device, int codes, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
+int nabwa_bgzf_handle_compress_ex(nabwa_bgzf_t *z, int codes, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
 
 #ifdef __cplusplus
 }

@@ -367,6 +367,8 @@ def lib():
     L.nabwa_bgzf_create.argtypes = [C.c_int, _P]
     L.nabwa_bgzf_handle_compress.argtypes = [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]
     L.nabwa_bgzf_destroy.argtypes = [_P]
+    L.nabwa_bgzf_compress_ex.argtypes = [C.c_int, C.c_int, _P, C.c_int64, _P, C.c_int64, _P, _P]
+    L.nabwa_bgzf_handle_compress_ex.argtypes = [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, _P, _P]
     L.nabwa_bgzf_inflated_size.argtypes = [_P, C.c_int64, _P, _P]
     L.nabwa_bgzf_decompress.argtypes = [C.c_int, _P, C.c_int64, _P, C.c_int64, _P, _P]
     L.nabwa_bgzf_handle_decompress.argtypes = [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]
@@ -485,11 +487,22 @@ def _bgzf_call(f, first, data, cap):
     return out[:n_out.value].tobytes()
 
 
-def bgzf_compress(data, device=0, cap=None):
+BGZF_CODES = {"fixed": 0, "dynamic": 1}                # NABWA_BGZF_CODES_FIXED, NABWA_BGZF_CODES_DYNAMIC
+
+
+def _bgzf_codes(codes):
+    if not isinstance(codes, str) or codes not in BGZF_CODES:
+        raise ValueError("codes: 'fixed' or 'dynamic', not %r" % (codes,))
+    return BGZF_CODES[codes]
+
+
+def bgzf_compress(data, device=0, cap=None, codes="fixed"):
     """data -> its BGZF blocks (slices of <= 0xff00 bytes, one block each, no end-of-file block), compressed on the GPU
-    (nabwa_bgzf_compress).  Only the inflated bytes are contract.  cap: the output capacity handed to the library (default: the
-    bound); a NabwaError of code ECAP carries the size that would do in .needed"""
-    return _bgzf_call(lib().nabwa_bgzf_compress, int(device), data, cap)
+    (nabwa_bgzf_compress_ex).  Only the inflated bytes are contract.  cap: the output capacity handed to the library (default: the
+    bound); a NabwaError of code ECAP carries the size that would do in .needed.  codes: "fixed" (fixed Huffman codes or stored
+    blocks) or "dynamic" (a dynamic Huffman block where that is shorter; no block is larger than with "fixed")"""
+    k = _bgzf_codes(codes)
+    return _bgzf_call(lambda dev, *a: lib().nabwa_bgzf_compress_ex(dev, k, *a), int(device), data, cap)
 
 
 def bgzf_inflated_size(data):
@@ -517,8 +530,9 @@ class Bgzf:
         self._h = _P()
         _chk(lib().nabwa_bgzf_create(int(device), C.byref(self._h)))
 
-    def compress(self, data, cap=None):
-        return _bgzf_call(lib().nabwa_bgzf_handle_compress, self._h, data, cap)
+    def compress(self, data, cap=None, codes="fixed"):
+        k = _bgzf_codes(codes)
+        return _bgzf_call(lambda h, *a: lib().nabwa_bgzf_handle_compress_ex(h, k, *a), self._h, data, cap)
 
     def decompress(self, data, cap=None):
         if cap is None:

@@ -41,8 +41,9 @@ static void bgzf_block(const uint8_t *in, size_t n, int level, std::vector<uint8
 
 struct BgzfOut {
 	FILE *f; std::vector<uint8_t> pend; int level;
-	nabwa_bgzf_t *gpu;                                 /* NABWA_BGZF=gpu: the blocks are made by the library's compressor; null: zlib on host threads */
+	nabwa_bgzf_t *gpu;                                 /* NABWA_BGZF=gpu, gpu-dynamic: the blocks are made by the library's compressor; null: zlib on host threads */
 	std::vector<uint8_t> packed;
+	int codes = NABWA_BGZF_CODES_FIXED;                /* gpu-dynamic: NABWA_BGZF_CODES_DYNAMIC */
 	void write(const void *p, size_t n) { const uint8_t *b = (const uint8_t*)p; pend.insert(pend.end(), b, b + n); if (pend.size() >= (64u << 20)) flush(false); }
 	void flush(bool all)
 	{
@@ -54,7 +55,7 @@ struct BgzfOut {
 			const size_t bound = (size_t)nabwa_bgzf_bound((int64_t)take);
 			if (packed.size() < bound) packed.resize(bound);
 			int64_t n_out = 0, nb = 0;
-			if (nabwa_bgzf_handle_compress(gpu, pend.data(), (int64_t)take, packed.data(), (int64_t)packed.size(), &n_out, &nb) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] BGZF on the GPU: %s\n", nabwa_last_error()); fflush(stderr); _exit(2); }
+			if (nabwa_bgzf_handle_compress_ex(gpu, codes, pend.data(), (int64_t)take, packed.data(), (int64_t)packed.size(), &n_out, &nb) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] BGZF on the GPU: %s\n", nabwa_last_error()); fflush(stderr); _exit(2); }
 			if (fwrite(packed.data(), 1, (size_t)n_out, f) != (size_t)n_out) die("output", "write failed");
 			pend.erase(pend.begin(), pend.begin() + take);
 			return;
@@ -176,7 +177,8 @@ struct Options {
 	nabwa_gap_opt_t go; nabwa_pe_opt_t po;
 	uint32_t rec_flags = 0;                                    /* NABWA_BAM_*: --only-aligned, --drop-aligned, --debug-bam, --broken-input, --skip-duplicates */
 	const char *prefix = 0, *ofile = 0, *temp_dir = 0, *input = 0;
-	bool bgzf_gpu = false;                                     /* NABWA_BGZF=gpu */
+	bool bgzf_gpu = false;                                     /* NABWA_BGZF=gpu or gpu-dynamic */
+	bool bgzf_dynamic = false;                                 /* NABWA_BGZF=gpu-dynamic */
 	bool bgzf_in_gpu = false;                                  /* NABWA_BGZF_IN=gpu */
 };
 /* -1: go on; else the exit status, after the line that says why */
@@ -233,10 +235,11 @@ static int parse_options(int argc, char **argv, Options &o)
 	}
 	o.input = argv[optind];
 	/* NABWA_BGZF: who deflates the output -- host (default: zlib level 2 on host threads) or gpu (the library's compressor on the first
-	 * GPU; other compressed bytes, the same inflated ones) */
+	 * GPU; other compressed bytes, the same inflated ones) or gpu-dynamic (the same with dynamic Huffman blocks where they are shorter) */
 	const char *bgzf_env = getenv("NABWA_BGZF");
-	o.bgzf_gpu = bgzf_env && !strcmp(bgzf_env, "gpu");
-	if (bgzf_env && !o.bgzf_gpu && strcmp(bgzf_env, "host")) { fprintf(stderr, "[nabwa_bam2bam] NABWA_BGZF=%s: host or gpu\n", bgzf_env); return 1; }
+	o.bgzf_dynamic = bgzf_env && !strcmp(bgzf_env, "gpu-dynamic");
+	o.bgzf_gpu = o.bgzf_dynamic || (bgzf_env && !strcmp(bgzf_env, "gpu"));
+	if (bgzf_env && !o.bgzf_gpu && strcmp(bgzf_env, "host")) { fprintf(stderr, "[nabwa_bam2bam] NABWA_BGZF=%s: host, gpu or gpu-dynamic\n", bgzf_env); return 1; }
 	/* NABWA_BGZF_IN: who inflates a BGZF input -- host (default: zlib on host threads) or gpu (the library's decompressor on the first
 	 * GPU); any other gzip stream and a plain file are read on the host under either */
 	const char *bgzf_in_env = getenv("NABWA_BGZF_IN");
@@ -507,6 +510,7 @@ int main(int argc, char **argv)
 	FILE *of = opt.ofile ? fopen(opt.ofile, "wb") : stdout;
 	if (!of) die(opt.ofile, "cannot create");
 	BgzfOut out{ of, {}, 2, bgzf, {} };
+	if (opt.bgzf_dynamic) out.codes = NABWA_BGZF_CODES_DYNAMIC;
 	write_output_header(out, ixs[0], old, argc, argv);
 
 	const bool timing = getenv("NABWA_TIMING") != 0;
@@ -530,7 +534,7 @@ int main(int argc, char **argv)
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: library calls: create %.3f s, pass 1 %.3f s, pass 2 %.3f s, output %.3f s, destroy %.3f s\n", P.t_call[0], P.t_call[1], P.t_call[2], P.t_call[3], P.t_call[4]);
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: reader thread %.3f s busy (%.3f s of it inflate, %s), passes 1 and 2 on this thread %.3f s (+ %.3f s waiting for input; the output thread waited %.3f s for the writer), writer thread %.3f s busy (deflate + write; %s)\n",
 						P.t_read, in.t_inflate, in.bgzf ? (bgzf_in ? "BGZF blocks on the GPU" : "BGZF blocks in parallel") : in.raw ? "not compressed" : "one gzip stream", P.t_lib, P.t_wait_in, P.t_wait_out, P.t_write,
-						opt.bgzf_gpu ? "BGZF on the GPU" : "zlib level 2 on host threads");
+						opt.bgzf_dynamic ? "BGZF on the GPU, dynamic Huffman codes" : opt.bgzf_gpu ? "BGZF on the GPU" : "zlib level 2 on host threads");
 	fprintf(stderr, "[nabwa_bam2bam] %ld sequences processed\n[nabwa_bam2bam] finished cleanly, shutting down.\n"
 			"[bwa_paired_sw] %lld out of %lld Q%d singletons are mated.\n[bwa_paired_sw] %lld out of %lld Q%d discordant pairs are fixed.\n",
 			P.tot_seqs, (long long)P.n_mapped[1], (long long)P.n_tot[1], 17, (long long)P.n_mapped[0], (long long)P.n_tot[0], 17);

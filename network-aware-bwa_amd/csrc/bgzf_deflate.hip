@@ -25,6 +25,36 @@ __global__ __launch_bounds__(BGZF_LANES) void bgzf_deflate_kernel(const uint8_t 
 	bgzf_phase_emit(Sh, t, m, ow, sizes + blockIdx.x);
 }
 
+/* the same slice, the same parse and the same tokens; the block is a dynamic Huffman one where that is strictly shorter than what the
+ * kernel above writes, and otherwise that block byte for byte (the phases: bgzf_deflate_body.hpp) */
+__global__ __launch_bounds__(BGZF_LANES) void bgzf_deflate_dyn_kernel(const uint8_t *in, int64_t n, uint8_t *stage, uint32_t *sizes)
+{
+	__shared__ BgzfShared Sh;
+	const uint32_t t = threadIdx.x;
+	const int64_t at = (int64_t)blockIdx.x * BGZF_SLICE;
+	const uint32_t m = n - at < (int64_t)BGZF_SLICE ? (uint32_t)(n - at) : BGZF_SLICE;      /* the grid has ceil(n / 0xff00) workgroups: m >= 1 */
+	uint32_t *ow = (uint32_t*)(stage + (size_t)blockIdx.x * BGZF_STRIDE);
+	bgzf_phase_load(Sh, t, (const uint32_t*)(in + at), m);
+	__syncthreads();
+	bgzf_phase_parse(Sh, t, m);
+	__syncthreads();
+	bgzf_phase_scan(Sh, t, m);
+	bgzf_dyn_phase_clear(Sh, t);                       /* the hash table is dead: its place is the dynamic mode's tables */
+	__syncthreads();
+	bgzf_dyn_phase_count(Sh, t, m);
+	__syncthreads();
+	bgzf_dyn_phase_sort(Sh, t);
+	__syncthreads();
+	bgzf_dyn_phase_header(Sh, t);
+	__syncthreads();
+	bgzf_dyn_phase_measure(Sh, t, m, ow);
+	__syncthreads();
+	bgzf_dyn_phase_offsets(Sh, t);
+	__threadfence();                                   /* the zeros are in place before another lane's atomic OR reaches the word */
+	__syncthreads();
+	bgzf_dyn_phase_emit(Sh, t, m, ow, sizes + blockIdx.x);
+}
+
 /* block k of the staging area to the sum of the sizes before it (at most a launch's slices, a few loads per lane); the last workgroup
  * writes the total.  A block starts at any byte of the packed area and at a multiple of 0x10000 of the staging area: bytes up to the
  * destination's next word, then whole words put together from two of the source's, then the bytes that are left. */
@@ -58,6 +88,10 @@ __global__ __launch_bounds__(256) void bgzf_pack_kernel(const uint8_t *stage, co
 extern "C" void nabwa_launch_bgzf_deflate(const uint8_t *in, int64_t n, int n_slices, uint8_t *stage, uint32_t *sizes, hipStream_t s)
 {
 	hipLaunchKernelGGL(bgzf_deflate_kernel, dim3(n_slices), dim3(BGZF_LANES), 0, s, in, n, stage, sizes);
+}
+extern "C" void nabwa_launch_bgzf_deflate_dyn(const uint8_t *in, int64_t n, int n_slices, uint8_t *stage, uint32_t *sizes, hipStream_t s)
+{
+	hipLaunchKernelGGL(bgzf_deflate_dyn_kernel, dim3(n_slices), dim3(BGZF_LANES), 0, s, in, n, stage, sizes);
 }
 extern "C" void nabwa_launch_bgzf_pack(const uint8_t *stage, const uint32_t *sizes, int n_slices, uint8_t *packed, int64_t *total, hipStream_t s)
 {

@@ -71,6 +71,7 @@ void nabwa_launch_fm_deep(const DeepParams *P, int n_waves, hipStream_t s);
 int nabwa_deep_occupancy(int ns, int lds_rd);
 /* bgzf_deflate.hip: slice k of in[0, n) -> one BGZF block at stage + k * 0x10000, its size in sizes[k]; then the blocks back to back */
 void nabwa_launch_bgzf_deflate(const uint8_t *in, int64_t n, int n_slices, uint8_t *stage, uint32_t *sizes, hipStream_t s);
+void nabwa_launch_bgzf_deflate_dyn(const uint8_t *in, int64_t n, int n_slices, uint8_t *stage, uint32_t *sizes, hipStream_t s);      /* dynamic Huffman blocks where they are shorter */
 void nabwa_launch_bgzf_pack(const uint8_t *stage, const uint32_t *sizes, int n_slices, uint8_t *packed, int64_t *total, hipStream_t s);
 /* bgzf_inflate.hip: member k (blk[k]: payload cmp + src, n_src bytes) -> isize bytes at plain + dst, its status word (bgzf_inflate_body.hpp) in status[k] */
 struct BgzfInBlk;

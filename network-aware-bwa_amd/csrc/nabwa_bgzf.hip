@@ -76,9 +76,10 @@ static int bgzf_reserve(nabwa_bgzf *z, int64_t slices)
 	return NABWA_OK;
 }
 
-extern "C" int nabwa_bgzf_handle_compress(nabwa_bgzf_t *z, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks)
+extern "C" int nabwa_bgzf_handle_compress_ex(nabwa_bgzf_t *z, int codes, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks)
 {
 	if (!z || n < 0 || cap < 0 || (n && !in) || (cap && !out)) return nabwa_fail(NABWA_EINVAL, "null argument");
+	if (codes != NABWA_BGZF_CODES_FIXED && codes != NABWA_BGZF_CODES_DYNAMIC) return nabwa_fail(NABWA_EINVAL, "codes: NABWA_BGZF_CODES_FIXED or NABWA_BGZF_CODES_DYNAMIC");
 	if (n_out) *n_out = 0;
 	if (n_blocks) *n_blocks = (n + SLICE - 1) / SLICE;
 	if (n == 0) return NABWA_OK;
@@ -93,7 +94,7 @@ extern "C" int nabwa_bgzf_handle_compress(nabwa_bgzf_t *z, const uint8_t *in, in
 		const int ns = (int)((m + SLICE - 1) / SLICE);
 		memcpy(z->h_in, in + at, (size_t)m);
 		HIP_CHECK(hipMemcpyAsync(z->d_in.p, z->h_in, (size_t)m, hipMemcpyHostToDevice, z->st));
-		nabwa_launch_bgzf_deflate(z->d_in.as<uint8_t>(), m, ns, z->d_stage.as<uint8_t>(), z->d_sizes.as<uint32_t>(), z->st);
+		(codes == NABWA_BGZF_CODES_DYNAMIC ? nabwa_launch_bgzf_deflate_dyn : nabwa_launch_bgzf_deflate)(z->d_in.as<uint8_t>(), m, ns, z->d_stage.as<uint8_t>(), z->d_sizes.as<uint32_t>(), z->st);
 		nabwa_launch_bgzf_pack(z->d_stage.as<uint8_t>(), z->d_sizes.as<uint32_t>(), ns, z->d_packed.as<uint8_t>(), z->d_total.as<int64_t>(), z->st);
 		HIP_CHECK(hipGetLastError());
 		HIP_CHECK(hipMemcpyAsync(z->h_total, z->d_total.p, sizeof(int64_t), hipMemcpyDeviceToHost, z->st));
@@ -112,13 +113,24 @@ extern "C" int nabwa_bgzf_handle_compress(nabwa_bgzf_t *z, const uint8_t *in, in
 	return NABWA_OK;
 }
 
-extern "C" int nabwa_bgzf_compress(int device, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks)
+extern "C" int nabwa_bgzf_handle_compress(nabwa_bgzf_t *z, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks)
 {
+	return nabwa_bgzf_handle_compress_ex(z, NABWA_BGZF_CODES_FIXED, in, n, out, cap, n_out, n_blocks);
+}
+
+extern "C" int nabwa_bgzf_compress_ex(int device, int codes, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks)
+{
+	if (codes != NABWA_BGZF_CODES_FIXED && codes != NABWA_BGZF_CODES_DYNAMIC) return nabwa_fail(NABWA_EINVAL, "codes: NABWA_BGZF_CODES_FIXED or NABWA_BGZF_CODES_DYNAMIC");
 	nabwa_bgzf_t *z = nullptr;
 	if (int r = nabwa_bgzf_create(device, &z)) return r;
-	const int r = nabwa_bgzf_handle_compress(z, in, n, out, cap, n_out, n_blocks);
+	const int r = nabwa_bgzf_handle_compress_ex(z, codes, in, n, out, cap, n_out, n_blocks);
 	nabwa_bgzf_destroy(z);
 	return r;
+}
+
+extern "C" int nabwa_bgzf_compress(int device, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks)
+{
+	return nabwa_bgzf_compress_ex(device, NABWA_BGZF_CODES_FIXED, in, n, out, cap, n_out, n_blocks);
 }
 
 /* ---------------------------------------------------------------- the decompressor */

@@ -234,6 +234,34 @@ def oracle_cal_sa_reg_gap(lib, ixh, opt, seq, rseq, off, per_read=0, n_threads=1
     return [rows[bounds[i]:bounds[i + 1]] for i in range(n)], maxe
 
 
+def check_width_records(nabwa, ix, gap_opt, opt, olib, bwt_of, seq, rseq, off):
+    """kernel W's records of a batch on index ix (nabwa_batch_width_records) against the oracle's bwt_cal_width (bwtaln.c:52-76) on the
+    oracle index whose two orc_bwt_t are bwt_of(0) and bwt_of(1): interval widths, lower bounds and the "same width as before" flag of
+    the full passes, lower bounds of the seed passes, both strands of every read"""
+    b = nabwa.Batch(ix, gap_opt, seq, rseq, off, False)
+    n, W, SW = len(off) - 1, int(np.diff(off).max()) + 1, opt.seed_len + 1
+    w = np.zeros((n, 2, W), np.uint32); bid = np.zeros((n, 2, W), np.uint8); sbid = np.zeros((n, 2, SW), np.uint8)
+    L = nabwa.lib()
+    L.nabwa_batch_width_records.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    assert L.nabwa_batch_width_records(b._h, 0, n, ptr(w), ptr(bid), ptr(sbid)) == 0, L.nabwa_last_error()
+    olib.orc_cal_width.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    ow = np.zeros(max(W, SW), np.uint32); ob = np.zeros(max(W, SW), np.int32)
+    for i in range(n):
+        ln = int(off[i + 1] - off[i])
+        for x, arr in ((0, seq), (1, rseq)):
+            s = np.ascontiguousarray(arr[off[i]:off[i + 1]])
+            olib.orc_cal_width(bwt_of(x), ln, ptr(s), ptr(ow), ptr(ob))
+            assert np.array_equal(w[i, x, :ln + 1], ow[:ln + 1]), (i, x)
+            assert np.array_equal(bid[i, x, :ln + 1] & 127, np.minimum(ob[:ln + 1], 127)), (i, x)
+            same = np.concatenate([[False], ow[1:ln + 1] == ow[:ln]])
+            assert np.array_equal(bid[i, x, :ln + 1] >> 7 != 0, same), (i, x)
+            if ln > opt.seed_len:
+                t = np.ascontiguousarray(s[ln - opt.seed_len:])
+                olib.orc_cal_width(bwt_of(x), opt.seed_len, ptr(t), ptr(ow), ptr(ob))
+                assert np.array_equal(sbid[i, x, :SW] & 127, np.minimum(ob[:SW], 127)), (i, x)
+    b.close()
+
+
 def load_ref():
     """The compiled reference (only in the build container / when oracle/_ref travelled)."""
     if not os.path.exists(REF_SO):

@@ -679,6 +679,31 @@ void nabwa_bgzf_destroy(nabwa_bgzf_t *z);
 int nabwa_bgzf_compress_ex(int device, int codes, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
 int nabwa_bgzf_handle_compress_ex(nabwa_bgzf_t *z, int codes, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
 
+/* ---- coordinate sort of finished BAM records on the GPU (bam_sort.hip, bam_sort_body.hpp).  Record i is
+ * in[in_off[i] .. in_off[i + 1]) as it stands in an uncompressed BAM stream: u32 block_size, then the block (refID at byte 4 and pos at
+ * byte 8 of the record, little-endian int32); the offsets are those nabwa_bam_batch_output writes.  `out` receives the same records in
+ * non-decreasing key order, records of equal key in the order they had in `in` (the sort is stable); out_off (n_rec + 1, may be NULL)
+ * their offsets from 0 and keys_out (n_rec, may be NULL) their keys, both in output order.
+ * The key of a record: the reference id as an unsigned word (so -1, unmapped without a place, sorts last), then pos + 1 (so -1 sorts first).
+ * NABWA_EINVAL  a null argument; n_rec < 0 or above 0x7fffffff; offsets that do not increase; a record shorter than 36 bytes -- all decided
+ *               on the host from the offsets alone, before the device is looked for (nabwa_bam_sort) and without touching the bytes
+ * NABWA_ECAP    cap is below the records' total, in_off[n_rec] - in_off[0] (nabwa_last_error says how much is needed)
+ * NABWA_EDATA   a record's block_size disagrees with its offsets (found on the device while the key is read); nabwa_last_error names the
+ *               lowest such record.  `out` is not written
+ * NABWA_ENODEV  no device;  NABWA_ENOMEM  the run does not fit the device: it needs 2 x the bytes + 40 B per record + the radix sort's
+ *               scratch, and the caller picks the run size
+ * n_rec == 0 is NABWA_OK with nothing written.  Nothing outside [out, out + cap) is written in any case.  There is no CPU path here.
+ * nabwa_bam_sort_create / _run / _destroy: a handle that keeps its stream and its device buffers (they grow and stay) between calls, one call
+ * at a time; nabwa_bam_sort is the handle used once.  nabwa_bam_sort_times: the device-event times of the handle's last successful run in
+ * milliseconds -- upload, key kernel, radix sort, sizes + scan, gather kernel, download. */
+#define NABWA_BAM_SORT_KEY(tid, pos) (((uint64_t)(uint32_t)(tid) << 32) | (uint32_t)((pos) + 1))
+typedef struct nabwa_bam_sort nabwa_bam_sort_t;
+int nabwa_bam_sort_create(int device, nabwa_bam_sort_t **out);
+void nabwa_bam_sort_destroy(nabwa_bam_sort_t *s);
+int nabwa_bam_sort_run(nabwa_bam_sort_t *s, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out);
+int nabwa_bam_sort(int device, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out);
+int nabwa_bam_sort_times(const nabwa_bam_sort_t *s, float ms[6]);
+
 #ifdef __cplusplus
 }
 #endif

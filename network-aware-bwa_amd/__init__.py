@@ -373,6 +373,13 @@ def lib():
     L.nabwa_bgzf_decompress.argtypes = [C.c_int, _P, C.c_int64, _P, C.c_int64, _P, _P]
     L.nabwa_bgzf_handle_decompress.argtypes = [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]
     L.nabwa_bgzf_destroy.restype = None
+    if hasattr(L, "nabwa_bam_sort_run"):           # (likewise)
+        L.nabwa_bam_sort_create.argtypes = [C.c_int, _P]
+        L.nabwa_bam_sort_destroy.argtypes = [_P]
+        L.nabwa_bam_sort_destroy.restype = None
+        L.nabwa_bam_sort_run.argtypes = [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P]
+        L.nabwa_bam_sort.argtypes = [C.c_int, C.c_int64, _P, _P, _P, C.c_int64, _P, _P]
+        L.nabwa_bam_sort_times.argtypes = [_P, _P]
     if hasattr(L, "nabwa_finish_counts"):          # (a library of an earlier build, loaded through NABWA_LIB for an A/B run, has no such entries)
         L.nabwa_refine_gapped_core.argtypes = [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int]
         L.nabwa_cal_md.argtypes = [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int64]
@@ -542,6 +549,87 @@ class Bgzf:
     def close(self):
         if self._h:
             lib().nabwa_bgzf_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bam_sort_key(tid, pos):
+    """the sort key of a BAM record (NABWA_BAM_SORT_KEY): the reference id as an unsigned word, so that -1 sorts last, then pos + 1, so that
+    -1 sorts first"""
+    return ((int(tid) & 0xffffffff) << 32) | ((int(pos) + 1) & 0xffffffff)
+
+
+def bam_record_offsets(records):
+    """the offsets (n + 1) of the records of an uncompressed BAM record stream, from their block_size words"""
+    a = np.frombuffer(bytes(records), np.uint8)
+    off, q = [0], 0
+    while q < a.size:
+        if a.size - q < 4:
+            raise ValueError("a record is cut short at byte %d" % q)
+        q += 4 + int.from_bytes(a[q:q + 4].tobytes(), "little")
+        off.append(q)
+    if q != a.size:
+        raise ValueError("the last record runs past the end of the bytes")
+    return np.array(off, np.int64)
+
+
+def _bam_sort_call(f, first, records, off, cap):
+    a = np.frombuffer(bytes(records), np.uint8)
+    off = bam_record_offsets(a) if off is None else np.ascontiguousarray(off, np.int64)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("off: n + 1 offsets")
+    n = off.size - 1
+    total = int(off[-1] - off[0])
+    cap = max(total, 0) if cap is None else int(cap)
+    out = np.empty(max(cap, 1), np.uint8)
+    out_off, keys = np.zeros(n + 1, np.int64), np.zeros(n, np.uint64)
+    rc = f(first, n, _ptr(a) if a.size else None, _ptr(off), _ptr(out), cap, _ptr(out_off), _ptr(keys))
+    if rc != OK:
+        e = NabwaError(rc, lib().nabwa_last_error().decode())
+        e.needed = total
+        raise e
+    return out[:total].tobytes() if n else b"", out_off, keys
+
+
+def bam_sort(records, off=None, device=0, cap=None):
+    """finished BAM records (an uncompressed record stream: u32 block_size + block, back to back) -> (the records sorted by coordinate,
+    their offsets, their keys), sorted and gathered on the GPU (nabwa_bam_sort).  The order is that of bam_sort_key, stable: records of
+    equal key keep their order.  off: the records' offsets (n + 1), as nabwa_bam_batch_output gives them; None: walked from the block_size
+    words on the host.  cap: the output capacity handed to the library (default: the records' total); a NabwaError of code ECAP
+    carries the size that would do in .needed, one of code EDATA names the first record whose block_size is not what its offsets say"""
+    return _bam_sort_call(lib().nabwa_bam_sort, int(device), records, off, cap)
+
+
+class BamSort:
+    """the coordinate sort as a handle that keeps its stream and its device buffers between calls (nabwa_bam_sort_create)"""
+
+    def __init__(self, device=0):
+        self._h = _P()
+        _chk(lib().nabwa_bam_sort_create(int(device), C.byref(self._h)))
+
+    def sort(self, records, off=None, cap=None):
+        return _bam_sort_call(lib().nabwa_bam_sort_run, self._h, records, off, cap)
+
+    def times(self):
+        """device-event times of the last sort in ms: upload, key kernel, radix sort, sizes + scan, gather kernel, download"""
+        ms = (C.c_float * 6)()
+        _chk(lib().nabwa_bam_sort_times(self._h, ms))
+        return list(ms)
+
+    def close(self):
+        if self._h:
+            lib().nabwa_bam_sort_destroy(self._h)
             self._h = None
 
     def __enter__(self):

@@ -8,6 +8,7 @@
 // lines kept; bam2bam.c:164-301).  Host code only; the GPU work is the library's.  Not provided: the 0MQ master mode
 // (-p; the worker side is nabwa_worker, worker_main.cpp) and resuming from .sai files (-0 -1 -2) -- each is refused, none is
 // silently ignored.  --only-aligned, --drop-aligned, --skip-duplicates, --broken-input and --debug-bam are the library's NABWA_BAM_* flags.
+// --sort (not the reference's): the records leave sorted by coordinate, runs sorted on the GPU or, NABWA_SORT=host, on host threads.
 // -t is accepted and ignored (NABWA_DEVICES=0,1,... names the GPUs: an index replica on each, batches dealt to them in turn, searched as
 // they come and passed in input order; default one GPU, NABWA_DEVICE or 0), --temp-dir likewise (the records wait in memory between the passes).
 #include <getopt.h>
@@ -20,6 +21,7 @@
 #define TOOL "nabwa_bam2bam"
 #include "bgzf_in.hpp"
 #include "bam_header.hpp"
+#include "bam_sort_host.hpp"
 
 /* ---------------------------------------------------------------- BGZF out (bgzf.c: blocks of <= 0xff00 input bytes, level 2) */
 static void bgzf_block(const uint8_t *in, size_t n, int level, std::vector<uint8_t> &out)
@@ -89,23 +91,6 @@ template <class F> static void each_contig(nabwa_index_t *ix, F f)
 	const int ns = nabwa_index_n_contigs(ix);
 	for (int i = 0; i < ns; ++i) { char name[1024]; int64_t off; int32_t len; nabwa_index_contig(ix, i, name, sizeof name, &off, &len); f(name, len); }
 }
-static std::string header_text(nabwa_index_t *ix, const std::string &old, int argc, char **argv)
-{
-	std::string pp, id; bool has_pp;
-	find_pp_tag(old, pp, id, has_pp);
-	std::string t = "@HD\tVN:1.4\n@PG\tID:" + id + (has_pp ? "\tPP:" + pp : "") + "\tPN:bwa\tVN:" + VERSION + (argc ? "\tCL:" : "");
-	for (int i = 0; i < argc; ++i) { t += argv[i]; t += i == argc - 1 ? '\n' : ' '; }
-	each_contig(ix, [&](const char *name, int32_t len) { t += std::string("@SQ\tSN:") + name + "\tLN:" + std::to_string(len) + "\n"; });
-	size_t p = 0;
-	while (p < old.size() && old[p]) {
-		size_t e = old.find('\n', p); if (e == std::string::npos) e = old.size();
-		const bool boring = e - p >= 3 && old[p] == '@' && ((old[p + 1] == 'S' && old[p + 2] == 'Q') || (old[p + 1] == 'H' && old[p + 2] == 'D'));
-		if (!boring) { t.append(old, p, e - p); t += '\n'; }
-		p = e + 1;
-	}
-	return t;
-}
-
 /* ---------------------------------------------------------------- the temporary file between the passes (bam2bam.c:1099-1135, 1733-1758)
  * With --temp-dir a batch that has to wait for the insert-size estimates does not wait in memory: its records leave as the reference's
  * temporary file holds them -- u32 length + the message of msg_init_from_pair, positioned (or finished, for a batch of single reads
@@ -180,6 +165,9 @@ struct Options {
 	bool bgzf_gpu = false;                                     /* NABWA_BGZF=gpu or gpu-dynamic */
 	bool bgzf_dynamic = false;                                 /* NABWA_BGZF=gpu-dynamic */
 	bool bgzf_in_gpu = false;                                  /* NABWA_BGZF_IN=gpu */
+	bool sort = false;                                         /* --sort: coordinate order */
+	bool sort_host = false;                                    /* NABWA_SORT=host: the runs are sorted on host threads, not on the GPU */
+	long sort_run_mib = 1024;                                  /* NABWA_SORT_RUN_MIB: record bytes of a run */
 };
 /* -1: go on; else the exit status, after the line that says why */
 static int parse_options(int argc, char **argv, Options &o)
@@ -192,7 +180,7 @@ static int parse_options(int argc, char **argv, Options &o)
 		{ "output", 1, 0, 'f' }, { "genome", 1, 0, 'g' }, { "only-aligned", 0, 0, 128 }, { "drop-aligned", 0, 0, 133 }, { "debug-bam", 0, 0, 129 },
 		{ "broken-input", 0, 0, 130 }, { "skip-duplicates", 0, 0, 131 }, { "temp-dir", 1, 0, 132 }, { "max-insert-size", 1, 0, 'a' },
 		{ "max-occurences", 1, 0, 'C' }, { "max-occurences-se", 1, 0, 'D' }, { "max-hits", 1, 0, 'h' }, { "max-discordant-hits", 1, 0, 'H' },
-		{ "chimeric-rate", 1, 0, 'c' }, { "disable-sw", 0, 0, 's' }, { "disable-isize-estimate", 0, 0, 'A' }, { "listen-port", 1, 0, 'p' }, { 0, 0, 0, 0 } };
+		{ "chimeric-rate", 1, 0, 'c' }, { "disable-sw", 0, 0, 's' }, { "disable-isize-estimate", 0, 0, 'A' }, { "listen-port", 1, 0, 'p' }, { "sort", 0, 0, 134 }, { 0, 0, 0, 0 } };
 	nabwa_gap_opt_t &go = o.go; nabwa_pe_opt_t &po = o.po;
 	nabwa_gap_init_opt(&go);
 	nabwa_pe_opt_default(&po);
@@ -218,6 +206,7 @@ static int parse_options(int argc, char **argv, Options &o)
 			case 'c': po.ap_prior = atof(optarg); break;
 			case 'A': po.force_isize = 1; break;
 			case 132: o.temp_dir = optarg; break;
+			case 134: o.sort = true; break;
 			case 'p': case '0': case '1': case '2':
 				fprintf(stderr, "[nabwa_bam2bam] this option of bwa bam2bam is not provided (0MQ modes, .sai resume)\n");
 				return 1;
@@ -230,7 +219,9 @@ static int parse_options(int argc, char **argv, Options &o)
 	if (po.n_multi < 0 || po.n_multi > NABWA_MAX_MULTI || po.N_multi < 0 || po.N_multi > NABWA_MAX_MULTI) { fprintf(stderr, "[nabwa_bam2bam] -h / -H: 0..%d\n", NABWA_MAX_MULTI); return 1; }
 	if (go.s_mm < 1 || go.s_gapo < 1 || go.s_gape < 1) { fprintf(stderr, "[nabwa_bam2bam] -M / -O / -E must be at least 1\n"); return 1; }
 	if (optind + 1 > argc || !o.prefix) {
-		fprintf(stderr, "\nUsage:   nabwa_bam2bam -g PREFIX [options of bwa bam2bam] [-f out.bam] <in.bam>\n\n");
+		fprintf(stderr, "\nUsage:   nabwa_bam2bam -g PREFIX [options of bwa bam2bam] [--sort] [-f out.bam] <in.bam>\n\n"
+						"         --sort   write the records sorted by coordinate (@HD SO:coordinate; ties keep the input order).\n"
+						"                  NABWA_SORT=gpu|host: who sorts a run (default gpu); NABWA_SORT_RUN_MIB: record bytes per run (default 1024)\n\n");
 		return 1;
 	}
 	o.input = argv[optind];
@@ -250,6 +241,19 @@ static int parse_options(int argc, char **argv, Options &o)
 	const char *finish_env = getenv("NABWA_FINISH");
 	if (finish_env && strcmp(finish_env, "gpu") && strcmp(finish_env, "host")) { fprintf(stderr, "[nabwa_bam2bam] NABWA_FINISH=%s: host or gpu\n", finish_env); return 1; }
 	if (!tool_dedup_ok()) return 1;      /* NABWA_DEDUP: the search batches read it (include/nabwa.h) */
+	/* --sort only: NABWA_SORT, who sorts a run -- gpu (default: nabwa_bam_sort_run on the first GPU) or host (bam_sort_host.hpp; the same bytes) --
+	 * and NABWA_SORT_RUN_MIB, the record bytes a run holds */
+	if (o.sort) {
+		const char *sort_env = getenv("NABWA_SORT");
+		o.sort_host = sort_env && !strcmp(sort_env, "host");
+		if (sort_env && !o.sort_host && strcmp(sort_env, "gpu")) { fprintf(stderr, "[nabwa_bam2bam] NABWA_SORT=%s: gpu or host\n", sort_env); return 1; }
+		if (const char *k = getenv("NABWA_SORT_RUN_MIB")) {
+			char *end = 0;
+			const long v = strtol(k, &end, 10);
+			if (end == k || *end || v < 1 || v > (1L << 20)) { fprintf(stderr, "[nabwa_bam2bam] NABWA_SORT_RUN_MIB=%s: a positive number of MiB\n", k); return 1; }
+			o.sort_run_mib = v;
+		}
+	}
 	return -1;
 }
 
@@ -265,9 +269,9 @@ static std::string read_input_header(BamIn &in, const char *name)
 	for (int i = 0; i < n_ref; ++i) { int32_t ln, tl; if (!in.read(&ln, 4) || ln < 0) die(name, "truncated header"); std::vector<char> nm(ln); if (!in.read(nm.data(), ln) || !in.read(&tl, 4)) die(name, "truncated header"); }
 	return old;
 }
-static void write_output_header(BgzfOut &out, nabwa_index_t *ix, const std::string &old, int argc, char **argv)
+static void write_output_header(BgzfOut &out, nabwa_index_t *ix, const std::string &old, int argc, char **argv, bool coordinate)
 {
-	const std::string text = header_text(ix, old, argc, argv);
+	const std::string text = header_text([&](auto f) { each_contig(ix, f); }, old, argc, argv, VERSION, coordinate);
 	const int32_t hl = (int32_t)text.size(), ns = nabwa_index_n_contigs(ix);
 	out.write("BAM\1", 4); out.write(&hl, 4); out.write(text.data(), text.size()); out.write(&ns, 4);
 	each_contig(ix, [&](const char *name, int32_t len) { const int32_t nl = (int32_t)strlen(name) + 1; out.write(&nl, 4); out.write(name, nl); out.write(&len, 4); });
@@ -276,6 +280,7 @@ static void write_output_header(BgzfOut &out, nabwa_index_t *ix, const std::stri
 /* ---------------------------------------------------------------- the records: a pipeline of threads, one stage each (DESIGN.md has the picture)
  *
  *   read_batches -in_ch-> create_batches -made_ch[g]-> search_on(g) -found_ch[g]-> pass1_loop, pass2_* -done_ch-> emit -out_ch-> write_out
+ *                                                                                      with --sort:  emit -out_ch-> sort_runs -sorted_ch-> write_out
  *
  * read_batches inflates the input and cuts it into batches of records (mates stay together); create_batches parses them (host work only)
  * and deals them to the GPUs in turn; search_on(g), one thread per GPU, searches that GPU's batches as they come (no random numbers, no
@@ -283,9 +288,15 @@ static void write_output_header(BgzfOut &out, nabwa_index_t *ix, const std::stri
  * order: everything that draws random numbers or fills the insert-size table happens there -- pass 1 for every batch (and pass 2 at once
  * for a batch of single reads), then, behind the barrier, pass 2 for what waited in memory or in the temporary file.  emit collects a
  * batch's output records and destroys it (host work only), a batch behind; write_out deflates and writes.
- * One path into the writer: whatever is written goes through done_ch, in the order the main thread put it there. */
+ * One path into the writer: whatever is written goes through done_ch, in the order the main thread put it there.
+ * --sort puts one stage between emit and write_out: sort_runs collects records into runs of NABWA_SORT_RUN_MIB MiB, sorts each run by coordinate
+ * (nabwa_bam_sort_run on the first GPU, or bam_sort_host under NABWA_SORT=host), keeps the sorted runs and their keys -- in memory, or with
+ * --temp-dir in a second unlinked file there -- and at the end of the input hands the writer one run as it is or the merge of several, made
+ * from the key arrays alone.  The writer still takes bytes from one thread in one order. */
 struct InBatch { std::vector<uint8_t> buf; std::vector<int64_t> off; };
-struct OutBytes { std::unique_ptr<uint8_t[]> p; size_t n = 0; };      /* no zero fill: the library writes every byte */
+struct OutBytes { std::unique_ptr<uint8_t[]> p; size_t n = 0; std::vector<int64_t> off; };      /* no zero fill: the library writes every byte.  off: --sort, the records' offsets where emit has them */
+/* a sorted run of --sort: its records in key order (in memory, or n bytes from `at` in the run file), their offsets and their keys */
+struct SortedRun { std::unique_ptr<uint8_t[]> p; size_t n = 0; long at = 0; std::vector<int64_t> off; std::vector<uint64_t> keys; };
 struct Finished { nabwa_bam_batch_t *batch = 0; OutBytes bytes; };     /* what emit takes: a batch whose records it collects, or (no batch) records already made */
 typedef Chan<nabwa_bam_batch_t*> BatchChan;
 
@@ -296,6 +307,12 @@ struct Pipeline {
 	std::vector<std::unique_ptr<BatchChan>> made_ch, found_ch; /* per GPU: parsed batches, searched batches */
 	Chan<Finished> done_ch{1};
 	Chan<OutBytes> out_ch{2};
+	/* --sort */
+	Chan<OutBytes> sorted_ch{2};
+	nabwa_bam_sort_t *sorter = 0;                             /* null under NABWA_SORT=host */
+	std::vector<SortedRun> runs;
+	FILE *run_file = 0;                                       /* --temp-dir: the sorted runs wait there */
+	uint64_t n_sorted = 0; double t_sort = 0;
 	/* the main thread's: the insert-size table, the random numbers (srand48(bns->seed), bam2bam.c:1745), what waits for pass 2 */
 	nabwa_isize_table_t *tab; uint64_t rng;
 	std::vector<nabwa_bam_batch_t*> waiting;
@@ -316,6 +333,12 @@ struct Pipeline {
 			const int fd = mkstemp(&tn[0]);
 			if (fd < 0 || !(spill = fdopen(fd, "w+b"))) die(opt.temp_dir, "cannot create a temporary file there");
 			unlink(tn.c_str());
+			if (opt.sort) {
+				std::string rn = std::string(opt.temp_dir) + "/nabwa_bam2bam_runs_XXXXXX";
+				const int rfd = mkstemp(&rn[0]);
+				if (rfd < 0 || !(run_file = fdopen(rfd, "w+b"))) die(opt.temp_dir, "cannot create a temporary file there");
+				unlink(rn.c_str());
+			}
 		}
 	}
 
@@ -454,9 +477,12 @@ struct Pipeline {
 			if (nabwa_bam_batch_t *b = f.batch) {
 				int64_t nb = 0;
 				const double ta = now_s();
+				std::vector<int64_t> &oo = f.bytes.off;               /* --sort: the offsets too */
+				if (opt.sort) { int nr = 0, nl = 0; nabwa_bam_batch_counts(b, &nr, &nl); oo.assign((size_t)nr + 1, 0); }
 				nabwa_bam_batch_output(b, 0, 0, 0, &nb);
 				f.bytes.p.reset(new uint8_t[(size_t)(nb ? nb : 1)]); f.bytes.n = (size_t)nb;
-				if (nabwa_bam_batch_output(b, f.bytes.p.get(), nb, 0, &nb) != NABWA_OK) die("output", nabwa_last_error());
+				if (nabwa_bam_batch_output(b, f.bytes.p.get(), nb, opt.sort ? oo.data() : 0, &nb) != NABWA_OK) die("output", nabwa_last_error());
+				while (oo.size() > 1 && oo[oo.size() - 1] == oo[oo.size() - 2]) oo.pop_back();      /* --only-aligned: the records that are there */
 				const double tb = now_s();
 				nabwa_bam_batch_destroy(b);
 				t_call[3] += tb - ta; t_call[4] += now_s() - tb;
@@ -467,10 +493,105 @@ struct Pipeline {
 		}
 		out_ch.close();
 	}
+	/* --sort: one run, in[off[0] .. off[n]) -> sorted, kept */
+	void sort_run(const std::vector<uint8_t> &in, const std::vector<int64_t> &off)
+	{
+		const int64_t n = (int64_t)off.size() - 1;
+		if (n <= 0) return;
+		SortedRun r;
+		r.n = in.size(); r.p.reset(new uint8_t[r.n]); r.off.resize((size_t)n + 1); r.keys.resize((size_t)n);
+		if (sorter) {
+			if (nabwa_bam_sort_run(sorter, n, in.data(), off.data(), r.p.get(), (int64_t)r.n, r.off.data(), r.keys.data()) != NABWA_OK) die("sort", nabwa_last_error());
+		} else {
+			const int64_t bad = bam_sort_host(io_threads(), n, in.data(), off.data(), r.p.get(), r.off.data(), r.keys.data());
+			if (bad >= 0) die("sort", ("record " + std::to_string(bad) + " of a run: its block_size is not what its offsets say").c_str());
+		}
+		if (run_file) {
+			r.at = ftell(run_file);
+			if (fwrite(r.p.get(), 1, r.n, run_file) != r.n) die("temporary file", "cannot write");
+			r.p.reset();
+		}
+		n_sorted += (uint64_t)n;
+		runs.push_back(std::move(r));
+	}
+	/* bytes [o, o + n) of run r for the merge: where they lie in memory, or read from the run file through the run's window */
+	struct RunWindow { std::vector<uint8_t> buf; int64_t lo = 0, hi = 0; };
+	const uint8_t *run_bytes(size_t r, int64_t o, int64_t n, std::vector<RunWindow> &win)
+	{
+		const SortedRun &R = runs[r];
+		if (R.p) return R.p.get() + o;
+		RunWindow &w = win[r];
+		if (o < w.lo || o + n > w.hi) {
+			int64_t len = n > (8 << 20) ? n : (8 << 20);
+			if (len > (int64_t)R.n - o) len = (int64_t)R.n - o;
+			w.buf.resize((size_t)len);
+			if (pread(fileno(run_file), w.buf.data(), (size_t)len, (off_t)(R.at + o)) != (ssize_t)len) die("temporary file", "truncated");
+			w.lo = o; w.hi = o + len;
+		}
+		return w.buf.data() + (o - w.lo);
+	}
+	void sort_runs()
+	{
+		const size_t limit = (size_t)opt.sort_run_mib << 20, CHUNK = (size_t)64 << 20;
+		std::vector<uint8_t> cur; std::vector<int64_t> cur_off(1, 0), walked;
+		OutBytes o;
+		while (out_ch.get(o)) {
+			const double t0 = now_s();
+			if (o.off.empty()) {                                  /* bytes that came ready-made from the temporary file: walk the block_size words */
+				walked.assign(1, 0);
+				for (size_t q = 0; q < o.n; ) { uint32_t bs; if (o.n - q < 4) die("sort", "a record cut short"); memcpy(&bs, o.p.get() + q, 4); q += 4 + (size_t)bs; if (q > o.n) die("sort", "a record cut short"); walked.push_back((int64_t)q); }
+			}
+			const std::vector<int64_t> &off = o.off.empty() ? walked : o.off;
+			const size_t nrec = off.size() - 1;
+			for (size_t i = 0; i < nrec; ) {
+				/* records i .. j - 1 go into the run: up to and including the one that fills it */
+				const int64_t room = (int64_t)(limit - cur.size());
+				size_t j = (size_t)(std::lower_bound(off.begin() + i + 1, off.end(), off[i] + room) - off.begin());
+				j = j < nrec ? j : nrec;
+				if (cur.capacity() < cur.size() + (size_t)(off[j] - off[i])) cur.reserve(std::max(2 * cur.capacity(), cur.size() + (size_t)(off[j] - off[i])));
+				const int64_t shift = (int64_t)cur.size() - off[i];
+				cur.insert(cur.end(), o.p.get() + off[i], o.p.get() + off[j]);
+				for (size_t k = i + 1; k <= j; ++k) cur_off.push_back(off[k] + shift);
+				i = j;
+				if (cur.size() >= limit) { sort_run(cur, cur_off); cur.clear(); cur_off.assign(1, 0); }
+			}
+			o.p.reset();
+			t_sort += now_s() - t0;
+		}
+		const double t0 = now_s();
+		sort_run(cur, cur_off);
+		std::vector<uint8_t>().swap(cur);
+		if (run_file && fflush(run_file) != 0) die("temporary file", "cannot write");
+		double t_blocked = 0;
+		auto hand_over = [&](OutBytes &&x) { const double tb = now_s(); sorted_ch.put(std::move(x)); t_blocked += now_s() - tb; };
+		if (runs.size() == 1 && runs[0].p) {                      /* one run: as it is */
+			OutBytes x; x.p = std::move(runs[0].p); x.n = runs[0].n;
+			hand_over(std::move(x));
+		} else if (!runs.empty()) {                               /* several: merged by their keys alone, ties to the earlier run (one run in the file: read back in order) */
+			std::vector<const std::vector<uint64_t>*> keys;
+			for (const SortedRun &r : runs) keys.push_back(&r.keys);
+			std::vector<RunWindow> win(runs.size());
+			OutBytes x; size_t x_cap = 0;
+			bam_sort_merge(keys, [&](size_t r, size_t i) {
+				const int64_t at = runs[r].off[i], n = runs[r].off[i + 1] - at;
+				if (x.n + (size_t)n > x_cap) {
+					if (x.n) hand_over(std::move(x));
+					x = OutBytes(); x_cap = (size_t)n > CHUNK ? (size_t)n : CHUNK; x.p.reset(new uint8_t[x_cap]);
+				}
+				memcpy(x.p.get() + x.n, run_bytes(r, at, n, win), (size_t)n);
+				x.n += (size_t)n;
+			});
+			if (x.n) hand_over(std::move(x));
+		}
+		if (run_file) fclose(run_file);
+		sorted_ch.close();
+		t_sort += now_s() - t0 - t_blocked;
+	}
 	void write_out()
 	{
+		Chan<OutBytes> &from = opt.sort ? sorted_ch : out_ch;
 		OutBytes o;
-		while (out_ch.get(o)) { const double t0 = now_s(); out.write(o.p.get(), o.n); o.p.reset(); t_write += now_s() - t0; }
+		while (from.get(o)) { const double t0 = now_s(); out.write(o.p.get(), o.n); o.p.reset(); t_write += now_s() - t0; }
 	}
 };
 
@@ -487,6 +608,9 @@ int main(int argc, char **argv)
 	/* the reader's handle is its own: a handle takes one call at a time, and reader and writer are two threads */
 	nabwa_bgzf_t *bgzf_in = 0;
 	if (opt.bgzf_in_gpu && nabwa_bgzf_create(devices[0], &bgzf_in) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] BGZF on the GPU: %s\n", nabwa_last_error()); return 2; }
+	/* --sort on the GPU: its handle now, so that a run without a usable device ends before anything is written */
+	nabwa_bam_sort_t *sorter = 0;
+	if (opt.sort && !opt.sort_host && nabwa_bam_sort_create(devices[0], &sorter) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] --sort on the GPU: %s\n", nabwa_last_error()); return 2; }
 	std::vector<nabwa_index_t*> ixs;
 	{
 		std::string err;
@@ -511,11 +635,14 @@ int main(int argc, char **argv)
 	if (!of) die(opt.ofile, "cannot create");
 	BgzfOut out{ of, {}, 2, bgzf, {} };
 	if (opt.bgzf_dynamic) out.codes = NABWA_BGZF_CODES_DYNAMIC;
-	write_output_header(out, ixs[0], old, argc, argv);
+	write_output_header(out, ixs[0], old, argc, argv, opt.sort);
 
 	const bool timing = getenv("NABWA_TIMING") != 0;
 	const double t_loop = now_s();
 	Pipeline P(opt, ixs, in, out, genome_len, seed);
+	P.sorter = sorter;
+	std::thread sort_thread;
+	if (opt.sort) sort_thread = std::thread(&Pipeline::sort_runs, &P);
 	std::thread reader(&Pipeline::read_batches, &P), creator(&Pipeline::create_batches, &P), finisher(&Pipeline::emit, &P), writer(&Pipeline::write_out, &P);
 	std::vector<std::thread> searchers;
 	for (size_t g = 0; g < P.n_dev; ++g) searchers.emplace_back(&Pipeline::search_on, &P, g);
@@ -527,11 +654,14 @@ int main(int argc, char **argv)
 	P.pass2_waiting();
 	P.pass2_spilled();
 	P.done_ch.close();
-	finisher.join(); writer.join();
+	finisher.join();
+	if (opt.sort) sort_thread.join();
+	writer.join();
 
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: start-up (device, index, headers) %.3f s, records %.3f s\n", t_loop - t_main, now_s() - t_loop);
 	if (timing) { double ts = 0; for (double x : P.t_search) ts += x; fprintf(stderr, "[nabwa_bam2bam] timing: search threads (%zu GPU%s) %.3f s busy\n", P.n_dev, P.n_dev > 1 ? "s" : "", ts); }
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: library calls: create %.3f s, pass 1 %.3f s, pass 2 %.3f s, output %.3f s, destroy %.3f s\n", P.t_call[0], P.t_call[1], P.t_call[2], P.t_call[3], P.t_call[4]);
+	if (timing && opt.sort) fprintf(stderr, "[nabwa_bam2bam] timing: sort thread %.3f s busy (%zu run(s) sorted on the %s, then handed on or merged)\n", P.t_sort, P.runs.size(), sorter ? "gpu" : "host");
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: reader thread %.3f s busy (%.3f s of it inflate, %s), passes 1 and 2 on this thread %.3f s (+ %.3f s waiting for input; the output thread waited %.3f s for the writer), writer thread %.3f s busy (deflate + write; %s)\n",
 						P.t_read, in.t_inflate, in.bgzf ? (bgzf_in ? "BGZF blocks on the GPU" : "BGZF blocks in parallel") : in.raw ? "not compressed" : "one gzip stream", P.t_lib, P.t_wait_in, P.t_wait_out, P.t_write,
 						opt.bgzf_dynamic ? "BGZF on the GPU, dynamic Huffman codes" : opt.bgzf_gpu ? "BGZF on the GPU" : "zlib level 2 on host threads");
@@ -541,9 +671,11 @@ int main(int argc, char **argv)
 	out.close();
 	if (bgzf) nabwa_bgzf_destroy(bgzf);
 	if (bgzf_in) nabwa_bgzf_destroy(bgzf_in);
+	if (sorter) nabwa_bam_sort_destroy(sorter);
 	nabwa_isize_table_destroy(P.tab);
 	tool_dedup_cache_summary(ixs);
 	for (nabwa_index_t *p : ixs) nabwa_index_destroy(p);
 	final_rename(opt.ofile, true);
+	if (opt.sort) fprintf(stderr, "[nabwa_bam2bam] sorted %llu records in %zu run(s) on the %s\n", (unsigned long long)P.n_sorted, P.runs.size(), opt.sort_host ? "host" : "gpu");
 	return 0;
 }

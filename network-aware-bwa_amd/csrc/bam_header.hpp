@@ -1,5 +1,5 @@
 // bam_header.hpp -- the text header `bwa bam2bam` writes (bam2bam.c:164-301): @HD, a new @PG chained to the old ones, @SQ from the
-// index, then every old line except @HD / @SQ.  Host code, used by bam2bam_main.cpp and (alone) by a CPU test.
+// index, then every old line except @HD / @SQ.  Host code, used by bam2bam_main.cpp and (alone) by CPU tests.
 //
 // The one subtle part is WHICH old @PG the new one names as its predecessor: the reference collects the IDs and the PP values in two
 // string sets and takes "the first ID that nobody links to" in the ITERATION ORDER OF ITS HASH SET (bam2bam.c:246-255) -- with one
@@ -89,4 +89,24 @@ static inline void find_pp_tag(const std::string &h, std::string &pp, std::strin
 	for (size_t i = 0; i < present.key.size(); ++i) if (present.full[i] && !linked.has(present.key[i])) { pp = present.key[i]; has_pp = true; break; }
 	id = "bwa";
 	for (int n = 1; present.has(id); ++n) id = "bwa-" + std::to_string(n);
+}
+
+/* the whole text (bam2bam.c:164-301).  contigs(f) calls f(name, length) for the contigs of the index, in order; version: the VN: of the new
+ * @PG line.  coordinate: the records that follow are sorted by coordinate (nabwa_bam2bam --sort, an addition of this tool) and @HD says so;
+ * without it the text is the reference's, byte for byte */
+template <class Contigs> static inline std::string header_text(Contigs contigs, const std::string &old, int argc, char **argv, const char *version, bool coordinate = false)
+{
+	std::string pp, id; bool has_pp;
+	find_pp_tag(old, pp, id, has_pp);
+	std::string t = std::string(coordinate ? "@HD\tVN:1.4\tSO:coordinate\n" : "@HD\tVN:1.4\n") + "@PG\tID:" + id + (has_pp ? "\tPP:" + pp : "") + "\tPN:bwa\tVN:" + version + (argc ? "\tCL:" : "");
+	for (int i = 0; i < argc; ++i) { t += argv[i]; t += i == argc - 1 ? '\n' : ' '; }
+	contigs([&](const char *name, int32_t len) { t += std::string("@SQ\tSN:") + name + "\tLN:" + std::to_string(len) + "\n"; });
+	size_t p = 0;
+	while (p < old.size() && old[p]) {
+		size_t e = old.find('\n', p); if (e == std::string::npos) e = old.size();
+		const bool boring = e - p >= 3 && old[p] == '@' && ((old[p + 1] == 'S' && old[p + 2] == 'Q') || (old[p + 1] == 'H' && old[p + 2] == 'D'));
+		if (!boring) { t.append(old, p, e - p); t += '\n'; }
+		p = e + 1;
+	}
+	return t;
 }

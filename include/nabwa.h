@@ -544,7 +544,8 @@ int nabwa_worker_core(nabwa_worker_t *w, nabwa_recv_fn recv, nabwa_send_fn send,
 void nabwa_worker_counts(const nabwa_worker_t *w, uint64_t out[4]);
 
 /* Read-back of the index parts derived at load time (tests): what 0 = full SA, 1 = inverse SA, 2 = text bases (one per
- * word), 3 = interval-table entries {k, l} of the last level (two words per key), 4 = the table's depth T (one word). */
+ * word), 3 = interval-table entries {k, l} of the last level (two words per key), 4 = the table's depth T (one word),
+ * 5 = the primary keys of table levels first.. (levels 0..16, one word each: the key whose interval holds the primary row, ~0u = none). */
 int nabwa_index_export(const nabwa_index_t *ix, int which, int what, uint64_t first, uint64_t n, uint32_t *out);
 
 /* Rank primitives for tests: Occ of all four bases at rows k[i] (bwt_occ4, bwt.c:159-176). */

@@ -836,7 +836,8 @@ class Index:
         return nm[:n], [raw[off[i]:off[i + 1] - 1].decode() for i in range(n)]
 
     def export(self, which, what, first, n):
-        """derived index parts for tests (nabwa_index_export): 0 full SA, 1 inverse SA, 2 text bases, 3 interval table, 4 its depth"""
+        """derived index parts for tests (nabwa_index_export): 0 full SA, 1 inverse SA, 2 text bases, 3 interval table, 4 its depth,
+        5 the primary keys of its levels first.. (levels 0..16)"""
         out = np.zeros(int(n) * (2 if what == 3 else 1), np.uint32)
         _chk(lib().nabwa_index_export(self._h, int(which), int(what), int(first), int(n), _ptr(out)))
         return out.reshape(-1, 2) if what == 3 else out

@@ -142,6 +142,30 @@ extern "C" void nabwa_launch_kmer_level(const DevBwt *B, const uint2 *prev, uint
 	hipLaunchKernelGGL(kmer_level_kernel, dim3((unsigned int)((n_par + 255) / 256)), dim3(256), 0, s, *B, prev, cur, n_par);
 }
 
+// The primary key of a level: the one key whose interval holds the primary row -- the string that is the indexed text's own prefix.
+// Every row of an interval carries one BWT symbol A/C/G/T except the primary row, so width(parent) = sum of its children's widths
+// + [primary row inside the parent's interval]: kernel W takes a level's width from the children it loads anyway (fm_search.hip)
+// and needs this key for the correction.  Found in the table itself, so no digit order can be got wrong; *out keeps its preset
+// 0xffffffff where the level has none (a text shorter than the level).
+// One thread per parent, as in kmer_level_kernel (level 16 has 2^32 keys, more than a launch has threads): its four children.
+__global__ __launch_bounds__(256) void kmer_primary_kernel(const uint2 *__restrict__ lv, uint64_t n_par, uint32_t primary, uint32_t *__restrict__ out)
+{
+	const uint64_t idx = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (idx >= n_par) return;
+	const uint4 *const src = (const uint4*)(lv + 4 * idx);
+	const uint4 a = src[0], b = src[1];
+	const uint2 e[4] = { make_uint2(a.x, a.y), make_uint2(a.z, a.w), make_uint2(b.x, b.y), make_uint2(b.z, b.w) };
+#pragma unroll
+	for (int c = 0; c < 4; ++c)
+		if (e[c].x <= e[c].y && e[c].x <= primary && primary <= e[c].y) *out = (uint32_t)(4 * idx + c);
+}
+
+extern "C" void nabwa_launch_kmer_primary(const uint2 *lv, uint64_t n_keys, uint32_t primary, uint32_t *out, hipStream_t s)
+{
+	const uint64_t n_par = n_keys / 4;
+	hipLaunchKernelGGL(kmer_primary_kernel, dim3((unsigned int)((n_par + 255) / 256)), dim3(256), 0, s, lv, n_par, primary, out);
+}
+
 // Full suffix array, its inverse and the text from the BWT and the row-sampled SA (bwt.c:72-81 is the per-row
 // walk this replaces).  One thread per SAMPLED row r (SA value v): LF(r) is the row of the suffix one position
 // to the left, so walking LF hands out v-1, v-2, ... until the next sampled row, and the BWT character met at each

@@ -108,13 +108,18 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 	uint32_t kk = 0, ll = 0, pw = 0; int bid = 0;
 	uint32_t wkey = 0xffffffffu; bool tok = false; int tbase = 0;   // interval-table key of the KT symbols from position tbase of this phase (the current restart point)
 	const int KT = (int)P.bwt[0].kmer_T, LW = (int)P.bwt[0].kmer_LW;
+	// the primary keys of the table's levels (fm_search.hpp, fm_index.hip): [strand][level], picked per lane in a table trip
+	__shared__ uint32_t s_pk[2 * NABWA_PK_LEVELS];
+	const bool quads = (P.text_mode & TM_W_QUADS) && P.ixtab;
+	if (threadIdx.x < 2 * NABWA_PK_LEVELS) s_pk[threadIdx.x] = quads ? P.ixtab[NABWA_IXTAB_WORDS + threadIdx.x] : 0xffffffffu;
+	__syncthreads();
+	bool nflag = true;                                          // this strand has an N (word PW-1 of its packed bases), read once when the item is taken
 	// after a restart (bwtaln.c:66-70) the pattern begins anew at the next position: its key comes from the packed read
 	auto rekey = [&](int from) {
 		tok = false; tbase = from;
-		if (!KT || !P.rd_pack || from + 4 >= n) return;
+		if (nflag || from + 4 >= n) return;                       // an N somewhere in this strand (or no table, no packed reads): step by step
 		const int PW = P.pack_stride / 2;
 		const uint32_t *const pk = P.rd_pack + (size_t)rid * P.pack_stride + x * PW;
-		if (pk[PW - 1]) return;                                   // an N somewhere in this strand: step by step
 		const int q = sbase + from;
 		const uint32_t w0 = pk[q >> 4], w1 = pk[(q >> 4) + 1], sh = ((uint32_t)q & 15u) << 1;
 		const uint32_t k16 = sh ? (w0 << sh) | (w1 >> (32u - sh)) : w0;
@@ -151,6 +156,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 					else if (len > 0) {
 						run = true; phase = 0; wi = 0; n = len; sbase = 0; tmode = false;
 						if (KT) { wkey = P.rd_key[6 * (size_t)rid + 2 + x]; tok = wkey != 0xffffffffu; }
+						nflag = !KT || !P.rd_pack || P.rd_pack[(size_t)rid * P.pack_stride + (x + 1u) * (uint32_t)(P.pack_stride / 2) - 1u] != 0u;
 						tbase = 0;
 						kk = 0; ll = BX(seq_len); bid = 0; pw = 0; blo = bhi = 0;
 					} else { if (x == 0u) P.rd_nN[rid] = 0; if (P.rd_cls) P.rd_cls[2 * (size_t)rid + x] = 0; }   // (an empty read: nothing to search)
@@ -212,12 +218,37 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 			// interval table (fm_index.hip) -- four independent 8-byte loads, the low levels cache-resident -- instead
 			// of four dependent rank queries.  An empty entry is the reference's restart (bwtaln.c:66-70): from there on
 			// the prefix is no longer the read's, so the rest of the phase steps normally.
+			// Two levels per load (quads): the four children of a key are 32 contiguous bytes of the next level, and every row of the
+			// parent's interval carries one BWT symbol A/C/G/T except the primary row -- so width(parent) = the sum of its children's
+			// widths (an empty child {1, 0} gives 0) + 1 if the parent is its level's primary key.  The children of K(t1) and of K(t1+2)
+			// give the widths of levels t1 and t1+2 that way (handed to out_pos as {1, width}) and the entries of t1+1 and t1+3 directly:
+			// two line requests per trip instead of four, and the interval left behind is the real one of the last level.
 			uint2 tv[4];
 			const uint2 *const lo = BX(kmer_lo);
+			const int t1 = wi - tbase + 1;
+			if (quads) {
+				uint4 qd[2][2];
 #pragma unroll
-			for (int u = 0; u < 4; ++u) {
-				const int t = wi - tbase + u + 1;
-				tv[u] = (lo + (size_t)((((uint64_t)1 << (2 * t)) - 4ull) / 3ull))[wkey >> (2 * (KT - t))];
+				for (int h = 0; h < 2; ++h) {
+					const int t = t1 + 2 * h;
+					const uint4 *const p = (const uint4*)(lo + LVO(t + 1) + 4 * (size_t)(wkey >> (2 * (KT - t))));
+					qd[h][0] = p[0]; qd[h][1] = p[1];
+				}
+#pragma unroll
+				for (int h = 0; h < 2; ++h) {
+					const int t = t1 + 2 * h;
+					const uint32_t ch = wkey >> (2 * (KT - t - 1)), c = ch & 3u;
+					const uint4 a = qd[h][0], b = qd[h][1];
+					const uint32_t sum = (a.y - a.x) + (a.w - a.z) + (b.y - b.x) + (b.w - b.z) + 4u + ((ch >> 2) == s_pk[x * NABWA_PK_LEVELS + t] ? 1u : 0u);
+					tv[2 * h] = make_uint2(1u, sum);
+					tv[2 * h + 1] = c == 0u ? make_uint2(a.x, a.y) : (c == 1u ? make_uint2(a.z, a.w) : (c == 2u ? make_uint2(b.x, b.y) : make_uint2(b.z, b.w)));
+				}
+			} else {
+#pragma unroll
+				for (int u = 0; u < 4; ++u) {
+					const int t = t1 + u;
+					tv[u] = (lo + LVO(t))[wkey >> (2 * (KT - t))];
+				}
 			}
 #pragma unroll
 			for (int u = 0; u < 4; ++u) {

@@ -12,6 +12,8 @@
 #define NABWA_ST_HITCAP    4   // kernel D: more hit rows than the wide result rows (NABWA_ALNCAP2): searched again with longer lists
 #define NABWA_ST_GROWN     5   // resolved by such a second search: the rows are the block grown[wide_idx[read]] names
 
+#define TM_W_QUADS 8
+
 struct SearchParams {
 	DevBwt bwt[2];
 	// reads (device): codes 0-3, 4 = N; seq = read reversed, rseq = reverse complement
@@ -29,7 +31,8 @@ struct SearchParams {
 	size_t wstride;
 	uint32_t woff_bid, woff_sbid;
 	uint32_t WL, WLB, SLB;
-	int text_mode;                            // 0: never leave the FM-index (the touch-counting run); 1: text mode where the index has it
+	int text_mode;                            // 0: never leave the FM-index (the touch-counting run); bit 0 / 1: text mode in kernel W / S where the index has it; bit 2: key form in S;
+	                                          // bit 3 (TM_W_QUADS, NABWA_W_QUADS): kernel W's table trips load two levels per 32 bytes
 	const uint32_t *rd_key;                   // per read six interval-table keys [6*rid + ..] (see pad_reads_kernel), ~0u = none
 	uint8_t *rd_nN;                           // per read: number of N in the read, saturated at 255
 	// per-lane scratch of kernel S: the arena
@@ -61,9 +64,15 @@ struct SearchParams {
 /* The per-index constants a lane of kernel D selects by its entry's strand, as a table the kernel copies into LDS (fm_deep_body.hpp): as
  * selects over the kernel's arguments they were a dozen scalar registers live across the chain loop -- spilled, and read back lane by lane
  * (v_readlane) at every use.  (The same for kernel S -- all its index pointers through such a table -- took its spilled scalars from 126 to 73
- * and made it 6 % SLOWER: an LDS round trip in front of every load.  Measured in round 3, not kept.)  Per index NABWA_IXTAB_STRIDE words: */
+ * and made it 6 % SLOWER: an LDS round trip in front of every load.  Measured in round 3, not kept.)  Per index NABWA_IXTAB_STRIDE words.
+ * Behind these NABWA_IXTAB_WORDS words the device table carries, per index, the NABWA_PK_LEVELS primary keys of the interval table (word
+ * NABWA_IXTAB_WORDS + NABWA_PK_LEVELS * index + level, levels 0..16; ~0u: the level has none): the one key of a level whose interval holds the
+ * primary row.  Kernel W copies those into its LDS and picks one per lane by strand and level (fm_search.hip, table trip); kernel D copies
+ * its own NABWA_IXTAB_WORDS and never sees them. */
 #define NABWA_IXTAB_STRIDE 24
 #define NABWA_IXTAB_WORDS  48
+#define NABWA_PK_LEVELS    17
+#define NABWA_IXTAB_ALL    (NABWA_IXTAB_WORDS + 2 * NABWA_PK_LEVELS)
 #define IX_BK 0                  /* pointers: two words each, low word first */
 #define IX_KMER 2
 #define IX_KMER_LO 4

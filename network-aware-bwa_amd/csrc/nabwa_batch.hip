@@ -345,14 +345,18 @@ static int working_buffers(nabwa_batch *b, const BatchShape &s)
 	memset(&P, 0, sizeof(P));
 	P.bwt[0] = ix->bwt[0]; P.bwt[1] = ix->bwt[1];
 	{	/* the per-index constants the search kernels pick per lane, as a table for their LDS (fm_search.hpp) */
-		uint32_t tab[NABWA_IXTAB_WORDS];
+		uint32_t tab[NABWA_IXTAB_ALL];
 		nabwa_ixtab_fill(tab, ix->bwt);
+		memcpy(tab + NABWA_IXTAB_WORDS, ix->kmer_pk, sizeof ix->kmer_pk);      /* kernel W's primary keys, behind kernel D's words */
 		HIP_CHECK(b->d_ixtab.get(ix, sizeof tab));
 		HIP_CHECK(hipMemcpy(b->d_ixtab, tab, sizeof tab, hipMemcpyHostToDevice));
 		P.ixtab = b->d_ixtab;
 	}
 	P.seq = b->d_seq; P.rseq = b->d_rseq; P.poff = b->d_poff; P.rd_len = b->d_len; P.rd_maxdiff = b->d_md; P.rd_maxgapo = b->d_mg; P.rd_key = b->d_key; P.rd_pack = b->d_pack; P.pack_stride = b->pack_stride;
-	P.text_mode = env_int("NABWA_TEXT_KERNELS", 7);      /* bit 0: text mode in the width kernel, bit 1: in the search kernel, bit 2: key form in the search kernel */
+	P.text_mode = env_int("NABWA_TEXT_KERNELS", 7) & 7;      /* bit 0: text mode in the width kernel, bit 1: in the search kernel, bit 2: key form in the search kernel */
+	/* kernel W (fm_search.hip; profiles/width_requests_bench.txt): NABWA_W_QUADS -- a table trip takes two levels from each 32 bytes it loads, the
+	 * parent's width as the sum over its children (0: one 8-byte entry per level, as before v14) */
+	if (env_int("NABWA_W_QUADS", 1)) P.text_mode |= TM_W_QUADS;
 	if (ix->bwt[0].kmer_T != ix->bwt[1].kmer_T) P.bwt[0].kmer_T = P.bwt[1].kmer_T = 0;
 	P.ids = 0; P.n = n;
 	P.s_mm = opt->s_mm; P.s_gapo = opt->s_gapo; P.s_gape = opt->s_gape; P.mode = opt->mode;

@@ -22,6 +22,7 @@ static int build_one(nabwa_index *ix, int t_, const uint32_t *words, uint64_t n_
 	if (on_device) HIP_CHECK(hipMemcpy(hdr, words, 20, hipMemcpyDeviceToHost)); else memcpy(hdr, words, 20);
 	DevBwt &B = ix->bwt[t_];
 	memset(&B, 0, sizeof(B));
+	memset(ix->kmer_pk[t_], 0xff, sizeof ix->kmer_pk[t_]);
 	B.primary = hdr[0]; B.L2[0] = 0; B.L2[1] = hdr[1]; B.L2[2] = hdr[2]; B.L2[3] = hdr[3]; B.seq_len = hdr[4];
 	/* the reference's loader computes n_sa = (seq_len + sa_intv) / sa_intv in 32 bits (bwtio.c:175, bwt.c:56): above this it wraps */
 	if (B.seq_len > 0xffffffdfu) return nabwa_fail(NABWA_EINVAL, "seq_len above 0xffffffdf: the reference's SA count wraps (bwtio.c:175)");
@@ -77,8 +78,16 @@ static int build_one(nabwa_index *ix, int t_, const uint32_t *words, uint64_t n_
 				nabwa_launch_kmer_level(&B, prev, cur, (uint64_t)1 << (2 * t), 0);
 				prev = cur; cur += (size_t)1 << (2 * t);
 			}
+			/* the primary key of every level, for kernel W's widths by summing (fm_index.hip: kmer_primary_kernel) */
+			DevBuf pk;
+			if (int r = pk.get(sizeof ix->kmer_pk[t_])) return r;
+			HIP_CHECK(hipMemsetAsync(pk.p, 0xff, sizeof ix->kmer_pk[t_], 0));
+			for (int t = 1; t <= T; ++t)
+				nabwa_launch_kmer_primary(ix->kmer[t_] + table_entries(t - 1), (uint64_t)1 << (2 * t), B.primary, pk.as<uint32_t>() + t, 0);
 			HIP_CHECK(hipGetLastError());
+			HIP_CHECK(hipMemcpy(ix->kmer_pk[t_], pk.p, sizeof ix->kmer_pk[t_], hipMemcpyDeviceToHost));
 			HIP_CHECK(hipDeviceSynchronize());
+			HIP_CHECK(pk.release());
 			ix->bytes += lo_n * 8;
 			B.kmer = prev; B.kmer_T = (uint32_t)T; B.kmer_lo = ix->kmer[t_]; B.kmer_LW = (uint32_t)T;
 		}
@@ -188,13 +197,19 @@ extern "C" void nabwa_index_destroy(nabwa_index_t *ix)
 }
 
 /* Read-back of the derived index parts (tests): what 0 = sa_full[first..), 1 = isa[first..), 2 = text bases first.. (one per
- * word), 3 = interval table, level kmer_T: entry pairs {k, l} of keys first.. (2 words each), 4 = kmer_T (one word). */
+ * word), 3 = interval table, level kmer_T: entry pairs {k, l} of keys first.. (2 words each), 4 = kmer_T (one word), 5 = the primary keys of
+ * levels first.. (level 0..16; ~0u: none). */
 extern "C" int nabwa_index_export(const nabwa_index_t *ix, int which, int what, uint64_t first, uint64_t n, uint32_t *out)
 {
 	if (!ix || !out || which < 0 || which > 1) return nabwa_fail(NABWA_EINVAL, "bad argument");
 	HIP_CHECK(hipSetDevice(ix->device));
 	const DevBwt &B = ix->bwt[which];
 	if (what == 4) { out[0] = B.kmer_T; return NABWA_OK; }
+	if (what == 5) {
+		if (first + n > NABWA_PK_LEVELS) return nabwa_fail(NABWA_EINVAL, "out of range");
+		memcpy(out, ix->kmer_pk[which] + first, n * 4);
+		return NABWA_OK;
+	}
 	if (what == 3) {
 		if (!B.kmer || first + n > (1ull << (2 * B.kmer_T))) return nabwa_fail(NABWA_EINVAL, "no interval table / out of range");
 		HIP_CHECK(hipMemcpy(out, B.kmer + first, n * 8, hipMemcpyDeviceToHost));

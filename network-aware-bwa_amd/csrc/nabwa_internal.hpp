@@ -43,6 +43,7 @@ struct nabwa_index {
 	uint2 *kmer[2] = {}, *kmer_top[2] = {};  // interval table: levels 1..LW back to back; level T on its own when T > LW (else inside the former)
 	uint64_t bytes = 0;
 	int kmer_T_pick = -1;           // depth of the interval tables, decided when the first direction is built
+	uint32_t kmer_pk[2][NABWA_PK_LEVELS] = {};   // per level 0..16 its primary key (fm_index.hip), ~0u where it has none; behind the ixtab words of every batch
 	nabwa_reference *ref = nullptr;
 	nabwa_reference *ref_nt = nullptr;   // colour index: the annotations of `ref` over the bases of <prefix>.nt.pac (cs2nt.hip)
 	uint8_t *d_ntpac = nullptr;          // ... and those bases in HBM, with their size in bytes

@@ -705,6 +705,52 @@ int nabwa_bam_sort_run(nabwa_bam_sort_t *s, int64_t n_rec, const uint8_t *in, co
 int nabwa_bam_sort(int device, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out);
 int nabwa_bam_sort_times(const nabwa_bam_sort_t *s, float ms[6]);
 
+/* ---- damage profile of finished BAM records on the GPU (nabwa_damage.hip, damage_kernels.hip, damage_body.hpp): the
+ * substitutions of the mapped reads against the reference by distance from the read's ends, and the read lengths.  Records and offsets are
+ * those of nabwa_bam_sort.  A record falls into the first class that fits, each with its counter in stats[]:
+ *   skipped_flags  flag & exclude_flags, or (flag & require_flags) != require_flags
+ *   skipped_place  refID < 0, refID >= the index's contigs, or pos < 0
+ *   skipped_mapq   mapq < min_mapq
+ *   skipped_empty  l_seq == 0 or n_cigar_op == 0
+ *   counted        the CIGAR is walked from rp = contig[refID].offset + pos: M, = and X consume read and reference, I and S the read, D and
+ *                  N the reference, H, P and the unassigned codes nothing.  A column of M / = / X with read index qi (0-based in the
+ *                  stored seq, L = l_seq) and reference position k: a 4-bit read code other than A, C, G, T skips it
+ *                  (columns_skipped_read); else k >= l_pac or k in a hole of the .amb skips it (columns_skipped_ref); else with the codes
+ *                  A C G T = 0 1 2 3, forward strand (r, q, d5, d3) = (ref, read, qi, L - 1 - qi), flag 0x10 (3 - ref, 3 - read, L - 1 -
+ *                  qi, qi) -- the substitution on the read's own strand, whose 5' end is the last stored base -- one is added to
+ *                  sub5[min(d5, n_pos)][r][q] and to sub3[min(d3, n_pos)][r][q] (row n_pos: everything further in, the baseline; a column
+ *                  of a short read counts near both ends) and to columns_counted; one to len_hist[min(L, NABWA_DAMAGE_LEN_BINS - 1)].
+ *                  A record that runs over a contig's end is counted against the concatenated reference, as the reference's MD is.
+ * NABWA_EINVAL  a null handle, index or option block; n_pos outside 1..256, which_ref outside 0..1; an index with no attached reference (no
+ *               nucleotide reference when which_ref is 1); n_rec < 0 or above 0x7fffffff; offsets that do not increase; a record shorter
+ *               than 36 bytes -- decided on the host from the arguments alone, the options before the index is looked at, everything
+ *               before the device is
+ * NABWA_EDATA   a block_size + 4 that is not the record's extent; 36 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq beyond the
+ *               record, counted or skipped; a counted record whose CIGAR does not consume l_seq read bases.  nabwa_last_error names the
+ *               lowest such record, and the failed call adds nothing to the handle's totals
+ * NABWA_ENODEV  no device;  NABWA_ENOMEM  the call's records (their bytes + 8 per record) do not fit the device: the caller picks the size
+ * n_rec == 0 is NABWA_OK.  There is no CPU path here.  No byte outside a record and no .pac byte at or past l_pac / 4 + 1 is read.
+ * The handle works on the index's device with the index's copy of the reference (that of NABWA_FINISH=gpu: no second one), keeps its
+ * stream and its device buffers (they grow and stay) between calls, one call at a time; THE INDEX MUST OUTLIVE THE HANDLE.
+ * nabwa_damage_fetch: the totals of the successful calls since create / clear -- sub5 and sub3 (n_pos + 1) * 16 words each, index (p * 4 +
+ * r) * 4 + q; len_hist NABWA_DAMAGE_LEN_BINS words; stats NABWA_DAMAGE_N_STATS words; any pointer may be NULL.  The counts are integer
+ * sums: the same records give the same tables bit for bit, in any order and any split into calls.
+ * nabwa_damage_times: device-event milliseconds of the last successful add -- upload, kernel, adding the call's table to the totals. */
+#define NABWA_DAMAGE_LEN_BINS 1024
+#define NABWA_DAMAGE_MAX_POS  256
+enum { NABWA_DAMAGE_STAT_SEEN = 0, NABWA_DAMAGE_STAT_COUNTED, NABWA_DAMAGE_STAT_SKIPPED_FLAGS, NABWA_DAMAGE_STAT_SKIPPED_PLACE,
+	   NABWA_DAMAGE_STAT_SKIPPED_MAPQ, NABWA_DAMAGE_STAT_SKIPPED_EMPTY, NABWA_DAMAGE_STAT_COLUMNS_COUNTED,
+	   NABWA_DAMAGE_STAT_COLUMNS_SKIPPED_READ, NABWA_DAMAGE_STAT_COLUMNS_SKIPPED_REF, NABWA_DAMAGE_N_STATS };
+typedef struct { int32_t n_pos; int32_t min_mapq; uint32_t exclude_flags; uint32_t require_flags; int32_t which_ref; int32_t pad; } nabwa_damage_opt_t;
+typedef struct nabwa_damage nabwa_damage_t;
+void nabwa_damage_default_opt(nabwa_damage_opt_t *o);      /* n_pos 25, min_mapq 0, exclude_flags 0xF04 (unmapped, secondary, QC-fail, duplicate, supplementary), require_flags 0, which_ref 0 */
+int nabwa_damage_create(nabwa_index_t *ix, const nabwa_damage_opt_t *opt, nabwa_damage_t **out);
+int nabwa_damage_add(nabwa_damage_t *d, int64_t n_rec, const uint8_t *in, const int64_t *in_off);
+int nabwa_damage_fetch(nabwa_damage_t *d, uint64_t *sub5, uint64_t *sub3, uint64_t *len_hist, uint64_t *stats);
+int nabwa_damage_clear(nabwa_damage_t *d);
+void nabwa_damage_destroy(nabwa_damage_t *d);
+int nabwa_damage_times(const nabwa_damage_t *d, float ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -380,6 +380,16 @@ def lib():
         L.nabwa_bam_sort_run.argtypes = [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P]
         L.nabwa_bam_sort.argtypes = [C.c_int, C.c_int64, _P, _P, _P, C.c_int64, _P, _P]
         L.nabwa_bam_sort_times.argtypes = [_P, _P]
+    if hasattr(L, "nabwa_damage_add"):             # (likewise)
+        L.nabwa_damage_default_opt.argtypes = [_P]
+        L.nabwa_damage_default_opt.restype = None
+        L.nabwa_damage_create.argtypes = [_P, _P, _P]
+        L.nabwa_damage_add.argtypes = [_P, C.c_int64, _P, _P]
+        L.nabwa_damage_fetch.argtypes = [_P, _P, _P, _P, _P]
+        L.nabwa_damage_clear.argtypes = [_P]
+        L.nabwa_damage_destroy.argtypes = [_P]
+        L.nabwa_damage_destroy.restype = None
+        L.nabwa_damage_times.argtypes = [_P, _P]
     if hasattr(L, "nabwa_finish_counts"):          # (a library of an earlier build, loaded through NABWA_LIB for an A/B run, has no such entries)
         L.nabwa_refine_gapped_core.argtypes = [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int]
         L.nabwa_cal_md.argtypes = [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int64]
@@ -630,6 +640,72 @@ class BamSort:
     def close(self):
         if self._h:
             lib().nabwa_bam_sort_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DamageOpt(C.Structure):
+    """nabwa_damage_opt_t"""
+    _fields_ = [("n_pos", C.c_int32), ("min_mapq", C.c_int32), ("exclude_flags", C.c_uint32), ("require_flags", C.c_uint32), ("which_ref", C.c_int32), ("pad", C.c_int32)]
+
+
+DAMAGE_LEN_BINS = 1024
+damage_stat_names = ("seen", "counted", "skipped_flags", "skipped_place", "skipped_mapq", "skipped_empty", "columns_counted", "columns_skipped_read",
+                     "columns_skipped_ref")       # the slots of stats[], NABWA_DAMAGE_STAT_*
+
+
+class Damage:
+    """the damage profile of finished BAM records on the GPU (nabwa_damage_*): the substitutions of the mapped reads against the index's
+    reference by distance from the read's ends, and the read lengths; include/nabwa.h has the rules.  The handle works on the index's device
+    with the index's copy of the reference, and the index must outlive it"""
+
+    def __init__(self, index, n_pos=25, min_mapq=0, exclude_flags=0xF04, require_flags=0, which_ref=0):
+        self._h = _P()
+        self._index = index                        # (kept alive)
+        self.n_pos = int(n_pos)
+        o = DamageOpt(int(n_pos), int(min_mapq), int(exclude_flags), int(require_flags), int(which_ref), 0)
+        _chk(lib().nabwa_damage_create(index._h, C.byref(o), C.byref(self._h)))
+
+    def add(self, records, off=None):
+        """counts the records of an uncompressed BAM record stream; off: their offsets (n + 1), None: walked from the block_size words on
+        the host.  A NabwaError of code EDATA names the first damaged record, and that call has counted nothing"""
+        a = np.frombuffer(bytes(records), np.uint8) if not isinstance(records, np.ndarray) else np.ascontiguousarray(records, np.uint8)
+        off = bam_record_offsets(a) if off is None else np.ascontiguousarray(off, np.int64)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError("off: n + 1 offsets")
+        _chk(lib().nabwa_damage_add(self._h, off.size - 1, _ptr(a) if a.size else None, _ptr(off)))
+
+    def fetch(self):
+        """-> (sub5, sub3, len_hist, stats): uint64 arrays of shape (n_pos + 1, 4, 4), (n_pos + 1, 4, 4), (1024,) and (len(damage_stat_names),);
+        sub5[p][r][q]: reference base r read as q at distance p from the 5' end, on the read's own strand; row n_pos: everything further in"""
+        sub5, sub3 = np.zeros((self.n_pos + 1, 4, 4), np.uint64), np.zeros((self.n_pos + 1, 4, 4), np.uint64)
+        len_hist, stats = np.zeros(DAMAGE_LEN_BINS, np.uint64), np.zeros(len(damage_stat_names), np.uint64)
+        _chk(lib().nabwa_damage_fetch(self._h, _ptr(sub5), _ptr(sub3), _ptr(len_hist), _ptr(stats)))
+        return sub5, sub3, len_hist, stats
+
+    def clear(self):
+        _chk(lib().nabwa_damage_clear(self._h))
+
+    def times(self):
+        """device-event times of the last add in ms: upload, kernel, adding the call's table to the totals"""
+        ms = (C.c_float * 3)()
+        _chk(lib().nabwa_damage_times(self._h, ms))
+        return list(ms)
+
+    def close(self):
+        if self._h:
+            lib().nabwa_damage_destroy(self._h)
             self._h = None
 
     def __enter__(self):

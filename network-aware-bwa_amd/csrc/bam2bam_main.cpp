@@ -9,6 +9,7 @@
 // (-p; the worker side is nabwa_worker, worker_main.cpp) and resuming from .sai files (-0 -1 -2) -- each is refused, none is
 // silently ignored.  --only-aligned, --drop-aligned, --skip-duplicates, --broken-input and --debug-bam are the library's NABWA_BAM_* flags.
 // --sort (not the reference's): the records leave sorted by coordinate, runs sorted on the GPU or, NABWA_SORT=host, on host threads.
+// --damage FILE (not the reference's): the damage profile of the records as they leave, counted on the first GPU.
 // -t is accepted and ignored (NABWA_DEVICES=0,1,... names the GPUs: an index replica on each, batches dealt to them in turn, searched as
 // they come and passed in input order; default one GPU, NABWA_DEVICE or 0), --temp-dir likewise (the records wait in memory between the passes).
 #include <getopt.h>
@@ -168,6 +169,8 @@ struct Options {
 	bool sort = false;                                         /* --sort: coordinate order */
 	bool sort_host = false;                                    /* NABWA_SORT=host: the runs are sorted on host threads, not on the GPU */
 	long sort_run_mib = 1024;                                  /* NABWA_SORT_RUN_MIB: record bytes of a run */
+	const char *damage_file = 0;                               /* --damage FILE: the damage profile of the records goes there */
+	nabwa_damage_opt_t damage;                                 /* NABWA_DAMAGE_POS, NABWA_DAMAGE_MAPQ */
 };
 /* -1: go on; else the exit status, after the line that says why */
 static int parse_options(int argc, char **argv, Options &o)
@@ -180,7 +183,7 @@ static int parse_options(int argc, char **argv, Options &o)
 		{ "output", 1, 0, 'f' }, { "genome", 1, 0, 'g' }, { "only-aligned", 0, 0, 128 }, { "drop-aligned", 0, 0, 133 }, { "debug-bam", 0, 0, 129 },
 		{ "broken-input", 0, 0, 130 }, { "skip-duplicates", 0, 0, 131 }, { "temp-dir", 1, 0, 132 }, { "max-insert-size", 1, 0, 'a' },
 		{ "max-occurences", 1, 0, 'C' }, { "max-occurences-se", 1, 0, 'D' }, { "max-hits", 1, 0, 'h' }, { "max-discordant-hits", 1, 0, 'H' },
-		{ "chimeric-rate", 1, 0, 'c' }, { "disable-sw", 0, 0, 's' }, { "disable-isize-estimate", 0, 0, 'A' }, { "listen-port", 1, 0, 'p' }, { "sort", 0, 0, 134 }, { 0, 0, 0, 0 } };
+		{ "chimeric-rate", 1, 0, 'c' }, { "disable-sw", 0, 0, 's' }, { "disable-isize-estimate", 0, 0, 'A' }, { "listen-port", 1, 0, 'p' }, { "sort", 0, 0, 134 }, { "damage", 1, 0, 135 }, { 0, 0, 0, 0 } };
 	nabwa_gap_opt_t &go = o.go; nabwa_pe_opt_t &po = o.po;
 	nabwa_gap_init_opt(&go);
 	nabwa_pe_opt_default(&po);
@@ -207,6 +210,7 @@ static int parse_options(int argc, char **argv, Options &o)
 			case 'A': po.force_isize = 1; break;
 			case 132: o.temp_dir = optarg; break;
 			case 134: o.sort = true; break;
+			case 135: o.damage_file = optarg; break;
 			case 'p': case '0': case '1': case '2':
 				fprintf(stderr, "[nabwa_bam2bam] this option of bwa bam2bam is not provided (0MQ modes, .sai resume)\n");
 				return 1;
@@ -219,9 +223,12 @@ static int parse_options(int argc, char **argv, Options &o)
 	if (po.n_multi < 0 || po.n_multi > NABWA_MAX_MULTI || po.N_multi < 0 || po.N_multi > NABWA_MAX_MULTI) { fprintf(stderr, "[nabwa_bam2bam] -h / -H: 0..%d\n", NABWA_MAX_MULTI); return 1; }
 	if (go.s_mm < 1 || go.s_gapo < 1 || go.s_gape < 1) { fprintf(stderr, "[nabwa_bam2bam] -M / -O / -E must be at least 1\n"); return 1; }
 	if (optind + 1 > argc || !o.prefix) {
-		fprintf(stderr, "\nUsage:   nabwa_bam2bam -g PREFIX [options of bwa bam2bam] [--sort] [-f out.bam] <in.bam>\n\n"
+		fprintf(stderr, "\nUsage:   nabwa_bam2bam -g PREFIX [options of bwa bam2bam] [--sort] [--damage FILE] [-f out.bam] <in.bam>\n\n"
 						"         --sort   write the records sorted by coordinate (@HD SO:coordinate; ties keep the input order).\n"
-						"                  NABWA_SORT=gpu|host: who sorts a run (default gpu); NABWA_SORT_RUN_MIB: record bytes per run (default 1024)\n\n");
+						"                  NABWA_SORT=gpu|host: who sorts a run (default gpu); NABWA_SORT_RUN_MIB: record bytes per run (default 1024)\n"
+						"         --damage FILE   write the damage profile of the records to FILE: substitutions against the reference by distance from\n"
+						"                  the read's ends, read lengths.  NABWA_DAMAGE_POS: positions per end, 1..256 (default 25); NABWA_DAMAGE_MAPQ:\n"
+						"                  the lowest mapping quality counted (default 0)\n\n");
 		return 1;
 	}
 	o.input = argv[optind];
@@ -254,6 +261,19 @@ static int parse_options(int argc, char **argv, Options &o)
 			o.sort_run_mib = v;
 		}
 	}
+	/* --damage only: NABWA_DAMAGE_POS, the positions counted from either end, and NABWA_DAMAGE_MAPQ, the lowest mapping quality counted */
+	if (o.damage_file) {
+		nabwa_damage_default_opt(&o.damage);
+		const struct { const char *name; int32_t *v; long lo, hi; const char *what; } vars[] = {
+			{ "NABWA_DAMAGE_POS", &o.damage.n_pos, 1, NABWA_DAMAGE_MAX_POS, "1 .. 256 positions" }, { "NABWA_DAMAGE_MAPQ", &o.damage.min_mapq, 0, 255, "a mapping quality, 0 .. 255" } };
+		for (const auto &x : vars)
+			if (const char *k = getenv(x.name)) {
+				char *end = 0;
+				const long v = strtol(k, &end, 10);
+				if (end == k || *end || v < x.lo || v > x.hi) { fprintf(stderr, "[nabwa_bam2bam] %s=%s: %s\n", x.name, k, x.what); return 1; }
+				*x.v = (int32_t)v;
+			}
+	}
 	return -1;
 }
 
@@ -281,6 +301,7 @@ static void write_output_header(BgzfOut &out, nabwa_index_t *ix, const std::stri
  *
  *   read_batches -in_ch-> create_batches -made_ch[g]-> search_on(g) -found_ch[g]-> pass1_loop, pass2_* -done_ch-> emit -out_ch-> write_out
  *                                                                                      with --sort:  emit -out_ch-> sort_runs -sorted_ch-> write_out
+ *                                                                                      with --damage: emit -out_ch-> count_damage -counted_ch-> sort_runs or write_out
  *
  * read_batches inflates the input and cuts it into batches of records (mates stay together); create_batches parses them (host work only)
  * and deals them to the GPUs in turn; search_on(g), one thread per GPU, searches that GPU's batches as they come (no random numbers, no
@@ -292,9 +313,11 @@ static void write_output_header(BgzfOut &out, nabwa_index_t *ix, const std::stri
  * --sort puts one stage between emit and write_out: sort_runs collects records into runs of NABWA_SORT_RUN_MIB MiB, sorts each run by coordinate
  * (nabwa_bam_sort_run on the first GPU, or bam_sort_host under NABWA_SORT=host), keeps the sorted runs and their keys -- in memory, or with
  * --temp-dir in a second unlinked file there -- and at the end of the input hands the writer one run as it is or the merge of several, made
- * from the key arrays alone.  The writer still takes bytes from one thread in one order. */
+ * from the key arrays alone.  The writer still takes bytes from one thread in one order.
+ * --damage puts one stage right behind emit: count_damage hands every piece of records to nabwa_damage_add on the first GPU and passes the bytes
+ * on untouched; the tables add up in the handle, in any order, and main writes them at the end. */
 struct InBatch { std::vector<uint8_t> buf; std::vector<int64_t> off; };
-struct OutBytes { std::unique_ptr<uint8_t[]> p; size_t n = 0; std::vector<int64_t> off; };      /* no zero fill: the library writes every byte.  off: --sort, the records' offsets where emit has them */
+struct OutBytes { std::unique_ptr<uint8_t[]> p; size_t n = 0; std::vector<int64_t> off; };      /* no zero fill: the library writes every byte.  off: --sort and --damage, the records' offsets where emit has them */
 /* a sorted run of --sort: its records in key order (in memory, or n bytes from `at` in the run file), their offsets and their keys */
 struct SortedRun { std::unique_ptr<uint8_t[]> p; size_t n = 0; long at = 0; std::vector<int64_t> off; std::vector<uint64_t> keys; };
 struct Finished { nabwa_bam_batch_t *batch = 0; OutBytes bytes; };     /* what emit takes: a batch whose records it collects, or (no batch) records already made */
@@ -313,6 +336,10 @@ struct Pipeline {
 	std::vector<SortedRun> runs;
 	FILE *run_file = 0;                                       /* --temp-dir: the sorted runs wait there */
 	uint64_t n_sorted = 0; double t_sort = 0;
+	/* --damage */
+	Chan<OutBytes> counted_ch{2};
+	nabwa_damage_t *damage = 0;
+	double t_damage = 0;
 	/* the main thread's: the insert-size table, the random numbers (srand48(bns->seed), bam2bam.c:1745), what waits for pass 2 */
 	nabwa_isize_table_t *tab; uint64_t rng;
 	std::vector<nabwa_bam_batch_t*> waiting;
@@ -477,11 +504,12 @@ struct Pipeline {
 			if (nabwa_bam_batch_t *b = f.batch) {
 				int64_t nb = 0;
 				const double ta = now_s();
-				std::vector<int64_t> &oo = f.bytes.off;               /* --sort: the offsets too */
-				if (opt.sort) { int nr = 0, nl = 0; nabwa_bam_batch_counts(b, &nr, &nl); oo.assign((size_t)nr + 1, 0); }
+				std::vector<int64_t> &oo = f.bytes.off;               /* --sort, --damage: the offsets too */
+				const bool want_off = opt.sort || opt.damage_file;
+				if (want_off) { int nr = 0, nl = 0; nabwa_bam_batch_counts(b, &nr, &nl); oo.assign((size_t)nr + 1, 0); }
 				nabwa_bam_batch_output(b, 0, 0, 0, &nb);
 				f.bytes.p.reset(new uint8_t[(size_t)(nb ? nb : 1)]); f.bytes.n = (size_t)nb;
-				if (nabwa_bam_batch_output(b, f.bytes.p.get(), nb, opt.sort ? oo.data() : 0, &nb) != NABWA_OK) die("output", nabwa_last_error());
+				if (nabwa_bam_batch_output(b, f.bytes.p.get(), nb, want_off ? oo.data() : 0, &nb) != NABWA_OK) die("output", nabwa_last_error());
 				while (oo.size() > 1 && oo[oo.size() - 1] == oo[oo.size() - 2]) oo.pop_back();      /* --only-aligned: the records that are there */
 				const double tb = now_s();
 				nabwa_bam_batch_destroy(b);
@@ -492,6 +520,27 @@ struct Pipeline {
 			t_wait_out += now_s() - t0;
 		}
 		out_ch.close();
+	}
+	/* records that came ready-made from the temporary file: their offsets, from the block_size words */
+	static void walk_records(const OutBytes &o, std::vector<int64_t> &walked, const char *who)
+	{
+		walked.assign(1, 0);
+		for (size_t q = 0; q < o.n; ) { uint32_t bs; if (o.n - q < 4) die(who, "a record cut short"); memcpy(&bs, o.p.get() + q, 4); q += 4 + (size_t)bs; if (q > o.n) die(who, "a record cut short"); walked.push_back((int64_t)q); }
+	}
+	/* what emit made, for the stage behind the optional ones */
+	Chan<OutBytes> &emitted() { return opt.damage_file ? counted_ch : out_ch; }
+	/* --damage: every piece of records through nabwa_damage_add, then on as it is (with its offsets, which --sort takes as emit's) */
+	void count_damage()
+	{
+		OutBytes o;
+		while (out_ch.get(o)) {
+			const double t0 = now_s();
+			if (o.off.empty()) walk_records(o, o.off, "damage");
+			if (nabwa_damage_add(damage, (int64_t)o.off.size() - 1, o.p.get(), o.off.data()) != NABWA_OK) die("damage", nabwa_last_error());
+			t_damage += now_s() - t0;
+			counted_ch.put(std::move(o));
+		}
+		counted_ch.close();
 	}
 	/* --sort: one run, in[off[0] .. off[n]) -> sorted, kept */
 	void sort_run(const std::vector<uint8_t> &in, const std::vector<int64_t> &off)
@@ -535,12 +584,9 @@ struct Pipeline {
 		const size_t limit = (size_t)opt.sort_run_mib << 20, CHUNK = (size_t)64 << 20;
 		std::vector<uint8_t> cur; std::vector<int64_t> cur_off(1, 0), walked;
 		OutBytes o;
-		while (out_ch.get(o)) {
+		while (emitted().get(o)) {
 			const double t0 = now_s();
-			if (o.off.empty()) {                                  /* bytes that came ready-made from the temporary file: walk the block_size words */
-				walked.assign(1, 0);
-				for (size_t q = 0; q < o.n; ) { uint32_t bs; if (o.n - q < 4) die("sort", "a record cut short"); memcpy(&bs, o.p.get() + q, 4); q += 4 + (size_t)bs; if (q > o.n) die("sort", "a record cut short"); walked.push_back((int64_t)q); }
-			}
+			if (o.off.empty()) walk_records(o, walked, "sort");
 			const std::vector<int64_t> &off = o.off.empty() ? walked : o.off;
 			const size_t nrec = off.size() - 1;
 			for (size_t i = 0; i < nrec; ) {
@@ -589,11 +635,46 @@ struct Pipeline {
 	}
 	void write_out()
 	{
-		Chan<OutBytes> &from = opt.sort ? sorted_ch : out_ch;
+		Chan<OutBytes> &from = opt.sort ? sorted_ch : emitted();
 		OutBytes o;
 		while (from.get(o)) { const double t0 = now_s(); out.write(o.p.get(), o.n); o.p.reset(); t_write += now_s() - t0; }
 	}
 };
+
+/* --damage: the handle's tables as text into `path`, made to be diffed: the stats by name, a row per end and position (the row behind the
+ * last position: everything further in), the read lengths that occur.  Returns the summary line for stderr: the records counted and the two
+ * frequencies ancient DNA is known by -- C>T at the first 5' base and G>A at the first 3' base, each among the reference's C resp. G there */
+static std::string write_damage_profile(nabwa_damage_t *d, int n_pos, const char *path)
+{
+	static const char *const stat_names[NABWA_DAMAGE_N_STATS] = { "seen", "counted", "skipped_flags", "skipped_place", "skipped_mapq", "skipped_empty",
+																   "columns_counted", "columns_skipped_read", "columns_skipped_ref" };
+	std::vector<uint64_t> sub[2] = { std::vector<uint64_t>((size_t)(n_pos + 1) * 16), std::vector<uint64_t>((size_t)(n_pos + 1) * 16) }, len(NABWA_DAMAGE_LEN_BINS), stats(NABWA_DAMAGE_N_STATS);
+	if (nabwa_damage_fetch(d, sub[0].data(), sub[1].data(), len.data(), stats.data()) != NABWA_OK) die("damage", nabwa_last_error());
+	FILE *f = fopen(path, "w");
+	if (!f) die(path, "cannot create");
+	fprintf(f, "# nabwa damage profile v1\n");
+	for (int k = 0; k < NABWA_DAMAGE_N_STATS; ++k) fprintf(f, "# %s %llu\n", stat_names[k], (unsigned long long)stats[(size_t)k]);
+	fprintf(f, "end\tpos");
+	for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) fprintf(f, "\t%c>%c", "ACGT"[r], "ACGT"[q]);
+	fprintf(f, "\n");
+	for (int e = 0; e < 2; ++e)
+		for (int p = 0; p <= n_pos; ++p) {
+			if (p < n_pos) fprintf(f, "%s\t%d", e ? "3p" : "5p", p + 1); else fprintf(f, "%s\t>%d", e ? "3p" : "5p", n_pos);
+			for (int k = 0; k < 16; ++k) fprintf(f, "\t%llu", (unsigned long long)sub[e][(size_t)p * 16 + (size_t)k]);
+			fprintf(f, "\n");
+		}
+	for (int L = 0; L < NABWA_DAMAGE_LEN_BINS; ++L) if (len[(size_t)L]) fprintf(f, "len\t%d\t%llu\n", L, (unsigned long long)len[(size_t)L]);
+	if (fclose(f) != 0) die(path, "cannot write");
+	auto freq = [&](int e, int r, int q) {
+		uint64_t tot = 0;
+		for (int k = 0; k < 4; ++k) tot += sub[e][(size_t)(r * 4 + k)];
+		char b[32];
+		if (tot) snprintf(b, sizeof b, "%.4f", (double)sub[e][(size_t)(r * 4 + q)] / (double)tot); else snprintf(b, sizeof b, "nan");
+		return std::string(b);
+	};
+	return "[nabwa_bam2bam] damage profile of " + std::to_string((unsigned long long)stats[NABWA_DAMAGE_STAT_COUNTED]) + " records: 5' C>T at position 1 " + freq(0, 1, 3)
+		   + ", 3' G>A at position 1 " + freq(1, 2, 0) + "\n";
+}
 
 int main(int argc, char **argv)
 {
@@ -611,6 +692,8 @@ int main(int argc, char **argv)
 	/* --sort on the GPU: its handle now, so that a run without a usable device ends before anything is written */
 	nabwa_bam_sort_t *sorter = 0;
 	if (opt.sort && !opt.sort_host && nabwa_bam_sort_create(devices[0], &sorter) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] --sort on the GPU: %s\n", nabwa_last_error()); return 2; }
+	/* --damage counts on the first GPU, through a handle on that GPU's index (made below, once the index is there): no such device ends the run here */
+	if (opt.damage_file && nabwa_device_count() <= devices[0]) { fprintf(stderr, "[nabwa_bam2bam] --damage on the GPU: no HIP device %d\n", devices[0]); return 2; }
 	std::vector<nabwa_index_t*> ixs;
 	{
 		std::string err;
@@ -619,6 +702,9 @@ int main(int argc, char **argv)
 	int64_t genome_len = 0; uint32_t seed = 0;
 	nabwa_index_reference_info(ixs[0], &genome_len, &seed);
 	fprintf(stderr, "[nabwa_bam2bam] genome length is %ld\n", (long)genome_len);
+	/* --damage: its handle on the first GPU's index now, so that a run that cannot count ends before anything is written */
+	nabwa_damage_t *damage = 0;
+	if (opt.damage_file && nabwa_damage_create(ixs[0], &opt.damage, &damage) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] --damage on the GPU: %s\n", nabwa_last_error()); return 2; }
 
 	FILE *inf = strcmp(opt.input, "-") ? fopen(opt.input, "rb") : stdin;
 	if (!inf) die(opt.input, "cannot open");
@@ -641,7 +727,9 @@ int main(int argc, char **argv)
 	const double t_loop = now_s();
 	Pipeline P(opt, ixs, in, out, genome_len, seed);
 	P.sorter = sorter;
-	std::thread sort_thread;
+	P.damage = damage;
+	std::thread sort_thread, damage_thread;
+	if (damage) damage_thread = std::thread(&Pipeline::count_damage, &P);
 	if (opt.sort) sort_thread = std::thread(&Pipeline::sort_runs, &P);
 	std::thread reader(&Pipeline::read_batches, &P), creator(&Pipeline::create_batches, &P), finisher(&Pipeline::emit, &P), writer(&Pipeline::write_out, &P);
 	std::vector<std::thread> searchers;
@@ -655,12 +743,14 @@ int main(int argc, char **argv)
 	P.pass2_spilled();
 	P.done_ch.close();
 	finisher.join();
+	if (damage) damage_thread.join();
 	if (opt.sort) sort_thread.join();
 	writer.join();
 
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: start-up (device, index, headers) %.3f s, records %.3f s\n", t_loop - t_main, now_s() - t_loop);
 	if (timing) { double ts = 0; for (double x : P.t_search) ts += x; fprintf(stderr, "[nabwa_bam2bam] timing: search threads (%zu GPU%s) %.3f s busy\n", P.n_dev, P.n_dev > 1 ? "s" : "", ts); }
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: library calls: create %.3f s, pass 1 %.3f s, pass 2 %.3f s, output %.3f s, destroy %.3f s\n", P.t_call[0], P.t_call[1], P.t_call[2], P.t_call[3], P.t_call[4]);
+	if (timing && damage) fprintf(stderr, "[nabwa_bam2bam] timing: damage thread %.3f s busy (upload and count on the gpu)\n", P.t_damage);
 	if (timing && opt.sort) fprintf(stderr, "[nabwa_bam2bam] timing: sort thread %.3f s busy (%zu run(s) sorted on the %s, then handed on or merged)\n", P.t_sort, P.runs.size(), sorter ? "gpu" : "host");
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: reader thread %.3f s busy (%.3f s of it inflate, %s), passes 1 and 2 on this thread %.3f s (+ %.3f s waiting for input; the output thread waited %.3f s for the writer), writer thread %.3f s busy (deflate + write; %s)\n",
 						P.t_read, in.t_inflate, in.bgzf ? (bgzf_in ? "BGZF blocks on the GPU" : "BGZF blocks in parallel") : in.raw ? "not compressed" : "one gzip stream", P.t_lib, P.t_wait_in, P.t_wait_out, P.t_write,
@@ -672,10 +762,13 @@ int main(int argc, char **argv)
 	if (bgzf) nabwa_bgzf_destroy(bgzf);
 	if (bgzf_in) nabwa_bgzf_destroy(bgzf_in);
 	if (sorter) nabwa_bam_sort_destroy(sorter);
+	std::string damage_line;
+	if (damage) { damage_line = write_damage_profile(damage, opt.damage.n_pos, opt.damage_file); nabwa_damage_destroy(damage); }
 	nabwa_isize_table_destroy(P.tab);
 	tool_dedup_cache_summary(ixs);
 	for (nabwa_index_t *p : ixs) nabwa_index_destroy(p);
 	final_rename(opt.ofile, true);
 	if (opt.sort) fprintf(stderr, "[nabwa_bam2bam] sorted %llu records in %zu run(s) on the %s\n", (unsigned long long)P.n_sorted, P.runs.size(), opt.sort_host ? "host" : "gpu");
+	if (damage) fprintf(stderr, "%s", damage_line.c_str());
 	return 0;
 }

@@ -1,4 +1,4 @@
-// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, dedup_kernels.hip, dedup_cache_kernels.hip, bgzf_deflate.hip, bgzf_inflate.hip and finish_kernels.hip, declared once.
+// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, dedup_kernels.hip, dedup_cache_kernels.hip, bgzf_deflate.hip, bgzf_inflate.hip, finish_kernels.hip and damage_kernels.hip, declared once.
 // The defining files and every host unit that calls one include this header, so a parameter list that differs between the two sides
 // is a compile error (C linkage carries no types).  Host side only: the kernel headers (nabwa_dev.hpp, fm_search.hpp, fm_deep.hpp,
 // fm_deep_body.hpp) do not include it -- the CPU emulation of the tests compiles those without HIP.
@@ -89,4 +89,9 @@ void nabwa_launch_md_count(const struct FinRef *R, const struct FinRec *recs, in
 						   int32_t *nm, int32_t *len_out, hipStream_t s);
 void nabwa_launch_md_write(const struct FinRef *R, const struct FinRec *recs, int n, const uint8_t *reads0, const uint8_t *reads1, const uint16_t *cigar,
 						   const int64_t *md_off, char *md, hipStream_t s);
+/* damage_kernels.hip (damage_body.hpp): the records of *P counted into the call's table (zero before), *bad (0xffffffff before) = the lowest
+ * damaged record; n_blocks workgroups share the records whatever their number.  Then the call's table onto the totals */
+struct DmgParams;
+void nabwa_launch_damage(const struct DmgParams *P, int n_blocks, unsigned long long *call, unsigned int *bad, hipStream_t s);
+void nabwa_launch_damage_add(int words, const unsigned long long *call, unsigned long long *total, hipStream_t s);
 }

@@ -751,6 +751,64 @@ int nabwa_damage_clear(nabwa_damage_t *d);
 void nabwa_damage_destroy(nabwa_damage_t *d);
 int nabwa_damage_times(const nabwa_damage_t *d, float ms[3]);
 
+/* ---- the coordinate sort once more, with the permutation: perm_out (n_rec, may be NULL) receives for each output record the index it had
+ * in `in`.  The sort carries this index on the device anyway, so it is one more download.  nabwa_bam_sort_run and nabwa_bam_sort are these
+ * with NULL. */
+int nabwa_bam_sort_run_ex(nabwa_bam_sort_t *s, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out, uint32_t *perm_out);
+int nabwa_bam_sort_ex(int device, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out, uint32_t *perm_out);
+
+/* ---- duplicate marking of finished BAM records on the GPU (nabwa_markdup.hip, markdup_kernels.hip, markdup_body.hpp).
+ * Records and offsets are those of nabwa_bam_sort.  The records get ordinals 0, 1, ... in the order they are added to a handle, across
+ * calls; at most 0x7fffffff between create / clear.  A record falls into the first class that fits, each with its counter in stats[]:
+ *   skipped_flags  flag & exclude_flags: never marked, in no group
+ *   already        flag & 0x400: in no group, reported dup = 0 (the caller's flag stands)
+ *   unmapped       flag & 0x4, refID < 0, pos < 0 or n_cigar_op == 0: in no group (but see "half pair")
+ *   pair           records i and i + 1 of one call are mates when i has flags 0x1 and 0x40 (and not 0x80), i + 1 has 0x1 and 0x80 (and not
+ *                  0x40), their read names are equal (length and bytes) and neither is skipped_flags or already.  Both mates mapped: a
+ *                  pair (stats[pairs] counts it once).  Exactly one mapped, a half pair: the mapped mate is a fragment, the unmapped mate
+ *                  (counted in unmapped) takes whatever mark its mate gets.  MATES MUST COME IN ONE CALL, next to each other
+ *   fragment       every other mapped record; one with flag 0x1 that has no mate next to it also counts in orphans
+ * Ends.  With the CIGAR's M, D, N, = and X consuming the reference, `lead` the S and H lengths before the first such operation (all of them
+ * if there is none) and `trail` those after the last (0 if there is none): left = pos - lead, right = pos + (the reference consumed) - 1 +
+ * trail, in 64 bits.  The 5' end of a record is (refID, strand, c5) with c5 = left on the forward strand and right with flag 0x10; c3 is
+ * the other of the two.  Score: the sum of the base qualities >= min_qual, 0xff counting as 0; of a pair the sum over both mates; capped at
+ * 0xfffffffe.
+ * Groups.  Fragments are equal on (refID, strand, c5), with single_ends = NABWA_MARKDUP_ENDS_BOTH on (refID, strand, c5, c3) (collapsed or
+ * merged reads, whose two ends are both real).  Pairs are equal on their two ends, the lower end first.  With NABWA_MARKDUP_ENDS_5P every
+ * pair also stands in the fragment groups of its two ends as a shadow that outranks every fragment and is never itself marked: a fragment
+ * that starts where a pair's mate starts is a duplicate (the rule of Picard and samtools).  ENDS_BOTH makes no shadows.
+ * Winner.  Within a group the highest score wins, then the lowest ordinal; every other real member gets dup = 1, of a pair both mates.  The
+ * result depends on nothing else: not on how the records were split into calls (mates together) and not on the device.
+ * NABWA_EINVAL  a null argument; min_qual outside 0..255, single_ends outside 0..1; n_rec < 0 or above 0x7fffffff, or more than 0x7fffffff
+ *               records in the handle; offsets that do not increase; a record shorter than 36 bytes -- decided on the host from the
+ *               arguments alone, before the device is touched
+ * NABWA_ECAP    nabwa_markdup_resolve: cap is below the records added
+ * NABWA_EDATA   a block_size + 4 that is not the record's extent; 36 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq beyond the
+ *               record, whatever its class; a mapped record with l_seq > 0 whose CIGAR does not consume l_seq read bases; a mapped record
+ *               with left < -2^30 or right >= 2^31 + 2^30.  nabwa_last_error names the lowest such record, and the failed call adds nothing
+ * NABWA_ENODEV  no device;  NABWA_ENOMEM  the device cannot hold it: a call needs its bytes + 28 B per record, the handle keeps 1 B per
+ *               record and 24 B per tuple (a fragment is one tuple, a pair three, without shadows one), a resolve needs 25 B per tuple more
+ * n_rec == 0 and a resolve with nothing added are NABWA_OK.  There is no CPU path here.  No byte outside the call's records is read.
+ * nabwa_markdup_resolve: dup[ordinal] (0 or 1) and stats (NABWA_MARKDUP_N_STATS words, may be NULL) for everything added since create /
+ * clear; it may be called again after more adds.  dup_fragments and dup_pairs count marked tuples, dup_records the records with dup = 1.
+ * The handle keeps its stream, its arena and its scratch (they grow and stay) between calls, one call at a time.
+ * nabwa_markdup_times: device-event milliseconds -- of the last successful add: upload, signature and tuple kernels; of the last resolve:
+ * radix sorts, mark kernels, download. */
+#define NABWA_MARKDUP_ENDS_5P   0
+#define NABWA_MARKDUP_ENDS_BOTH 1
+enum { NABWA_MARKDUP_STAT_SEEN = 0, NABWA_MARKDUP_STAT_SKIPPED_FLAGS, NABWA_MARKDUP_STAT_ALREADY, NABWA_MARKDUP_STAT_UNMAPPED,
+	   NABWA_MARKDUP_STAT_FRAGMENTS, NABWA_MARKDUP_STAT_PAIRS, NABWA_MARKDUP_STAT_ORPHANS, NABWA_MARKDUP_STAT_DUP_FRAGMENTS,
+	   NABWA_MARKDUP_STAT_DUP_PAIRS, NABWA_MARKDUP_STAT_DUP_RECORDS, NABWA_MARKDUP_N_STATS };
+typedef struct { int32_t min_qual; int32_t single_ends; uint32_t exclude_flags; int32_t pad; } nabwa_markdup_opt_t;
+typedef struct nabwa_markdup nabwa_markdup_t;
+void nabwa_markdup_default_opt(nabwa_markdup_opt_t *o);    /* min_qual 15, NABWA_MARKDUP_ENDS_5P, exclude_flags 0xB00 (secondary, QC-fail, supplementary) */
+int nabwa_markdup_create(int device, const nabwa_markdup_opt_t *opt, nabwa_markdup_t **out);
+int nabwa_markdup_add(nabwa_markdup_t *m, int64_t n_rec, const uint8_t *in, const int64_t *in_off);
+int nabwa_markdup_resolve(nabwa_markdup_t *m, uint8_t *dup, int64_t cap, uint64_t *stats);
+int nabwa_markdup_clear(nabwa_markdup_t *m);
+void nabwa_markdup_destroy(nabwa_markdup_t *m);
+int nabwa_markdup_times(const nabwa_markdup_t *m, float ms[5]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -380,6 +380,19 @@ def lib():
         L.nabwa_bam_sort_run.argtypes = [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P]
         L.nabwa_bam_sort.argtypes = [C.c_int, C.c_int64, _P, _P, _P, C.c_int64, _P, _P]
         L.nabwa_bam_sort_times.argtypes = [_P, _P]
+    if hasattr(L, "nabwa_bam_sort_run_ex"):        # (likewise)
+        L.nabwa_bam_sort_run_ex.argtypes = [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P]
+        L.nabwa_bam_sort_ex.argtypes = [C.c_int, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P]
+    if hasattr(L, "nabwa_markdup_add"):            # (likewise)
+        L.nabwa_markdup_default_opt.argtypes = [_P]
+        L.nabwa_markdup_default_opt.restype = None
+        L.nabwa_markdup_create.argtypes = [C.c_int, _P, _P]
+        L.nabwa_markdup_add.argtypes = [_P, C.c_int64, _P, _P]
+        L.nabwa_markdup_resolve.argtypes = [_P, _P, C.c_int64, _P]
+        L.nabwa_markdup_clear.argtypes = [_P]
+        L.nabwa_markdup_destroy.argtypes = [_P]
+        L.nabwa_markdup_destroy.restype = None
+        L.nabwa_markdup_times.argtypes = [_P, _P]
     if hasattr(L, "nabwa_damage_add"):             # (likewise)
         L.nabwa_damage_default_opt.argtypes = [_P]
         L.nabwa_damage_default_opt.restype = None
@@ -594,7 +607,7 @@ def bam_record_offsets(records):
     return np.array(off, np.int64)
 
 
-def _bam_sort_call(f, first, records, off, cap):
+def _bam_sort_call(f, first, records, off, cap, perm=False):
     a = np.frombuffer(bytes(records), np.uint8)
     off = bam_record_offsets(a) if off is None else np.ascontiguousarray(off, np.int64)
     if off.ndim != 1 or off.size < 1:
@@ -604,20 +617,28 @@ def _bam_sort_call(f, first, records, off, cap):
     cap = max(total, 0) if cap is None else int(cap)
     out = np.empty(max(cap, 1), np.uint8)
     out_off, keys = np.zeros(n + 1, np.int64), np.zeros(n, np.uint64)
-    rc = f(first, n, _ptr(a) if a.size else None, _ptr(off), _ptr(out), cap, _ptr(out_off), _ptr(keys))
+    if perm:
+        order = np.zeros(n, np.uint32)
+        rc = f(first, n, _ptr(a) if a.size else None, _ptr(off), _ptr(out), cap, _ptr(out_off), _ptr(keys), _ptr(order))
+    else:
+        rc = f(first, n, _ptr(a) if a.size else None, _ptr(off), _ptr(out), cap, _ptr(out_off), _ptr(keys))
     if rc != OK:
         e = NabwaError(rc, lib().nabwa_last_error().decode())
         e.needed = total
         raise e
-    return out[:total].tobytes() if n else b"", out_off, keys
+    res = (out[:total].tobytes() if n else b"", out_off, keys)
+    return res + (order,) if perm else res
 
 
-def bam_sort(records, off=None, device=0, cap=None):
+def bam_sort(records, off=None, device=0, cap=None, perm=False):
     """finished BAM records (an uncompressed record stream: u32 block_size + block, back to back) -> (the records sorted by coordinate,
     their offsets, their keys), sorted and gathered on the GPU (nabwa_bam_sort).  The order is that of bam_sort_key, stable: records of
     equal key keep their order.  off: the records' offsets (n + 1), as nabwa_bam_batch_output gives them; None: walked from the block_size
     words on the host.  cap: the output capacity handed to the library (default: the records' total); a NabwaError of code ECAP
-    carries the size that would do in .needed, one of code EDATA names the first record whose block_size is not what its offsets say"""
+    carries the size that would do in .needed, one of code EDATA names the first record whose block_size is not what its offsets say.
+    perm=True appends the permutation as a fourth result: for each output record the index it had in the input (nabwa_bam_sort_ex)"""
+    if perm:
+        return _bam_sort_call(lib().nabwa_bam_sort_ex, int(device), records, off, cap, True)
     return _bam_sort_call(lib().nabwa_bam_sort, int(device), records, off, cap)
 
 
@@ -628,8 +649,12 @@ class BamSort:
         self._h = _P()
         _chk(lib().nabwa_bam_sort_create(int(device), C.byref(self._h)))
 
-    def sort(self, records, off=None, cap=None):
+    def sort(self, records, off=None, cap=None, perm=False):
+        if perm:
+            return _bam_sort_call(lib().nabwa_bam_sort_run_ex, self._h, records, off, cap, True)
         return _bam_sort_call(lib().nabwa_bam_sort_run, self._h, records, off, cap)
+
+    run = sort                                     # (nabwa_bam_sort_run)
 
     def times(self):
         """device-event times of the last sort in ms: upload, key kernel, radix sort, sizes + scan, gather kernel, download"""
@@ -719,6 +744,89 @@ class Damage:
             self.close()
         except Exception:
             pass
+
+
+class MarkDupOpt(C.Structure):
+    """nabwa_markdup_opt_t"""
+    _fields_ = [("min_qual", C.c_int32), ("single_ends", C.c_int32), ("exclude_flags", C.c_uint32), ("pad", C.c_int32)]
+
+
+MARKDUP_ENDS = {"5p": 0, "both": 1}                # NABWA_MARKDUP_ENDS_5P, _BOTH
+markdup_stat_names = ("seen", "skipped_flags", "already", "unmapped", "fragments", "pairs", "orphans", "dup_fragments", "dup_pairs",
+                      "dup_records")               # the slots of stats[], NABWA_MARKDUP_STAT_*
+
+
+def _records_and_offsets(records, off):
+    a = np.frombuffer(bytes(records), np.uint8) if not isinstance(records, np.ndarray) else np.ascontiguousarray(records, np.uint8)
+    off = bam_record_offsets(a) if off is None else np.ascontiguousarray(off, np.int64)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("off: n + 1 offsets")
+    return a, off
+
+
+class MarkDup:
+    """duplicate marking of finished BAM records on the GPU (nabwa_markdup_*): records that share their unclipped 5' end and strand (pairs:
+    both ends) are one group, its best-scoring member stays and the others are marked; include/nabwa.h has the rules.  Mates must lie
+    next to each other within one add."""
+
+    def __init__(self, device=0, min_qual=15, single_ends="5p", exclude_flags=0xB00):
+        if single_ends not in MARKDUP_ENDS:
+            raise ValueError('single_ends: "5p" or "both"')
+        self._h = _P()
+        self.n = 0                                 # records added since create / clear
+        o = MarkDupOpt(int(min_qual), MARKDUP_ENDS[single_ends], int(exclude_flags), 0)
+        _chk(lib().nabwa_markdup_create(int(device), C.byref(o), C.byref(self._h)))
+
+    def add(self, records, off=None):
+        """takes the records of an uncompressed BAM record stream; off: their offsets (n + 1), None: walked from the block_size words on
+        the host.  A NabwaError of code EDATA names the first damaged record, and that call has added nothing"""
+        a, off = _records_and_offsets(records, off)
+        _chk(lib().nabwa_markdup_add(self._h, off.size - 1, _ptr(a) if a.size else None, _ptr(off)))
+        self.n += off.size - 1
+
+    def resolve(self):
+        """-> (dup, stats): dup[i] = 1 where the i-th record added is a duplicate (uint8), stats by markdup_stat_names (uint64)"""
+        dup, stats = np.zeros(self.n, np.uint8), np.zeros(len(markdup_stat_names), np.uint64)
+        _chk(lib().nabwa_markdup_resolve(self._h, _ptr(dup) if self.n else None, self.n, _ptr(stats)))
+        return dup, stats
+
+    def clear(self):
+        _chk(lib().nabwa_markdup_clear(self._h))
+        self.n = 0
+
+    def times(self):
+        """device-event times in ms: of the last add upload and signature kernels, of the last resolve sorts, mark kernels and download"""
+        ms = (C.c_float * 5)()
+        _chk(lib().nabwa_markdup_times(self._h, ms))
+        return list(ms)
+
+    def close(self):
+        if self._h:
+            lib().nabwa_markdup_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def markdup(records, off=None, device=0, **opts):
+    """finished BAM records -> (the same bytes with flag 0x400 set on the duplicates, dup, stats), marked on the GPU (MarkDup used once)"""
+    a, off = _records_and_offsets(records, off)
+    with MarkDup(device, **opts) as m:
+        m.add(a, off)
+        dup, stats = m.resolve()
+    out = a.copy()
+    out[off[:-1][dup != 0] + 19] |= 0x04           # flag: bytes 18..19 of a record; 0x400 is bit 2 of the upper one
+    return out.tobytes(), dup, stats
 
 
 class Index:

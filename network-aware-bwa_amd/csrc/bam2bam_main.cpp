@@ -10,6 +10,7 @@
 // silently ignored.  --only-aligned, --drop-aligned, --skip-duplicates, --broken-input and --debug-bam are the library's NABWA_BAM_* flags.
 // --sort (not the reference's): the records leave sorted by coordinate, runs sorted on the GPU or, NABWA_SORT=host, on host threads.
 // --damage FILE (not the reference's): the damage profile of the records as they leave, counted on the first GPU.
+// --mark-duplicates, --remove-duplicates (not the reference's; with --sort): duplicates found on the first GPU, flagged 0x400 or dropped.
 // -t is accepted and ignored (NABWA_DEVICES=0,1,... names the GPUs: an index replica on each, batches dealt to them in turn, searched as
 // they come and passed in input order; default one GPU, NABWA_DEVICE or 0), --temp-dir likewise (the records wait in memory between the passes).
 #include <getopt.h>
@@ -171,6 +172,9 @@ struct Options {
 	long sort_run_mib = 1024;                                  /* NABWA_SORT_RUN_MIB: record bytes of a run */
 	const char *damage_file = 0;                               /* --damage FILE: the damage profile of the records goes there */
 	nabwa_damage_opt_t damage;                                 /* NABWA_DAMAGE_POS, NABWA_DAMAGE_MAPQ */
+	bool mark_dups = false, remove_dups = false;               /* --mark-duplicates, --remove-duplicates */
+	nabwa_markdup_opt_t markdup;                               /* NABWA_MARKDUP_ENDS, NABWA_MARKDUP_QUAL */
+	bool dups() const { return mark_dups || remove_dups; }
 };
 /* -1: go on; else the exit status, after the line that says why */
 static int parse_options(int argc, char **argv, Options &o)
@@ -183,7 +187,8 @@ static int parse_options(int argc, char **argv, Options &o)
 		{ "output", 1, 0, 'f' }, { "genome", 1, 0, 'g' }, { "only-aligned", 0, 0, 128 }, { "drop-aligned", 0, 0, 133 }, { "debug-bam", 0, 0, 129 },
 		{ "broken-input", 0, 0, 130 }, { "skip-duplicates", 0, 0, 131 }, { "temp-dir", 1, 0, 132 }, { "max-insert-size", 1, 0, 'a' },
 		{ "max-occurences", 1, 0, 'C' }, { "max-occurences-se", 1, 0, 'D' }, { "max-hits", 1, 0, 'h' }, { "max-discordant-hits", 1, 0, 'H' },
-		{ "chimeric-rate", 1, 0, 'c' }, { "disable-sw", 0, 0, 's' }, { "disable-isize-estimate", 0, 0, 'A' }, { "listen-port", 1, 0, 'p' }, { "sort", 0, 0, 134 }, { "damage", 1, 0, 135 }, { 0, 0, 0, 0 } };
+		{ "chimeric-rate", 1, 0, 'c' }, { "disable-sw", 0, 0, 's' }, { "disable-isize-estimate", 0, 0, 'A' }, { "listen-port", 1, 0, 'p' }, { "sort", 0, 0, 134 }, { "damage", 1, 0, 135 },
+		{ "mark-duplicates", 0, 0, 136 }, { "remove-duplicates", 0, 0, 137 }, { 0, 0, 0, 0 } };
 	nabwa_gap_opt_t &go = o.go; nabwa_pe_opt_t &po = o.po;
 	nabwa_gap_init_opt(&go);
 	nabwa_pe_opt_default(&po);
@@ -211,6 +216,8 @@ static int parse_options(int argc, char **argv, Options &o)
 			case 132: o.temp_dir = optarg; break;
 			case 134: o.sort = true; break;
 			case 135: o.damage_file = optarg; break;
+			case 136: o.mark_dups = true; break;
+			case 137: o.remove_dups = true; break;
 			case 'p': case '0': case '1': case '2':
 				fprintf(stderr, "[nabwa_bam2bam] this option of bwa bam2bam is not provided (0MQ modes, .sai resume)\n");
 				return 1;
@@ -223,12 +230,18 @@ static int parse_options(int argc, char **argv, Options &o)
 	if (po.n_multi < 0 || po.n_multi > NABWA_MAX_MULTI || po.N_multi < 0 || po.N_multi > NABWA_MAX_MULTI) { fprintf(stderr, "[nabwa_bam2bam] -h / -H: 0..%d\n", NABWA_MAX_MULTI); return 1; }
 	if (go.s_mm < 1 || go.s_gapo < 1 || go.s_gape < 1) { fprintf(stderr, "[nabwa_bam2bam] -M / -O / -E must be at least 1\n"); return 1; }
 	if (optind + 1 > argc || !o.prefix) {
-		fprintf(stderr, "\nUsage:   nabwa_bam2bam -g PREFIX [options of bwa bam2bam] [--sort] [--damage FILE] [-f out.bam] <in.bam>\n\n"
+		fprintf(stderr, "\nUsage:   nabwa_bam2bam -g PREFIX [options of bwa bam2bam] [--sort [--mark-duplicates | --remove-duplicates]] [--damage FILE] [-f out.bam] <in.bam>\n\n"
 						"         --sort   write the records sorted by coordinate (@HD SO:coordinate; ties keep the input order).\n"
 						"                  NABWA_SORT=gpu|host: who sorts a run (default gpu); NABWA_SORT_RUN_MIB: record bytes per run (default 1024)\n"
 						"         --damage FILE   write the damage profile of the records to FILE: substitutions against the reference by distance from\n"
 						"                  the read's ends, read lengths.  NABWA_DAMAGE_POS: positions per end, 1..256 (default 25); NABWA_DAMAGE_MAPQ:\n"
-						"                  the lowest mapping quality counted (default 0)\n\n");
+						"                  the lowest mapping quality counted (default 0)\n"
+						"         --mark-duplicates   with --sort: set flag 0x400 on every record but the best of those that share their unclipped 5' end and\n"
+						"                  strand (pairs: both ends); the best has the highest sum of base qualities.  Marked on the gpu; there is no host\n"
+						"                  path, also under NABWA_SORT=host.  With --damage the profile then leaves the duplicates out\n"
+						"         --remove-duplicates   the same, but the duplicates are dropped\n"
+						"                  NABWA_MARKDUP_ENDS=5p|both: single reads are equal on their 5' end (default) or on both ends (merged reads);\n"
+						"                  NABWA_MARKDUP_QUAL: the lowest base quality that counts, 0..93 (default 15)\n\n");
 		return 1;
 	}
 	o.input = argv[optind];
@@ -259,6 +272,24 @@ static int parse_options(int argc, char **argv, Options &o)
 			const long v = strtol(k, &end, 10);
 			if (end == k || *end || v < 1 || v > (1L << 20)) { fprintf(stderr, "[nabwa_bam2bam] NABWA_SORT_RUN_MIB=%s: a positive number of MiB\n", k); return 1; }
 			o.sort_run_mib = v;
+		}
+	}
+	/* --mark-duplicates, --remove-duplicates: one of them, with --sort; NABWA_MARKDUP_ENDS, which ends make single reads equal, and
+	 * NABWA_MARKDUP_QUAL, the lowest base quality that counts */
+	if (o.mark_dups && o.remove_dups) { fprintf(stderr, "[nabwa_bam2bam] --mark-duplicates and --remove-duplicates: one of the two\n"); return 1; }
+	if (o.dups() && !o.sort) { fprintf(stderr, "[nabwa_bam2bam] %s needs --sort: the duplicates are known once the whole input is in\n", o.mark_dups ? "--mark-duplicates" : "--remove-duplicates"); return 1; }
+	if (o.dups()) {
+		nabwa_markdup_default_opt(&o.markdup);
+		if (const char *k = getenv("NABWA_MARKDUP_ENDS")) {
+			if (!strcmp(k, "5p")) o.markdup.single_ends = NABWA_MARKDUP_ENDS_5P;
+			else if (!strcmp(k, "both")) o.markdup.single_ends = NABWA_MARKDUP_ENDS_BOTH;
+			else { fprintf(stderr, "[nabwa_bam2bam] NABWA_MARKDUP_ENDS=%s: 5p or both\n", k); return 1; }
+		}
+		if (const char *k = getenv("NABWA_MARKDUP_QUAL")) {
+			char *end = 0;
+			const long v = strtol(k, &end, 10);
+			if (end == k || *end || v < 0 || v > 93) { fprintf(stderr, "[nabwa_bam2bam] NABWA_MARKDUP_QUAL=%s: a base quality, 0 .. 93\n", k); return 1; }
+			o.markdup.min_qual = (int32_t)v;
 		}
 	}
 	/* --damage only: NABWA_DAMAGE_POS, the positions counted from either end, and NABWA_DAMAGE_MAPQ, the lowest mapping quality counted */
@@ -302,6 +333,8 @@ static void write_output_header(BgzfOut &out, nabwa_index_t *ix, const std::stri
  *   read_batches -in_ch-> create_batches -made_ch[g]-> search_on(g) -found_ch[g]-> pass1_loop, pass2_* -done_ch-> emit -out_ch-> write_out
  *                                                                                      with --sort:  emit -out_ch-> sort_runs -sorted_ch-> write_out
  *                                                                                      with --damage: emit -out_ch-> count_damage -counted_ch-> sort_runs or write_out
+ *                                                             with --mark-duplicates:  emit -out_ch-> mark_duplicates -marked_ch-> sort_runs -sorted_ch-> write_out
+ *                                                                     and --damage:    ... sort_runs -sorted_ch-> count_damage -counted_ch-> write_out
  *
  * read_batches inflates the input and cuts it into batches of records (mates stay together); create_batches parses them (host work only)
  * and deals them to the GPUs in turn; search_on(g), one thread per GPU, searches that GPU's batches as they come (no random numbers, no
@@ -315,11 +348,16 @@ static void write_output_header(BgzfOut &out, nabwa_index_t *ix, const std::stri
  * --temp-dir in a second unlinked file there -- and at the end of the input hands the writer one run as it is or the merge of several, made
  * from the key arrays alone.  The writer still takes bytes from one thread in one order.
  * --damage puts one stage right behind emit: count_damage hands every piece of records to nabwa_damage_add on the first GPU and passes the bytes
- * on untouched; the tables add up in the handle, in any order, and main writes them at the end. */
+ * on untouched; the tables add up in the handle, in any order, and main writes them at the end.
+ * --mark-duplicates / --remove-duplicates put one stage in front of sort_runs: mark_duplicates hands every piece to nabwa_markdup_add on the
+ * first GPU and passes it on untouched; a piece is a whole batch, and read_batches keeps mates in one batch, so mates reach the library next
+ * to each other.  The records' ordinals are their places in the stream sort_runs takes; each run keeps them beside its keys (run base + the
+ * sort's permutation).  When the input ends the stage resolves once, and sort_runs, as it hands over or merges, sets 0x400 on a duplicate
+ * or leaves it out.  --damage then counts behind the sort, on what leaves. */
 struct InBatch { std::vector<uint8_t> buf; std::vector<int64_t> off; };
 struct OutBytes { std::unique_ptr<uint8_t[]> p; size_t n = 0; std::vector<int64_t> off; };      /* no zero fill: the library writes every byte.  off: --sort and --damage, the records' offsets where emit has them */
 /* a sorted run of --sort: its records in key order (in memory, or n bytes from `at` in the run file), their offsets and their keys */
-struct SortedRun { std::unique_ptr<uint8_t[]> p; size_t n = 0; long at = 0; std::vector<int64_t> off; std::vector<uint64_t> keys; };
+struct SortedRun { std::unique_ptr<uint8_t[]> p; size_t n = 0; long at = 0; std::vector<int64_t> off; std::vector<uint64_t> keys; std::vector<uint64_t> ords; };      /* ords: --mark-duplicates, the records' ordinals */
 struct Finished { nabwa_bam_batch_t *batch = 0; OutBytes bytes; };     /* what emit takes: a batch whose records it collects, or (no batch) records already made */
 typedef Chan<nabwa_bam_batch_t*> BatchChan;
 
@@ -340,6 +378,13 @@ struct Pipeline {
 	Chan<OutBytes> counted_ch{2};
 	nabwa_damage_t *damage = 0;
 	double t_damage = 0;
+	/* --mark-duplicates, --remove-duplicates */
+	Chan<OutBytes> marked_ch{2};
+	nabwa_markdup_t *markdup = 0;
+	std::vector<uint8_t> dup;                                 /* by ordinal, once mark_duplicates has closed marked_ch */
+	uint64_t dup_stats[NABWA_MARKDUP_N_STATS] = {};
+	uint64_t n_run_base = 0, n_marked_in = 0;                 /* records in the runs sorted so far; records the marker has taken */
+	double t_markdup = 0;
 	/* the main thread's: the insert-size table, the random numbers (srand48(bns->seed), bam2bam.c:1745), what waits for pass 2 */
 	nabwa_isize_table_t *tab; uint64_t rng;
 	std::vector<nabwa_bam_batch_t*> waiting;
@@ -528,12 +573,31 @@ struct Pipeline {
 		for (size_t q = 0; q < o.n; ) { uint32_t bs; if (o.n - q < 4) die(who, "a record cut short"); memcpy(&bs, o.p.get() + q, 4); q += 4 + (size_t)bs; if (q > o.n) die(who, "a record cut short"); walked.push_back((int64_t)q); }
 	}
 	/* what emit made, for the stage behind the optional ones */
-	Chan<OutBytes> &emitted() { return opt.damage_file ? counted_ch : out_ch; }
+	Chan<OutBytes> &emitted() { return opt.dups() ? marked_ch : opt.damage_file ? counted_ch : out_ch; }
+	/* --mark-duplicates: every piece of records through nabwa_markdup_add, then on as it is; the marks once the input has ended */
+	void mark_duplicates()
+	{
+		OutBytes o;
+		while (out_ch.get(o)) {
+			const double t0 = now_s();
+			if (o.off.empty()) walk_records(o, o.off, "duplicates");
+			if (nabwa_markdup_add(markdup, (int64_t)o.off.size() - 1, o.p.get(), o.off.data()) != NABWA_OK) die("duplicates", nabwa_last_error());
+			n_marked_in += (uint64_t)o.off.size() - 1;
+			t_markdup += now_s() - t0;
+			marked_ch.put(std::move(o));
+		}
+		const double t0 = now_s();
+		dup.assign((size_t)(n_marked_in ? n_marked_in : 1), 0);
+		if (nabwa_markdup_resolve(markdup, dup.data(), (int64_t)n_marked_in, dup_stats) != NABWA_OK) die("duplicates", nabwa_last_error());
+		t_markdup += now_s() - t0;
+		marked_ch.close();
+	}
 	/* --damage: every piece of records through nabwa_damage_add, then on as it is (with its offsets, which --sort takes as emit's) */
 	void count_damage()
 	{
 		OutBytes o;
-		while (out_ch.get(o)) {
+		Chan<OutBytes> &from = opt.dups() ? sorted_ch : out_ch;      /* behind the marker: the duplicates are flagged or gone */
+		while (from.get(o)) {
 			const double t0 = now_s();
 			if (o.off.empty()) walk_records(o, o.off, "damage");
 			if (nabwa_damage_add(damage, (int64_t)o.off.size() - 1, o.p.get(), o.off.data()) != NABWA_OK) die("damage", nabwa_last_error());
@@ -549,12 +613,16 @@ struct Pipeline {
 		if (n <= 0) return;
 		SortedRun r;
 		r.n = in.size(); r.p.reset(new uint8_t[r.n]); r.off.resize((size_t)n + 1); r.keys.resize((size_t)n);
+		std::vector<uint32_t> perm(opt.dups() ? (size_t)n : 0);
+		uint32_t *perm_out = opt.dups() ? perm.data() : 0;
 		if (sorter) {
-			if (nabwa_bam_sort_run(sorter, n, in.data(), off.data(), r.p.get(), (int64_t)r.n, r.off.data(), r.keys.data()) != NABWA_OK) die("sort", nabwa_last_error());
+			if (nabwa_bam_sort_run_ex(sorter, n, in.data(), off.data(), r.p.get(), (int64_t)r.n, r.off.data(), r.keys.data(), perm_out) != NABWA_OK) die("sort", nabwa_last_error());
 		} else {
-			const int64_t bad = bam_sort_host(io_threads(), n, in.data(), off.data(), r.p.get(), r.off.data(), r.keys.data());
+			const int64_t bad = bam_sort_host(io_threads(), n, in.data(), off.data(), r.p.get(), r.off.data(), r.keys.data(), perm_out);
 			if (bad >= 0) die("sort", ("record " + std::to_string(bad) + " of a run: its block_size is not what its offsets say").c_str());
 		}
+		if (opt.dups()) { r.ords.resize((size_t)n); for (int64_t i = 0; i < n; ++i) r.ords[(size_t)i] = n_run_base + perm[(size_t)i]; }
+		n_run_base += (uint64_t)n;
 		if (run_file) {
 			r.at = ftell(run_file);
 			if (fwrite(r.p.get(), 1, r.n, run_file) != r.n) die("temporary file", "cannot write");
@@ -610,8 +678,22 @@ struct Pipeline {
 		if (run_file && fflush(run_file) != 0) die("temporary file", "cannot write");
 		double t_blocked = 0;
 		auto hand_over = [&](OutBytes &&x) { const double tb = now_s(); sorted_ch.put(std::move(x)); t_blocked += now_s() - tb; };
-		if (runs.size() == 1 && runs[0].p) {                      /* one run: as it is */
+		auto is_dup = [&](size_t r, size_t i) { return opt.dups() && dup[(size_t)runs[r].ords[i]] != 0; };
+		if (runs.size() == 1 && runs[0].p) {                      /* one run: as it is, but for the duplicates -- flagged where they lie, or the rest moved up over them */
 			OutBytes x; x.p = std::move(runs[0].p); x.n = runs[0].n;
+			if (opt.dups()) {
+				const SortedRun &R = runs[0];
+				size_t w = 0;
+				for (size_t i = 0; i + 1 < R.off.size(); ++i) {
+					const size_t at = (size_t)R.off[i], n = (size_t)(R.off[i + 1] - R.off[i]);
+					const bool d = is_dup(0, i);
+					if (d && opt.remove_dups) continue;
+					if (d) x.p[at + 19] |= 0x04;                      /* flag 0x400: bytes 18 .. 19 of the record */
+					if (w != at) memmove(x.p.get() + w, x.p.get() + at, n);
+					w += n;
+				}
+				x.n = w;
+			}
 			hand_over(std::move(x));
 		} else if (!runs.empty()) {                               /* several: merged by their keys alone, ties to the earlier run (one run in the file: read back in order) */
 			std::vector<const std::vector<uint64_t>*> keys;
@@ -620,11 +702,14 @@ struct Pipeline {
 			OutBytes x; size_t x_cap = 0;
 			bam_sort_merge(keys, [&](size_t r, size_t i) {
 				const int64_t at = runs[r].off[i], n = runs[r].off[i + 1] - at;
+				const bool d = is_dup(r, i);
+				if (d && opt.remove_dups) return;
 				if (x.n + (size_t)n > x_cap) {
 					if (x.n) hand_over(std::move(x));
 					x = OutBytes(); x_cap = (size_t)n > CHUNK ? (size_t)n : CHUNK; x.p.reset(new uint8_t[x_cap]);
 				}
 				memcpy(x.p.get() + x.n, run_bytes(r, at, n, win), (size_t)n);
+				if (d) x.p[x.n + 19] |= 0x04;
 				x.n += (size_t)n;
 			});
 			if (x.n) hand_over(std::move(x));
@@ -635,7 +720,7 @@ struct Pipeline {
 	}
 	void write_out()
 	{
-		Chan<OutBytes> &from = opt.sort ? sorted_ch : emitted();
+		Chan<OutBytes> &from = opt.dups() && opt.damage_file ? counted_ch : opt.sort ? sorted_ch : emitted();
 		OutBytes o;
 		while (from.get(o)) { const double t0 = now_s(); out.write(o.p.get(), o.n); o.p.reset(); t_write += now_s() - t0; }
 	}
@@ -692,6 +777,9 @@ int main(int argc, char **argv)
 	/* --sort on the GPU: its handle now, so that a run without a usable device ends before anything is written */
 	nabwa_bam_sort_t *sorter = 0;
 	if (opt.sort && !opt.sort_host && nabwa_bam_sort_create(devices[0], &sorter) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] --sort on the GPU: %s\n", nabwa_last_error()); return 2; }
+	/* --mark-duplicates, --remove-duplicates: the handle on the first GPU now, for the same reason; there is no host path, whatever NABWA_SORT says */
+	nabwa_markdup_t *markdup = 0;
+	if (opt.dups() && nabwa_markdup_create(devices[0], &opt.markdup, &markdup) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] %s on the GPU: %s\n", opt.mark_dups ? "--mark-duplicates" : "--remove-duplicates", nabwa_last_error()); return 2; }
 	/* --damage counts on the first GPU, through a handle on that GPU's index (made below, once the index is there): no such device ends the run here */
 	if (opt.damage_file && nabwa_device_count() <= devices[0]) { fprintf(stderr, "[nabwa_bam2bam] --damage on the GPU: no HIP device %d\n", devices[0]); return 2; }
 	std::vector<nabwa_index_t*> ixs;
@@ -728,7 +816,9 @@ int main(int argc, char **argv)
 	Pipeline P(opt, ixs, in, out, genome_len, seed);
 	P.sorter = sorter;
 	P.damage = damage;
-	std::thread sort_thread, damage_thread;
+	P.markdup = markdup;
+	std::thread sort_thread, damage_thread, markdup_thread;
+	if (markdup) markdup_thread = std::thread(&Pipeline::mark_duplicates, &P);
 	if (damage) damage_thread = std::thread(&Pipeline::count_damage, &P);
 	if (opt.sort) sort_thread = std::thread(&Pipeline::sort_runs, &P);
 	std::thread reader(&Pipeline::read_batches, &P), creator(&Pipeline::create_batches, &P), finisher(&Pipeline::emit, &P), writer(&Pipeline::write_out, &P);
@@ -743,14 +833,17 @@ int main(int argc, char **argv)
 	P.pass2_spilled();
 	P.done_ch.close();
 	finisher.join();
-	if (damage) damage_thread.join();
+	if (markdup) markdup_thread.join();
+	if (damage && !markdup) damage_thread.join();
 	if (opt.sort) sort_thread.join();
+	if (damage && markdup) damage_thread.join();
 	writer.join();
 
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: start-up (device, index, headers) %.3f s, records %.3f s\n", t_loop - t_main, now_s() - t_loop);
 	if (timing) { double ts = 0; for (double x : P.t_search) ts += x; fprintf(stderr, "[nabwa_bam2bam] timing: search threads (%zu GPU%s) %.3f s busy\n", P.n_dev, P.n_dev > 1 ? "s" : "", ts); }
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: library calls: create %.3f s, pass 1 %.3f s, pass 2 %.3f s, output %.3f s, destroy %.3f s\n", P.t_call[0], P.t_call[1], P.t_call[2], P.t_call[3], P.t_call[4]);
 	if (timing && damage) fprintf(stderr, "[nabwa_bam2bam] timing: damage thread %.3f s busy (upload and count on the gpu)\n", P.t_damage);
+	if (timing && markdup) fprintf(stderr, "[nabwa_bam2bam] timing: duplicates thread %.3f s busy (upload, signatures and the resolve on the gpu)\n", P.t_markdup);
 	if (timing && opt.sort) fprintf(stderr, "[nabwa_bam2bam] timing: sort thread %.3f s busy (%zu run(s) sorted on the %s, then handed on or merged)\n", P.t_sort, P.runs.size(), sorter ? "gpu" : "host");
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: reader thread %.3f s busy (%.3f s of it inflate, %s), passes 1 and 2 on this thread %.3f s (+ %.3f s waiting for input; the output thread waited %.3f s for the writer), writer thread %.3f s busy (deflate + write; %s)\n",
 						P.t_read, in.t_inflate, in.bgzf ? (bgzf_in ? "BGZF blocks on the GPU" : "BGZF blocks in parallel") : in.raw ? "not compressed" : "one gzip stream", P.t_lib, P.t_wait_in, P.t_wait_out, P.t_write,
@@ -762,6 +855,7 @@ int main(int argc, char **argv)
 	if (bgzf) nabwa_bgzf_destroy(bgzf);
 	if (bgzf_in) nabwa_bgzf_destroy(bgzf_in);
 	if (sorter) nabwa_bam_sort_destroy(sorter);
+	if (markdup) nabwa_markdup_destroy(markdup);
 	std::string damage_line;
 	if (damage) { damage_line = write_damage_profile(damage, opt.damage.n_pos, opt.damage_file); nabwa_damage_destroy(damage); }
 	nabwa_isize_table_destroy(P.tab);
@@ -770,5 +864,8 @@ int main(int argc, char **argv)
 	final_rename(opt.ofile, true);
 	if (opt.sort) fprintf(stderr, "[nabwa_bam2bam] sorted %llu records in %zu run(s) on the %s\n", (unsigned long long)P.n_sorted, P.runs.size(), opt.sort_host ? "host" : "gpu");
 	if (damage) fprintf(stderr, "%s", damage_line.c_str());
+	if (opt.dups()) fprintf(stderr, "[nabwa_bam2bam] %s %llu of %llu records as duplicates (%llu pairs, %llu single reads) on the gpu\n", opt.remove_dups ? "removed" : "marked",
+							(unsigned long long)P.dup_stats[NABWA_MARKDUP_STAT_DUP_RECORDS], (unsigned long long)P.dup_stats[NABWA_MARKDUP_STAT_SEEN],
+							(unsigned long long)P.dup_stats[NABWA_MARKDUP_STAT_DUP_PAIRS], (unsigned long long)P.dup_stats[NABWA_MARKDUP_STAT_DUP_FRAGMENTS]);
 	return 0;
 }

@@ -149,7 +149,7 @@ static int sort_reserve(nabwa_bam_sort_t *s, int64_t total, int64_t n, size_t tm
 	return NABWA_OK;
 }
 
-static int sort_run_checked(nabwa_bam_sort_t *s, int64_t n_rec, int64_t total, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t *out_off, uint64_t *keys_out)
+static int sort_run_checked(nabwa_bam_sort_t *s, int64_t n_rec, int64_t total, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t *out_off, uint64_t *keys_out, uint32_t *perm_out)
 {
 	HIP_CHECK(hipSetDevice(s->device));
 	const int n = (int)n_rec;
@@ -198,31 +198,42 @@ static int sort_run_checked(nabwa_bam_sort_t *s, int64_t n_rec, int64_t total, c
 	HIP_CHECK(hipMemcpyAsync(out, s->d_out.p, (size_t)total, hipMemcpyDeviceToHost, st));
 	if (out_off) HIP_CHECK(hipMemcpyAsync(out_off, s->d_ooff.p, (size_t)(n_rec + 1) * 8, hipMemcpyDeviceToHost, st));
 	if (keys_out) HIP_CHECK(hipMemcpyAsync(keys_out, dk.Current(), (size_t)n_rec * 8, hipMemcpyDeviceToHost, st));
+	if (perm_out) HIP_CHECK(hipMemcpyAsync(perm_out, dv.Current(), (size_t)n_rec * 4, hipMemcpyDeviceToHost, st));
 	HIP_CHECK(hipEventRecord(s->ev[6], st));
 	HIP_CHECK(hipStreamSynchronize(st));
 	for (int k = 0; k < 6; ++k) HIP_CHECK(hipEventElapsedTime(&s->ms[k], s->ev[k], s->ev[k + 1]));
 	return NABWA_OK;
 }
 
-extern "C" int nabwa_bam_sort_run(nabwa_bam_sort_t *s, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out)
+extern "C" int nabwa_bam_sort_run_ex(nabwa_bam_sort_t *s, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out, uint32_t *perm_out)
 {
 	if (!s) return nabwa_fail(NABWA_EINVAL, "null argument");
 	int64_t total = 0;
 	if (int r = sort_check(n_rec, in, in_off, out, cap, &total)) return r;
 	if (n_rec == 0) return NABWA_OK;
-	return sort_run_checked(s, n_rec, total, in, in_off, out, out_off, keys_out);
+	return sort_run_checked(s, n_rec, total, in, in_off, out, out_off, keys_out, perm_out);
 }
 
-extern "C" int nabwa_bam_sort(int device, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out)
+extern "C" int nabwa_bam_sort_ex(int device, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out, uint32_t *perm_out)
 {
 	int64_t total = 0;
 	if (int r = sort_check(n_rec, in, in_off, out, cap, &total)) return r;      /* before the device is looked for */
 	if (n_rec == 0) return NABWA_OK;
 	nabwa_bam_sort_t *s = nullptr;
 	if (int r = nabwa_bam_sort_create(device, &s)) return r;
-	const int r = sort_run_checked(s, n_rec, total, in, in_off, out, out_off, keys_out);
+	const int r = sort_run_checked(s, n_rec, total, in, in_off, out, out_off, keys_out, perm_out);
 	nabwa_bam_sort_destroy(s);
 	return r;
+}
+
+extern "C" int nabwa_bam_sort_run(nabwa_bam_sort_t *s, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out)
+{
+	return nabwa_bam_sort_run_ex(s, n_rec, in, in_off, out, cap, out_off, keys_out, nullptr);
+}
+
+extern "C" int nabwa_bam_sort(int device, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out)
+{
+	return nabwa_bam_sort_ex(device, n_rec, in, in_off, out, cap, out_off, keys_out, nullptr);
 }
 
 extern "C" int nabwa_bam_sort_times(const nabwa_bam_sort_t *s, float ms[6])

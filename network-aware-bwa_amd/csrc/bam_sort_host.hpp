@@ -10,9 +10,9 @@
 #include <vector>
 #include "../../include/nabwa.h"
 
-/* records in[off[i] .. off[i + 1]), i < n, each of at least 36 bytes -> out, out_off (n + 1) and keys_out (n) as nabwa_bam_sort_run gives
- * them, by nt threads.  Returns -1, or the lowest record whose block_size is not what its offsets say (nothing is written to out then) */
-static inline int64_t bam_sort_host(int nt, int64_t n, const uint8_t *in, const int64_t *off, uint8_t *out, int64_t *out_off, uint64_t *keys_out)
+/* records in[off[i] .. off[i + 1]), i < n, each of at least 36 bytes -> out, out_off (n + 1), keys_out (n) and perm_out (n, may be null) as
+ * nabwa_bam_sort_run_ex gives them, by nt threads.  Returns -1, or the lowest record whose block_size is not what its offsets say (nothing is written to out then) */
+static inline int64_t bam_sort_host(int nt, int64_t n, const uint8_t *in, const int64_t *off, uint8_t *out, int64_t *out_off, uint64_t *keys_out, uint32_t *perm_out = nullptr)
 {
 	typedef std::pair<uint64_t, uint32_t> KI;
 	if (nt < 1) nt = 1;
@@ -49,6 +49,7 @@ static inline int64_t bam_sort_host(int nt, int64_t n, const uint8_t *in, const 
 			const uint32_t i = a[(size_t)j].second;
 			memcpy(out + oo[(size_t)j], in + off[i], (size_t)(off[i + 1] - off[i]));
 			if (keys_out) keys_out[j] = a[(size_t)j].first;
+			if (perm_out) perm_out[j] = i;
 		}
 	});
 	if (out_off) memcpy(out_off, oo.data(), sizeof(int64_t) * ((size_t)n + 1));

@@ -1,4 +1,4 @@
-// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, dedup_kernels.hip, dedup_cache_kernels.hip, bgzf_deflate.hip, bgzf_inflate.hip, finish_kernels.hip and damage_kernels.hip, declared once.
+// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, dedup_kernels.hip, dedup_cache_kernels.hip, bgzf_deflate.hip, bgzf_inflate.hip, finish_kernels.hip, damage_kernels.hip and markdup_kernels.hip, declared once.
 // The defining files and every host unit that calls one include this header, so a parameter list that differs between the two sides
 // is a compile error (C linkage carries no types).  Host side only: the kernel headers (nabwa_dev.hpp, fm_search.hpp, fm_deep.hpp,
 // fm_deep_body.hpp) do not include it -- the CPU emulation of the tests compiles those without HIP.
@@ -94,4 +94,14 @@ void nabwa_launch_md_write(const struct FinRef *R, const struct FinRec *recs, in
 struct DmgParams;
 void nabwa_launch_damage(const struct DmgParams *P, int n_blocks, unsigned long long *call, unsigned int *bad, hipStream_t s);
 void nabwa_launch_damage_add(int words, const unsigned long long *call, unsigned long long *total, hipStream_t s);
+/* markdup_kernels.hip (markdup_body.hpp): the records of *P into the call's scratch, *bad (0xffffffff before) = the lowest damaged record;
+ * then, for a sound call, their tuples onto the arena.  The resolve: the index column, the key column of the next radix pass, the marks of
+ * the n sorted tuples, the marks of the n records' unmapped mates */
+struct MdParams; struct MdArena;
+void nabwa_launch_markdup_sig(const struct MdParams *P, int n_blocks, unsigned int *bad, hipStream_t s);
+void nabwa_launch_markdup_emit(const struct MdParams *P, const struct MdArena *A, hipStream_t s);
+void nabwa_launch_markdup_iota(int64_t n, uint32_t *idx, hipStream_t s);
+void nabwa_launch_markdup_gather(int64_t n, const uint32_t *idx, const uint64_t *src, uint64_t *keys, hipStream_t s);
+void nabwa_launch_markdup_mark(int64_t n, const uint32_t *idx, const uint64_t *hi, const uint64_t *lo, const uint64_t *k3, uint8_t *dup, unsigned long long *stats, hipStream_t s);
+void nabwa_launch_markdup_prop(int64_t n, const uint8_t *link, uint8_t *dup, unsigned long long *stats, hipStream_t s);
 }

@@ -809,6 +809,55 @@ int nabwa_markdup_clear(nabwa_markdup_t *m);
 void nabwa_markdup_destroy(nabwa_markdup_t *m);
 int nabwa_markdup_times(const nabwa_markdup_t *m, float ms[5]);
 
+/* ---- the BAM index (.bai, SAM specification 5.2) of finished, coordinate-sorted BAM records on the GPU (nabwa_bai.hip, bai_kernels.hip,
+ * bai_body.hpp).  Records and offsets are those of nabwa_bam_sort; n_ref is the number of reference sequences of the header.
+ * nabwa_bai_add takes records in the order of the file.  stream_off is where in[in_off[0]] lies in the uncompressed BAM stream, the header
+ * included; it is not below the end of the records added before (gaps are allowed).
+ * A record.  tid, pos and flag are its fields; end = pos + the lengths of its M, D, N, = and X operations, or pos + 1 with flag 0x4, without
+ * a CIGAR or where that sum is 0; beg = pos; bin = reg2bin(beg, end) of the specification (the record's own bin field is not read).  A
+ * record with tid < 0 has no place: it is only counted (n_no_coor).
+ * nabwa_bai_finish takes the BGZF blocks of the finished file: blk_uoff[b] and blk_coff[b] are where block b starts in the uncompressed
+ * stream and in the file, entry n_blk being the end-of-file block (blk_uoff[n_blk] is the stream's length).  The virtual offset of stream
+ * offset U is blk_coff[b] << 16 | (U - blk_uoff[b]) with b the last block that has blk_uoff[b] <= U; the stream's end is therefore the
+ * end-of-file block at 0.
+ * The file, fully determined: "BAI\1", n_ref; per reference its bins in rising number, only those that hold records; within a bin the
+ * records in stream order, a record starting a new chunk unless its start lies in the BGZF block in which the bin's previous record ends
+ * (vend >> 16 == vbeg >> 16), a chunk running from its first record's start to its last record's end; a reference with records has
+ * pseudo-bin 37450 last, with the chunks (start of its first record, end of its last) and (records without flag 0x4, records with it);
+ * the linear index has 1 + max((end - 1) >> 14) windows, windows beg >> 14 .. (end - 1) >> 14 of a record taking the lowest start of the
+ * records that touch them, an untouched window the next touched one's value; a reference without records has n_bin = 0 and n_intv = 0;
+ * the file ends with the 64-bit count of the records with tid < 0.
+ * NABWA_EINVAL  a null argument; n_ref < 0; n_rec, offsets and record sizes as nabwa_markdup_add; a stream_off below 0 or below the end of
+ *               the last add; nabwa_bai_finish: n_blk < 0, a blk_uoff that falls, a blk_coff that does not rise, a block of more than 65536
+ *               bytes, a blk_coff of 2^48 or more, a record added that starts before blk_uoff[0] or ends behind blk_uoff[n_blk], more than
+ *               0x7fffffff windows -- decided on the host, before the device is touched
+ * NABWA_ECAP    nabwa_bai_finish: cap is below the file's size (*n_out says it)
+ * NABWA_EDATA   a block_size + 4 that is not the record's extent; 36 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq beyond the
+ *               record; tid >= n_ref; tid >= 0 with pos < 0; end > 2^29; a NABWA_BAM_SORT_KEY below that of the record in front of it, the
+ *               last record of the add before included.  nabwa_last_error names the lowest such record, and the failed call adds nothing
+ * NABWA_ENODEV  no device;  NABWA_ENOMEM  the device cannot hold it: a call needs its bytes + 8 B per record, the handle keeps 32 B per
+ *               record, a finish needs 60 B per record more, 8 B per window and the file
+ * n_rec == 0 and a finish with nothing added are NABWA_OK.  There is no CPU path here.  No byte outside the call's records is read.
+ * nabwa_bai_finish with out == NULL (cap 0) only says the size in *n_out.  It does not consume the handle: more adds and another finish
+ * may follow.  stats (NABWA_BAI_N_STATS words, may be NULL): the records added, those with a place, those without, the bins and the chunks
+ * written (pseudo-bins not counted), the windows, the file's bytes.
+ * nabwa_bai_times: device-event milliseconds -- of the last successful add: upload, signature kernel; of the last finish that wrote a
+ * file: radix sort, virtual offsets / chunks / layout, linear index, writer kernels, download. */
+enum { NABWA_BAI_STAT_RECORDS = 0, NABWA_BAI_STAT_PLACED, NABWA_BAI_STAT_NO_COOR, NABWA_BAI_STAT_BINS, NABWA_BAI_STAT_CHUNKS, NABWA_BAI_STAT_WINDOWS,
+	   NABWA_BAI_STAT_BYTES, NABWA_BAI_N_STATS };
+typedef struct nabwa_bai nabwa_bai_t;
+int nabwa_bai_create(int device, int32_t n_ref, nabwa_bai_t **out);
+int nabwa_bai_add(nabwa_bai_t *b, int64_t n_rec, const uint8_t *in, const int64_t *in_off, int64_t stream_off);
+int nabwa_bai_finish(nabwa_bai_t *b, int64_t n_blk, const int64_t *blk_uoff, const int64_t *blk_coff, uint8_t *out, int64_t cap, int64_t *n_out, uint64_t *stats);
+int nabwa_bai_clear(nabwa_bai_t *b);
+void nabwa_bai_destroy(nabwa_bai_t *b);
+int nabwa_bai_times(const nabwa_bai_t *b, float ms[7]);
+/* host only, no device: the block table of whole BGZF members back to back, for nabwa_bai_finish, from their BSIZE and ISIZE fields.  The
+ * last member is taken as the end-of-file block: *n_blk is the number of members before it, and both arrays (either may be NULL) take
+ * *n_blk + 1 entries where cap (in entries) allows; NABWA_ECAP where it does not (*n_blk is set), NABWA_EDATA for what
+ * nabwa_bgzf_inflated_size refuses, for no member at all and for a last member that is not empty */
+int nabwa_bgzf_block_table(const uint8_t *in, int64_t n, int64_t *blk_uoff, int64_t *blk_coff, int64_t cap, int64_t *n_blk);
+
 #ifdef __cplusplus
 }
 #endif

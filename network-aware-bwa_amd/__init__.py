@@ -393,6 +393,15 @@ def lib():
         L.nabwa_markdup_destroy.argtypes = [_P]
         L.nabwa_markdup_destroy.restype = None
         L.nabwa_markdup_times.argtypes = [_P, _P]
+    if hasattr(L, "nabwa_bai_add"):                # (likewise)
+        L.nabwa_bai_create.argtypes = [C.c_int, C.c_int32, _P]
+        L.nabwa_bai_add.argtypes = [_P, C.c_int64, _P, _P, C.c_int64]
+        L.nabwa_bai_finish.argtypes = [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P]
+        L.nabwa_bai_clear.argtypes = [_P]
+        L.nabwa_bai_destroy.argtypes = [_P]
+        L.nabwa_bai_destroy.restype = None
+        L.nabwa_bai_times.argtypes = [_P, _P]
+        L.nabwa_bgzf_block_table.argtypes = [_P, C.c_int64, _P, _P, C.c_int64, _P]
     if hasattr(L, "nabwa_damage_add"):             # (likewise)
         L.nabwa_damage_default_opt.argtypes = [_P]
         L.nabwa_damage_default_opt.restype = None
@@ -542,6 +551,18 @@ def bgzf_inflated_size(data):
     n_out, n_blocks = C.c_int64(), C.c_int64()
     _chk(lib().nabwa_bgzf_inflated_size(_ptr(a), a.size, C.byref(n_out), C.byref(n_blocks)))
     return n_out.value, n_blocks.value
+
+
+def bgzf_block_table(data):
+    """a BGZF file that ends with its end-of-file block -> (blk_uoff, blk_coff): where every member starts in the inflated stream and in the
+    file, the end-of-file block last (int64 arrays of the members' number), from the BSIZE and ISIZE fields alone; needs no device.  It is
+    what Bai.finish takes.  NabwaError of code EDATA as bgzf_inflated_size, and for a file whose last member is not empty"""
+    a = np.frombuffer(bytes(data), np.uint8)
+    n_blk = C.c_int64()
+    _chk(lib().nabwa_bgzf_block_table(_ptr(a), a.size, None, None, 0, C.byref(n_blk)))
+    uoff, coff = np.zeros(n_blk.value + 1, np.int64), np.zeros(n_blk.value + 1, np.int64)
+    _chk(lib().nabwa_bgzf_block_table(_ptr(a), a.size, _ptr(uoff), _ptr(coff), uoff.size, C.byref(n_blk)))
+    return uoff, coff
 
 
 def bgzf_decompress(data, device=0, cap=None):
@@ -827,6 +848,83 @@ def markdup(records, off=None, device=0, **opts):
     out = a.copy()
     out[off[:-1][dup != 0] + 19] |= 0x04           # flag: bytes 18..19 of a record; 0x400 is bit 2 of the upper one
     return out.tobytes(), dup, stats
+
+
+bai_stat_names = ("records", "placed", "no_coor", "bins", "chunks", "windows", "bytes")      # the slots of stats[], NABWA_BAI_STAT_*
+
+
+class Bai:
+    """the BAM index (.bai) of finished, coordinate-sorted BAM records, built on the GPU (nabwa_bai_*); include/nabwa.h has the rules.
+    n_ref: the reference sequences of the file's header."""
+
+    def __init__(self, n_ref, device=0):
+        self._h = _P()
+        self.end = 0                               # where the records added so far end in the uncompressed stream
+        _chk(lib().nabwa_bai_create(int(device), int(n_ref), C.byref(self._h)))
+
+    def add(self, records, off=None, stream_off=0):
+        """takes the next records of the file; off: their offsets (n + 1), None: walked from the block_size words on the host; stream_off:
+        where the first of them lies in the uncompressed BAM stream, header included -- not before the end of those added so far.  A
+        NabwaError of code EDATA names the first damaged or misplaced record, and that call has added nothing"""
+        a, off = _records_and_offsets(records, off)
+        _chk(lib().nabwa_bai_add(self._h, off.size - 1, _ptr(a) if a.size else None, _ptr(off), int(stream_off)))
+        if off.size > 1:
+            self.end = int(stream_off) + int(off[-1] - off[0])
+
+    def size(self, blk_uoff, blk_coff):
+        """the bytes finish would return"""
+        u, c = np.ascontiguousarray(blk_uoff, np.int64), np.ascontiguousarray(blk_coff, np.int64)
+        if u.ndim != 1 or u.size < 1 or u.shape != c.shape:
+            raise ValueError("blk_uoff, blk_coff: n_blk + 1 entries each")
+        n = C.c_int64()
+        _chk(lib().nabwa_bai_finish(self._h, u.size - 1, _ptr(u), _ptr(c), None, 0, C.byref(n), None))
+        return n.value
+
+    def finish(self, blk_uoff, blk_coff):
+        """blk_uoff, blk_coff: where every BGZF block of the finished file starts in the uncompressed stream and in the file, the
+        end-of-file block last (bgzf_block_table) -> (the .bai file's bytes, stats by bai_stat_names (uint64)).  The handle keeps what was
+        added: more adds and another finish may follow"""
+        u, c = np.ascontiguousarray(blk_uoff, np.int64), np.ascontiguousarray(blk_coff, np.int64)
+        out = np.zeros(self.size(u, c), np.uint8)
+        n, stats = C.c_int64(), np.zeros(len(bai_stat_names), np.uint64)
+        _chk(lib().nabwa_bai_finish(self._h, u.size - 1, _ptr(u), _ptr(c), _ptr(out), out.size, C.byref(n), _ptr(stats)))
+        return out[:n.value].tobytes(), stats
+
+    def clear(self):
+        _chk(lib().nabwa_bai_clear(self._h))
+        self.end = 0
+
+    def times(self):
+        """device-event times in ms: of the last add upload and signature kernel, of the last finish radix sort, virtual offsets / chunks /
+        layout, linear index, writer kernels and download"""
+        ms = (C.c_float * 7)()
+        _chk(lib().nabwa_bai_times(self._h, ms))
+        return list(ms)
+
+    def close(self):
+        if self._h:
+            lib().nabwa_bai_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bai(records, blk_uoff, blk_coff, n_ref, stream_off=0, off=None, device=0):
+    """finished, coordinate-sorted BAM records that start at stream_off of the uncompressed stream, and the block table of the BGZF file they
+    were written to -> (the .bai file's bytes, stats), built on the GPU (Bai used once)"""
+    with Bai(n_ref, device) as b:
+        b.add(records, off, stream_off)
+        return b.finish(blk_uoff, blk_coff)
 
 
 class Index:

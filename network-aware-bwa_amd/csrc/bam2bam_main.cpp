@@ -11,6 +11,7 @@
 // --sort (not the reference's): the records leave sorted by coordinate, runs sorted on the GPU or, NABWA_SORT=host, on host threads.
 // --damage FILE (not the reference's): the damage profile of the records as they leave, counted on the first GPU.
 // --mark-duplicates, --remove-duplicates (not the reference's; with --sort): duplicates found on the first GPU, flagged 0x400 or dropped.
+// --index (not the reference's; with --sort and -f): out.bam.bai beside the output, built on the first GPU from the records as they are written.
 // -t is accepted and ignored (NABWA_DEVICES=0,1,... names the GPUs: an index replica on each, batches dealt to them in turn, searched as
 // they come and passed in input order; default one GPU, NABWA_DEVICE or 0), --temp-dir likewise (the records wait in memory between the passes).
 #include <getopt.h>
@@ -48,7 +49,24 @@ struct BgzfOut {
 	nabwa_bgzf_t *gpu;                                 /* NABWA_BGZF=gpu, gpu-dynamic: the blocks are made by the library's compressor; null: zlib on host threads */
 	std::vector<uint8_t> packed;
 	int codes = NABWA_BGZF_CODES_FIXED;                /* gpu-dynamic: NABWA_BGZF_CODES_DYNAMIC */
-	void write(const void *p, size_t n) { const uint8_t *b = (const uint8_t*)p; pend.insert(pend.end(), b, b + n); if (pend.size() >= (64u << 20)) flush(false); }
+	uint64_t n_taken = 0;                              /* the uncompressed bytes taken so far, the header's first */
+	bool track = false;                                /* --index: where every block written starts, uncompressed and in the file */
+	std::vector<int64_t> blk_u, blk_c;
+	int64_t u_at = 0, c_at = 0;
+	void write(const void *p, size_t n) { const uint8_t *b = (const uint8_t*)p; pend.insert(pend.end(), b, b + n); n_taken += n; if (pend.size() >= (64u << 20)) flush(false); }
+	/* the members just written, whoever made them: BSIZE at +16, ISIZE in the trailer */
+	void note(const uint8_t *p, size_t n)
+	{
+		if (!track) return;
+		for (size_t q = 0; q < n; ) {
+			if (n - q < 26) die("output", "a BGZF block cut short");
+			const size_t bsize = (size_t)(p[q + 16] | p[q + 17] << 8) + 1;
+			if (bsize < 26 || bsize > n - q) die("output", "a BGZF block cut short");
+			uint32_t isize; memcpy(&isize, p + q + bsize - 4, 4);
+			blk_u.push_back(u_at); blk_c.push_back(c_at);
+			u_at += isize; c_at += (int64_t)bsize; q += bsize;
+		}
+	}
 	void flush(bool all)
 	{
 		const size_t BS = 0xff00;
@@ -61,6 +79,7 @@ struct BgzfOut {
 			int64_t n_out = 0, nb = 0;
 			if (nabwa_bgzf_handle_compress_ex(gpu, codes, pend.data(), (int64_t)take, packed.data(), (int64_t)packed.size(), &n_out, &nb) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] BGZF on the GPU: %s\n", nabwa_last_error()); fflush(stderr); _exit(2); }
 			if (fwrite(packed.data(), 1, (size_t)n_out, f) != (size_t)n_out) die("output", "write failed");
+			note(packed.data(), (size_t)n_out);
 			pend.erase(pend.begin(), pend.begin() + take);
 			return;
 		}
@@ -75,6 +94,7 @@ struct BgzfOut {
 		});
 		for (auto &x : th) x.join();
 		for (auto &p : parts) if (!p.empty() && fwrite(p.data(), 1, p.size(), f) != p.size()) die("output", "write failed");
+		for (auto &p : parts) note(p.data(), p.size());
 		pend.erase(pend.begin(), pend.begin() + take);
 	}
 	void close()
@@ -82,6 +102,7 @@ struct BgzfOut {
 		flush(true);
 		static const uint8_t eof[28] = { 31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 		if (fwrite(eof, 1, 28, f) != 28 || fflush(f) != 0) die("output", "write failed");
+		note(eof, 28);
 		if (f != stdout) fclose(f);
 	}
 };
@@ -175,6 +196,7 @@ struct Options {
 	bool mark_dups = false, remove_dups = false;               /* --mark-duplicates, --remove-duplicates */
 	nabwa_markdup_opt_t markdup;                               /* NABWA_MARKDUP_ENDS, NABWA_MARKDUP_QUAL */
 	bool dups() const { return mark_dups || remove_dups; }
+	bool index = false;                                        /* --index: out.bam.bai beside the output */
 };
 /* -1: go on; else the exit status, after the line that says why */
 static int parse_options(int argc, char **argv, Options &o)
@@ -188,7 +210,7 @@ static int parse_options(int argc, char **argv, Options &o)
 		{ "broken-input", 0, 0, 130 }, { "skip-duplicates", 0, 0, 131 }, { "temp-dir", 1, 0, 132 }, { "max-insert-size", 1, 0, 'a' },
 		{ "max-occurences", 1, 0, 'C' }, { "max-occurences-se", 1, 0, 'D' }, { "max-hits", 1, 0, 'h' }, { "max-discordant-hits", 1, 0, 'H' },
 		{ "chimeric-rate", 1, 0, 'c' }, { "disable-sw", 0, 0, 's' }, { "disable-isize-estimate", 0, 0, 'A' }, { "listen-port", 1, 0, 'p' }, { "sort", 0, 0, 134 }, { "damage", 1, 0, 135 },
-		{ "mark-duplicates", 0, 0, 136 }, { "remove-duplicates", 0, 0, 137 }, { 0, 0, 0, 0 } };
+		{ "mark-duplicates", 0, 0, 136 }, { "remove-duplicates", 0, 0, 137 }, { "index", 0, 0, 138 }, { 0, 0, 0, 0 } };
 	nabwa_gap_opt_t &go = o.go; nabwa_pe_opt_t &po = o.po;
 	nabwa_gap_init_opt(&go);
 	nabwa_pe_opt_default(&po);
@@ -218,6 +240,7 @@ static int parse_options(int argc, char **argv, Options &o)
 			case 135: o.damage_file = optarg; break;
 			case 136: o.mark_dups = true; break;
 			case 137: o.remove_dups = true; break;
+			case 138: o.index = true; break;
 			case 'p': case '0': case '1': case '2':
 				fprintf(stderr, "[nabwa_bam2bam] this option of bwa bam2bam is not provided (0MQ modes, .sai resume)\n");
 				return 1;
@@ -230,7 +253,7 @@ static int parse_options(int argc, char **argv, Options &o)
 	if (po.n_multi < 0 || po.n_multi > NABWA_MAX_MULTI || po.N_multi < 0 || po.N_multi > NABWA_MAX_MULTI) { fprintf(stderr, "[nabwa_bam2bam] -h / -H: 0..%d\n", NABWA_MAX_MULTI); return 1; }
 	if (go.s_mm < 1 || go.s_gapo < 1 || go.s_gape < 1) { fprintf(stderr, "[nabwa_bam2bam] -M / -O / -E must be at least 1\n"); return 1; }
 	if (optind + 1 > argc || !o.prefix) {
-		fprintf(stderr, "\nUsage:   nabwa_bam2bam -g PREFIX [options of bwa bam2bam] [--sort [--mark-duplicates | --remove-duplicates]] [--damage FILE] [-f out.bam] <in.bam>\n\n"
+		fprintf(stderr, "\nUsage:   nabwa_bam2bam -g PREFIX [options of bwa bam2bam] [--sort [--mark-duplicates | --remove-duplicates] [--index]] [--damage FILE] [-f out.bam] <in.bam>\n\n"
 						"         --sort   write the records sorted by coordinate (@HD SO:coordinate; ties keep the input order).\n"
 						"                  NABWA_SORT=gpu|host: who sorts a run (default gpu); NABWA_SORT_RUN_MIB: record bytes per run (default 1024)\n"
 						"         --damage FILE   write the damage profile of the records to FILE: substitutions against the reference by distance from\n"
@@ -241,7 +264,9 @@ static int parse_options(int argc, char **argv, Options &o)
 						"                  path, also under NABWA_SORT=host.  With --damage the profile then leaves the duplicates out\n"
 						"         --remove-duplicates   the same, but the duplicates are dropped\n"
 						"                  NABWA_MARKDUP_ENDS=5p|both: single reads are equal on their 5' end (default) or on both ends (merged reads);\n"
-						"                  NABWA_MARKDUP_QUAL: the lowest base quality that counts, 0..93 (default 15)\n\n");
+						"                  NABWA_MARKDUP_QUAL: the lowest base quality that counts, 0..93 (default 15)\n"
+						"         --index   with --sort and -f: write the BAM index of the output to <out.bam>.bai, from the records as they are written.\n"
+						"                  Built on the gpu; there is no host path, also under NABWA_SORT=host.  No reference sequence may be longer than 2^29\n\n");
 		return 1;
 	}
 	o.input = argv[optind];
@@ -292,6 +317,9 @@ static int parse_options(int argc, char **argv, Options &o)
 			o.markdup.min_qual = (int32_t)v;
 		}
 	}
+	/* --index: the index of a file in coordinate order, which has a name */
+	if (o.index && !o.sort) { fprintf(stderr, "[nabwa_bam2bam] --index needs --sort: a BAM index is one of a file in coordinate order\n"); return 1; }
+	if (o.index && !o.ofile) { fprintf(stderr, "[nabwa_bam2bam] --index needs -f out.bam: the index goes to out.bam.bai, and standard output has no name\n"); return 1; }
 	/* --damage only: NABWA_DAMAGE_POS, the positions counted from either end, and NABWA_DAMAGE_MAPQ, the lowest mapping quality counted */
 	if (o.damage_file) {
 		nabwa_damage_default_opt(&o.damage);
@@ -353,7 +381,11 @@ static void write_output_header(BgzfOut &out, nabwa_index_t *ix, const std::stri
  * first GPU and passes it on untouched; a piece is a whole batch, and read_batches keeps mates in one batch, so mates reach the library next
  * to each other.  The records' ordinals are their places in the stream sort_runs takes; each run keeps them beside its keys (run base + the
  * sort's permutation).  When the input ends the stage resolves once, and sort_runs, as it hands over or merges, sets 0x400 on a duplicate
- * or leaves it out.  --damage then counts behind the sort, on what leaves. */
+ * or leaves it out.  --damage then counts behind the sort, on what leaves.
+ * --index puts one stage right in front of write_out (behind count_damage where that one is there too): index_records hands every piece to
+ * nabwa_bai_add on the first GPU with the offset the writer will give it in the uncompressed stream -- the header's length, then what went
+ * before -- and passes it on untouched; it sees exactly the records that are written.  BgzfOut notes where each block it writes starts, and
+ * main finishes the index from that table once the file is closed. */
 struct InBatch { std::vector<uint8_t> buf; std::vector<int64_t> off; };
 struct OutBytes { std::unique_ptr<uint8_t[]> p; size_t n = 0; std::vector<int64_t> off; };      /* no zero fill: the library writes every byte.  off: --sort and --damage, the records' offsets where emit has them */
 /* a sorted run of --sort: its records in key order (in memory, or n bytes from `at` in the run file), their offsets and their keys */
@@ -385,6 +417,11 @@ struct Pipeline {
 	uint64_t dup_stats[NABWA_MARKDUP_N_STATS] = {};
 	uint64_t n_run_base = 0, n_marked_in = 0;                 /* records in the runs sorted so far; records the marker has taken */
 	double t_markdup = 0;
+	/* --index */
+	Chan<OutBytes> indexed_ch{2};
+	nabwa_bai_t *bai = 0;
+	int64_t index_at = 0;                                     /* where the next piece lies in the uncompressed stream: behind the header, then behind what was passed on */
+	double t_index = 0;
 	/* the main thread's: the insert-size table, the random numbers (srand48(bns->seed), bam2bam.c:1745), what waits for pass 2 */
 	nabwa_isize_table_t *tab; uint64_t rng;
 	std::vector<nabwa_bam_batch_t*> waiting;
@@ -718,9 +755,27 @@ struct Pipeline {
 		sorted_ch.close();
 		t_sort += now_s() - t0 - t_blocked;
 	}
+	/* what leaves for the file, in the file's order */
+	Chan<OutBytes> &leaving() { return opt.dups() && opt.damage_file ? counted_ch : opt.sort ? sorted_ch : emitted(); }
+	/* --index: every piece through nabwa_bai_add with the stream offset it is written at, then on as it is */
+	void index_records()
+	{
+		OutBytes o;
+		std::vector<int64_t> walked;
+		while (leaving().get(o)) {
+			const double t0 = now_s();
+			if (o.off.empty()) walk_records(o, walked, "index");
+			const std::vector<int64_t> &off = o.off.empty() ? walked : o.off;
+			if (nabwa_bai_add(bai, (int64_t)off.size() - 1, o.p.get(), off.data(), index_at) != NABWA_OK) die("index", nabwa_last_error());
+			index_at += (int64_t)o.n;
+			t_index += now_s() - t0;
+			indexed_ch.put(std::move(o));
+		}
+		indexed_ch.close();
+	}
 	void write_out()
 	{
-		Chan<OutBytes> &from = opt.dups() && opt.damage_file ? counted_ch : opt.sort ? sorted_ch : emitted();
+		Chan<OutBytes> &from = opt.index ? indexed_ch : leaving();
 		OutBytes o;
 		while (from.get(o)) { const double t0 = now_s(); out.write(o.p.get(), o.n); o.p.reset(); t_write += now_s() - t0; }
 	}
@@ -780,6 +835,8 @@ int main(int argc, char **argv)
 	/* --mark-duplicates, --remove-duplicates: the handle on the first GPU now, for the same reason; there is no host path, whatever NABWA_SORT says */
 	nabwa_markdup_t *markdup = 0;
 	if (opt.dups() && nabwa_markdup_create(devices[0], &opt.markdup, &markdup) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] %s on the GPU: %s\n", opt.mark_dups ? "--mark-duplicates" : "--remove-duplicates", nabwa_last_error()); return 2; }
+	/* --index builds on the first GPU, through a handle made below, once the index says how many reference sequences there are */
+	if (opt.index && nabwa_device_count() <= devices[0]) { fprintf(stderr, "[nabwa_bam2bam] --index on the GPU: no HIP device %d\n", devices[0]); return 2; }
 	/* --damage counts on the first GPU, through a handle on that GPU's index (made below, once the index is there): no such device ends the run here */
 	if (opt.damage_file && nabwa_device_count() <= devices[0]) { fprintf(stderr, "[nabwa_bam2bam] --damage on the GPU: no HIP device %d\n", devices[0]); return 2; }
 	std::vector<nabwa_index_t*> ixs;
@@ -793,6 +850,15 @@ int main(int argc, char **argv)
 	/* --damage: its handle on the first GPU's index now, so that a run that cannot count ends before anything is written */
 	nabwa_damage_t *damage = 0;
 	if (opt.damage_file && nabwa_damage_create(ixs[0], &opt.damage, &damage) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] --damage on the GPU: %s\n", nabwa_last_error()); return 2; }
+
+	/* --index: a .bai addresses 2^29 bases of a reference sequence; its handle now, so that a run that cannot index ends before anything is written */
+	nabwa_bai_t *bai = 0;
+	if (opt.index) {
+		each_contig(ixs[0], [&](const char *name, int32_t len) {
+			if ((int64_t)len > ((int64_t)1 << 29)) { fprintf(stderr, "[nabwa_bam2bam] --index: reference sequence %s has %ld bases, a BAM index addresses 536870912\n", name, (long)len); exit(1); }
+		});
+		if (nabwa_bai_create(devices[0], nabwa_index_n_contigs(ixs[0]), &bai) != NABWA_OK) { fprintf(stderr, "[nabwa_bam2bam] --index on the GPU: %s\n", nabwa_last_error()); return 2; }
+	}
 
 	FILE *inf = strcmp(opt.input, "-") ? fopen(opt.input, "rb") : stdin;
 	if (!inf) die(opt.input, "cannot open");
@@ -809,6 +875,7 @@ int main(int argc, char **argv)
 	if (!of) die(opt.ofile, "cannot create");
 	BgzfOut out{ of, {}, 2, bgzf, {} };
 	if (opt.bgzf_dynamic) out.codes = NABWA_BGZF_CODES_DYNAMIC;
+	out.track = opt.index;
 	write_output_header(out, ixs[0], old, argc, argv, opt.sort);
 
 	const bool timing = getenv("NABWA_TIMING") != 0;
@@ -817,7 +884,9 @@ int main(int argc, char **argv)
 	P.sorter = sorter;
 	P.damage = damage;
 	P.markdup = markdup;
-	std::thread sort_thread, damage_thread, markdup_thread;
+	P.bai = bai; P.index_at = (int64_t)out.n_taken;
+	std::thread sort_thread, damage_thread, markdup_thread, index_thread;
+	if (bai) index_thread = std::thread(&Pipeline::index_records, &P);
 	if (markdup) markdup_thread = std::thread(&Pipeline::mark_duplicates, &P);
 	if (damage) damage_thread = std::thread(&Pipeline::count_damage, &P);
 	if (opt.sort) sort_thread = std::thread(&Pipeline::sort_runs, &P);
@@ -837,6 +906,7 @@ int main(int argc, char **argv)
 	if (damage && !markdup) damage_thread.join();
 	if (opt.sort) sort_thread.join();
 	if (damage && markdup) damage_thread.join();
+	if (bai) index_thread.join();
 	writer.join();
 
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: start-up (device, index, headers) %.3f s, records %.3f s\n", t_loop - t_main, now_s() - t_loop);
@@ -844,6 +914,7 @@ int main(int argc, char **argv)
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: library calls: create %.3f s, pass 1 %.3f s, pass 2 %.3f s, output %.3f s, destroy %.3f s\n", P.t_call[0], P.t_call[1], P.t_call[2], P.t_call[3], P.t_call[4]);
 	if (timing && damage) fprintf(stderr, "[nabwa_bam2bam] timing: damage thread %.3f s busy (upload and count on the gpu)\n", P.t_damage);
 	if (timing && markdup) fprintf(stderr, "[nabwa_bam2bam] timing: duplicates thread %.3f s busy (upload, signatures and the resolve on the gpu)\n", P.t_markdup);
+	if (timing && bai) fprintf(stderr, "[nabwa_bam2bam] timing: index thread %.3f s busy (upload and tuples on the gpu)\n", P.t_index);
 	if (timing && opt.sort) fprintf(stderr, "[nabwa_bam2bam] timing: sort thread %.3f s busy (%zu run(s) sorted on the %s, then handed on or merged)\n", P.t_sort, P.runs.size(), sorter ? "gpu" : "host");
 	if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: reader thread %.3f s busy (%.3f s of it inflate, %s), passes 1 and 2 on this thread %.3f s (+ %.3f s waiting for input; the output thread waited %.3f s for the writer), writer thread %.3f s busy (deflate + write; %s)\n",
 						P.t_read, in.t_inflate, in.bgzf ? (bgzf_in ? "BGZF blocks on the GPU" : "BGZF blocks in parallel") : in.raw ? "not compressed" : "one gzip stream", P.t_lib, P.t_wait_in, P.t_wait_out, P.t_write,
@@ -862,10 +933,29 @@ int main(int argc, char **argv)
 	tool_dedup_cache_summary(ixs);
 	for (nabwa_index_t *p : ixs) nabwa_index_destroy(p);
 	final_rename(opt.ofile, true);
+	uint64_t bai_stats[NABWA_BAI_N_STATS] = {};
+	if (bai) {                                                  /* the file is whole: its block table is, and the index goes beside the name it ends up with */
+		const double t0 = now_s();
+		int64_t n_bai = 0;
+		if (nabwa_bai_finish(bai, (int64_t)out.blk_u.size() - 1, out.blk_u.data(), out.blk_c.data(), 0, 0, &n_bai, 0) != NABWA_OK) die("index", nabwa_last_error());
+		std::vector<uint8_t> file((size_t)n_bai);
+		if (nabwa_bai_finish(bai, (int64_t)out.blk_u.size() - 1, out.blk_u.data(), out.blk_c.data(), file.data(), n_bai, &n_bai, bai_stats) != NABWA_OK) die("index", nabwa_last_error());
+		nabwa_bai_destroy(bai);
+		std::string name(opt.ofile);
+		size_t e = name.size();
+		while (e > 0 && name[e - 1] == '_') --e;                /* final_rename's rule */
+		if (e != 0 && name[e - 1] != '/') name.resize(e);
+		name += ".bai";
+		FILE *bf = fopen(name.c_str(), "wb");
+		if (!bf || fwrite(file.data(), 1, file.size(), bf) != file.size() || fclose(bf) != 0) die(name.c_str(), "cannot write");
+		if (timing) fprintf(stderr, "[nabwa_bam2bam] timing: index finished and written in %.3f s\n", now_s() - t0);
+	}
 	if (opt.sort) fprintf(stderr, "[nabwa_bam2bam] sorted %llu records in %zu run(s) on the %s\n", (unsigned long long)P.n_sorted, P.runs.size(), opt.sort_host ? "host" : "gpu");
 	if (damage) fprintf(stderr, "%s", damage_line.c_str());
 	if (opt.dups()) fprintf(stderr, "[nabwa_bam2bam] %s %llu of %llu records as duplicates (%llu pairs, %llu single reads) on the gpu\n", opt.remove_dups ? "removed" : "marked",
 							(unsigned long long)P.dup_stats[NABWA_MARKDUP_STAT_DUP_RECORDS], (unsigned long long)P.dup_stats[NABWA_MARKDUP_STAT_SEEN],
 							(unsigned long long)P.dup_stats[NABWA_MARKDUP_STAT_DUP_PAIRS], (unsigned long long)P.dup_stats[NABWA_MARKDUP_STAT_DUP_FRAGMENTS]);
+	if (opt.index) fprintf(stderr, "[nabwa_bam2bam] indexed %llu records, %llu chunks in %llu bins on the gpu\n", (unsigned long long)bai_stats[NABWA_BAI_STAT_RECORDS],
+							(unsigned long long)bai_stats[NABWA_BAI_STAT_CHUNKS], (unsigned long long)bai_stats[NABWA_BAI_STAT_BINS]);
 	return 0;
 }

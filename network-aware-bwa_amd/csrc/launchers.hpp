@@ -1,4 +1,4 @@
-// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, dedup_kernels.hip, dedup_cache_kernels.hip, bgzf_deflate.hip, bgzf_inflate.hip, finish_kernels.hip, damage_kernels.hip and markdup_kernels.hip, declared once.
+// launchers.hpp -- the host-callable launchers and occupancy queries of fm_index.hip, fm_search.hip, batch_kernels.hip, fm_deep.hip, dedup_kernels.hip, dedup_cache_kernels.hip, bgzf_deflate.hip, bgzf_inflate.hip, finish_kernels.hip, damage_kernels.hip, markdup_kernels.hip and bai_kernels.hip, declared once.
 // The defining files and every host unit that calls one include this header, so a parameter list that differs between the two sides
 // is a compile error (C linkage carries no types).  Host side only: the kernel headers (nabwa_dev.hpp, fm_search.hpp, fm_deep.hpp,
 // fm_deep_body.hpp) do not include it -- the CPU emulation of the tests compiles those without HIP.
@@ -104,4 +104,13 @@ void nabwa_launch_markdup_iota(int64_t n, uint32_t *idx, hipStream_t s);
 void nabwa_launch_markdup_gather(int64_t n, const uint32_t *idx, const uint64_t *src, uint64_t *keys, hipStream_t s);
 void nabwa_launch_markdup_mark(int64_t n, const uint32_t *idx, const uint64_t *hi, const uint64_t *lo, const uint64_t *k3, uint8_t *dup, unsigned long long *stats, hipStream_t s);
 void nabwa_launch_markdup_prop(int64_t n, const uint8_t *link, uint8_t *dup, unsigned long long *stats, hipStream_t s);
+/* bai_kernels.hip (bai_body.hpp): the records of *P as tuples into the arena, P->cnt[0] (0xffffffff before) = the lowest damaged record,
+ * P->cnt[1] (0 before) = the records without a reference.  The finish: the ordinal column, then the steps of *F in the order of the enum,
+ * a sort and three scans between them (nabwa_bai.hip) */
+struct BaiParams; struct BaiFin;
+enum { NABWA_BAI_STEP_REF = 0, NABWA_BAI_STEP_HEAD, NABWA_BAI_STEP_PLACE, NABWA_BAI_STEP_REFSIZE, NABWA_BAI_STEP_LIN, NABWA_BAI_STEP_WRITE_REF,
+	   NABWA_BAI_STEP_WRITE_TUPLE, NABWA_BAI_STEP_WRITE_LIN };
+void nabwa_launch_bai_sig(const struct BaiParams *P, int n_blocks, hipStream_t s);
+void nabwa_launch_bai_iota(int64_t n, uint32_t *idx, hipStream_t s);
+void nabwa_launch_bai_step(int step, const struct BaiFin *F, hipStream_t s);
 }

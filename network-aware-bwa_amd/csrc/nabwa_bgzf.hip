@@ -188,6 +188,25 @@ extern "C" int nabwa_bgzf_inflated_size(const uint8_t *in, int64_t n, int64_t *n
 	return bgzf_walk(in, n, nullptr, n_out, n_blocks);
 }
 
+extern "C" int nabwa_bgzf_block_table(const uint8_t *in, int64_t n, int64_t *blk_uoff, int64_t *blk_coff, int64_t cap, int64_t *n_blk)
+{
+	if (n < 0 || (n && !in) || cap < 0 || !n_blk) return nabwa_fail(NABWA_EINVAL, "null argument");
+	*n_blk = 0;
+	std::vector<BgzfInBlk> blk;
+	if (int r = bgzf_walk(in, n, &blk, nullptr, nullptr)) return r;
+	if (blk.empty()) return edata("no BGZF member: %lld bytes", (long long)n);
+	if (blk.back().isize != 0) return edata("BGZF member %lld, the last, is no end-of-file block: ISIZE %lld", (long long)blk.size() - 1, (long long)blk.back().isize);
+	*n_blk = (int64_t)blk.size() - 1;
+	if ((blk_uoff || blk_coff) && cap < (int64_t)blk.size()) return nabwa_fail(NABWA_ECAP, "the block table needs one entry per BGZF member (*n_blk + 1)");
+	int64_t at = 0;                                    /* where member k starts: behind the trailer of the one before */
+	for (size_t k = 0; k < blk.size(); ++k) {
+		if (blk_uoff) blk_uoff[k] = (int64_t)blk[k].dst;
+		if (blk_coff) blk_coff[k] = at;
+		at = (int64_t)(blk[k].src + blk[k].n_src + 8);
+	}
+	return NABWA_OK;
+}
+
 static int inflate_grow(nabwa_bgzf *z, DevBuf &b, int64_t &cap, int64_t want)
 {
 	if (want <= cap) return NABWA_OK;

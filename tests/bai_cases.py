@@ -1,0 +1,520 @@
+"""What the tests of the BAM index (nabwa_bai_*, nabwa.Bai, `nabwa_bam2bam --sort --index`) share: the Python oracle of the semantics in
+include/nabwa.h -- dicts of bins and windows, no sorting, no scans --, a reader of .bai files that answers region queries the way the SAM
+specification describes (reg2bins, chunks, the linear index, seek and inflate), BGZF files of small blocks, the case lists, and the CPU
+builds of csrc/bai_body.hpp under tests/emu/, so that tests/test_bai_emu.py runs the inputs of tests/test_gpu_bai.py through the bodies
+without a GPU."""
+import bisect
+import ctypes as C
+import os
+import struct
+import subprocess
+import zlib
+
+import numpy as np
+
+import bamlib as B
+import nabwa_testlib as T
+from damage_cases import Damaged, many_ops, parse_cigar, record, split_records       # noqa: F401  (the record builder and its kin)
+
+EMU_DIR = os.path.join(T.ROOT, "tests", "emu")
+CSRC = os.path.join(T.ROOT, "network-aware-bwa_amd", "csrc")
+STAT_NAMES = ("records", "placed", "no_coor", "bins", "chunks", "windows", "bytes")
+N_STATS = len(STAT_NAMES)
+RECORDS, PLACED, NO_COOR, BINS, CHUNKS, WINDOWS, BYTES = range(N_STATS)
+MAX_END = 1 << 29
+PSEUDO_BIN = 37450
+
+
+# ---------------------------------------------------------------------------------------------------------------- records
+def rec(ref_id, pos, cigar, flag=0, name=b"r", **kw):
+    """an aligned record whose sequence is as long as its CIGAR says"""
+    ops = parse_cigar(cigar)
+    L = sum(n for n, op in ops if op in "MIS=X")
+    return record(ref_id, pos, 37, flag, ops, "A" * min(L, 40) if L > 4000 else "A" * L, name=name, **kw)
+
+
+def unmapped(ref_id=-1, pos=-1, flag=4, name=b"u", L=8):
+    return record(ref_id, pos, 0, flag, "*", "C" * L, name=name)
+
+
+def sort_key(r):
+    tid, pos = struct.unpack_from("<ii", r, 4)
+    return ((tid & 0xffffffff) << 32) | ((pos + 1) & 0xffffffff)
+
+
+def in_order(recs):
+    """the records in coordinate order, ties in the order given (what --sort writes)"""
+    return sorted(recs, key=sort_key)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the oracle
+def reg2bin(beg, end):
+    end -= 1
+    for shift, first in ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1)):
+        if beg >> shift == end >> shift:
+            return first + (beg >> shift)
+    return 0
+
+
+def reg2bins(beg, end):
+    end -= 1
+    out = [0]
+    for shift, first in ((26, 1), (23, 9), (20, 73), (17, 585), (14, 4681)):
+        out += range(first + (beg >> shift), first + (end >> shift) + 1)
+    return out
+
+
+def parse(r, n_ref):
+    """a record's bytes -> (tid, pos, flag, end), or None for one that is damaged whatever stands in front of it"""
+    size = len(r)
+    bs, tid, pos, l_name, _mapq, _bin, n_cig, flag, L = struct.unpack_from("<IiiBBHHHI", r, 0)
+    if bs + 4 != size or 36 + l_name + 4 * n_cig + (L + 1) // 2 + L > size:
+        return None
+    if tid >= n_ref or (tid >= 0 and pos < 0):
+        return None
+    span = 0
+    if tid >= 0 and not flag & 4:
+        span = sum(w >> 4 for w in struct.unpack_from("<%dI" % n_cig, r, 36 + l_name) if w & 15 in (0, 2, 3, 7, 8))
+    end = pos + (span if span else 1)
+    if tid >= 0 and end > MAX_END:
+        return None
+    return tid, pos, flag, end
+
+
+def voff_of(u, blk_uoff, blk_coff):
+    b = bisect.bisect_right(blk_uoff, u) - 1
+    assert 0 <= b and 0 <= u - blk_uoff[b] <= 0xffff
+    return int(blk_coff[b]) << 16 | (u - int(blk_uoff[b]))
+
+
+def oracle(calls, n_ref, blk_uoff, blk_coff):
+    """calls: (records, stream_off) in turn -> (the .bai file, stats).  Raises Damaged(lowest index) for the first call that holds a damaged
+    record; leave such a call out to see what the handle holds after it"""
+    blk_uoff, blk_coff = [int(x) for x in blk_uoff], [int(x) for x in blk_coff]
+    refs = [dict(bins={}, lin={}, first=None, last=None, mapped=0, unmapped=0) for _ in range(n_ref)]
+    n_no_coor = n_all = 0
+    last_key = 0
+    for recs, stream_off in calls:
+        u = stream_off
+        for i, r in enumerate(recs):
+            r = bytes(r)
+            x = parse(r, n_ref)
+            if x is None or sort_key(r) < last_key:
+                raise Damaged(i)
+            last_key = sort_key(r)
+        for r in recs:
+            tid, pos, flag, end = parse(bytes(r), n_ref)
+            us, ue = u, u + len(r)
+            u = ue
+            n_all += 1
+            if tid < 0:
+                n_no_coor += 1
+                continue
+            vb, ve = voff_of(us, blk_uoff, blk_coff), voff_of(ue, blk_uoff, blk_coff)
+            R = refs[tid]
+            chunks = R["bins"].setdefault(reg2bin(pos, end), [])
+            if chunks and chunks[-1][1] >> 16 == vb >> 16:
+                chunks[-1][1] = ve
+            else:
+                chunks.append([vb, ve])
+            for w in range(pos >> 14, ((end - 1) >> 14) + 1):
+                R["lin"][w] = min(R["lin"].get(w, vb), vb)
+            R["first"] = vb if R["first"] is None else R["first"]
+            R["last"] = ve
+            R["unmapped" if flag & 4 else "mapped"] += 1
+    out = [b"BAI\1", struct.pack("<i", n_ref)]
+    n_bins = n_chunks = n_win = 0
+    for R in refs:
+        if R["first"] is None:
+            out.append(struct.pack("<ii", 0, 0))
+            continue
+        out.append(struct.pack("<i", len(R["bins"]) + 1))
+        for b in sorted(R["bins"]):
+            out.append(struct.pack("<Ii", b, len(R["bins"][b])))
+            out += [struct.pack("<QQ", *c) for c in R["bins"][b]]
+            n_bins, n_chunks = n_bins + 1, n_chunks + len(R["bins"][b])
+        out.append(struct.pack("<IiQQQQ", PSEUDO_BIN, 2, R["first"], R["last"], R["mapped"], R["unmapped"]))
+        n_intv = max(R["lin"]) + 1
+        vals, nxt = [0] * n_intv, None
+        for w in range(n_intv - 1, -1, -1):
+            nxt = R["lin"].get(w, nxt)
+            vals[w] = nxt
+        out.append(struct.pack("<i%dQ" % n_intv, n_intv, *vals))
+        n_win += n_intv
+    out.append(struct.pack("<Q", n_no_coor))
+    data = b"".join(out)
+    return data, np.array([n_all, n_all - n_no_coor, n_no_coor, n_bins, n_chunks, n_win, len(data)], np.uint64)
+
+
+# ---------------------------------------------------------------------------------------------------------------- BGZF and the reader
+def bgzf_pack(stream, sizes, level=6):
+    """the stream as BGZF members of sizes[0], sizes[1], ... (in turn, over again) uncompressed bytes, and the end-of-file block"""
+    out, q, k = [], 0, 0
+    while q < len(stream):
+        part = stream[q:q + sizes[k % len(sizes)]]
+        q, k = q + len(part), k + 1
+        z = zlib.compressobj(level, zlib.DEFLATED, -15)
+        body = z.compress(part) + z.flush()
+        out.append(struct.pack("<4BI2BH2BHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, len(body) + 25) + body + struct.pack("<II", zlib.crc32(part), len(part)))
+    out.append(bytes([31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0]))
+    return b"".join(out)
+
+
+def block_table(data):
+    """(blk_uoff, blk_coff) of a BGZF file that ends with its end-of-file block, from BSIZE and ISIZE alone"""
+    uoff, coff, q, u = [], [], 0, 0
+    while q < len(data):
+        bsize = struct.unpack_from("<H", data, q + 16)[0] + 1
+        uoff.append(u)
+        coff.append(q)
+        u += struct.unpack_from("<I", data, q + bsize - 4)[0]
+        q += bsize
+    assert q == len(data) and len(uoff) >= 1 and (len(uoff) == 1 or uoff[-1] >= uoff[-2])
+    return np.array(uoff, np.int64), np.array(coff, np.int64)
+
+
+class Bgzf:
+    """a BGZF file read at virtual offsets; which blocks were inflated is kept in .touched"""
+
+    def __init__(self, data):
+        self.data, self.touched, self.cache = data, set(), {}
+
+    def block(self, coff):
+        if coff not in self.cache:
+            bsize = struct.unpack_from("<H", self.data, coff + 16)[0] + 1
+            self.cache[coff] = (zlib.decompress(self.data[coff + 18:coff + bsize - 8], -15), coff + bsize)
+            self.touched.add(coff)
+        return self.cache[coff]
+
+    def read(self, v, n):
+        """n bytes from virtual offset v -> (bytes, the virtual offset behind them)"""
+        coff, at, out = v >> 16, v & 0xffff, b""
+        while True:
+            plain, nxt = self.block(coff)
+            part = plain[at:at + n - len(out)]
+            out, at = out + part, at + len(part)
+            if len(out) == n:
+                return out, coff << 16 | at
+            coff, at = nxt, 0
+            if coff >= len(self.data):
+                raise EOFError("a read past the end-of-file block")
+
+    def tell_start(self, v):
+        """v normalised: the end of a block is the start of the next one with bytes (what a reader's position is before it reads on)"""
+        coff, at = v >> 16, v & 0xffff
+        while coff < len(self.data):
+            plain, nxt = self.block(coff)
+            if at < len(plain) or nxt >= len(self.data):
+                break
+            coff, at = nxt, 0
+        return coff << 16 | at
+
+
+def parse_bai(data):
+    """-> (per reference (bins: {bin: [(beg, end)]}, lin: [..]), n_no_coor); every byte must be used"""
+    assert data[:4] == b"BAI\1"
+    n_ref, q, refs = struct.unpack_from("<i", data, 4)[0], 8, []
+    for _ in range(n_ref):
+        n_bin, bins = struct.unpack_from("<i", data, q)[0], {}
+        q += 4
+        for _ in range(n_bin):
+            b, n_chunk = struct.unpack_from("<Ii", data, q)
+            q += 8
+            assert b not in bins
+            bins[b] = [struct.unpack_from("<QQ", data, q + 16 * k) for k in range(n_chunk)]
+            q += 16 * n_chunk
+        n_intv = struct.unpack_from("<i", data, q)[0]
+        refs.append((bins, list(struct.unpack_from("<%dQ" % n_intv, data, q + 4))))
+        q += 4 + 8 * n_intv
+    n_no_coor = struct.unpack_from("<Q", data, q)[0]
+    assert q + 8 == len(data)
+    return refs, n_no_coor
+
+
+def extent(r):
+    """(tid, beg, end) of a sound record"""
+    tid, pos, _, end = parse(bytes(r), 1 << 31)
+    return tid, pos, end
+
+
+def query(bai, f, tid, beg, end):
+    """the records of reference tid that overlap [beg, end), read from the Bgzf f through the parsed index: the chunks of the bins of
+    reg2bins, those dropped that end at or before the linear index's value for beg's window, then seek, inflate and filter"""
+    bins, lin = bai[0][tid]
+    if beg >> 14 >= len(lin):
+        return []
+    min_off = lin[beg >> 14]
+    chunks = sorted(c for b in reg2bins(beg, end) for c in bins.get(b, []) if c[1] > min_off)
+    out, seen = [], set()
+    for cb, ce in chunks:
+        v = cb
+        while f.tell_start(v) < ce:
+            at = f.tell_start(v)
+            head, v = f.read(v, 4)
+            body, v = f.read(v, struct.unpack("<I", head)[0])
+            r = head + body
+            rt, rb, re_ = extent(r)
+            if rt != tid or rb >= end:
+                break
+            if re_ > beg and at not in seen:
+                seen.add(at)
+                out.append((at, r))
+    return [r for _, r in sorted(out)]
+
+
+def scan(recs, tid, beg, end):
+    """the same from every record of the file: the definition"""
+    return [r for r in recs if extent(r)[0] == tid and extent(r)[1] < end and extent(r)[2] > beg]
+
+
+# ---------------------------------------------------------------------------------------------------------------- block tables and the case lists
+def table(total, size, c0=0, cuts=()):
+    """a block table for a stream of `total` bytes: blocks of `size` bytes, and a block boundary at every offset of `cuts` as well; the
+    compressed offsets start at c0 and rise by something that is not the blocks' length"""
+    starts = sorted(set(range(0, total, size)) | {c for c in cuts if 0 < c < total}) if total else []
+    uoff = starts + [total]
+    coff = [c0]
+    for a, b in zip(uoff, uoff[1:]):
+        coff.append(coff[-1] + 26 + (b - a) // 3)
+    if not starts:
+        coff = [c0]
+    return np.array(uoff, np.int64), np.array(coff, np.int64)
+
+
+HEADER = 321         # the bytes in front of the first record in the cases' streams: a BAM header of some length
+
+
+def one_call(recs):
+    return [(recs, HEADER)]
+
+
+def stream_len(calls):
+    return max([HEADER] + [so + sum(len(r) for r in recs) for recs, so in calls])
+
+
+def shape_cases():
+    """(name, n_ref, calls): the shapes of a record and of a file at which the bodies can go wrong"""
+    out = []
+    # every byte alignment: record 2 a + 1 starts at residue a mod 16 once the name of the one in front has been made as long as that takes
+    recs = []
+    for a in range(16):
+        cur = sum(len(r) for r in recs)
+        probe = rec(0, 100 + 3 * a, "20M", name=b"n")
+        recs.append(rec(0, 100 + 3 * a, "20M", name=b"n" * (1 + (a - cur - len(probe)) % 16)))
+        recs.append(rec(0, 101 + 3 * a, "5S17M2D3M", name=b"m" * (1 + a % 5)))
+    out.append(("alignments", 1, one_call(recs)))
+    # CIGARs around the lane group
+    recs = [unmapped(0, 10, 0, b"no_cigar")]
+    for n_ops in (1, 15, 16, 17, 33, 200):
+        recs.append(rec(0, 16000 + n_ops, many_ops(n_ops, 40), name=b"c%d" % n_ops))
+    recs.append(rec(0, 16300, [(1000 + i, "MN"[i % 2]) for i in range(33)], name=b"wide"))
+    out.append(("CIGAR lengths", 1, one_call(recs)))
+    # every operation, and CIGARs that consume no reference
+    recs = [rec(1, 500, c, name=c.encode()) for c in ("30M", "4S26M", "4H26M", "10M2I18M", "10M3D17M", "10M50N20M", "10=1X19=", "12M2P18M", "3S5M1I4=2D3X50N10M2P4M3S2H")]
+    recs += [rec(1, 600, "6S", name=b"only_s"), rec(1, 600, "5S6I", name=b"s_and_i"), rec(1, 16383, "4I", name=b"i_at_window_end"),
+             record(1, 16384, 37, 0, "4M", "ACGT", raw_ops=[5 << 4 | 9, 7 << 4 | 15], name=b"raw")]      # unassigned operation codes consume nothing
+    out.append(("operations", 3, one_call(recs)))
+    # placed unmapped records (flag 0x4 with a place: one base long whatever the CIGAR says), and records without a reference at the end
+    recs = [rec(0, 100, "30M", name=b"m0"), unmapped(0, 100, 4 | 8, b"placed"), rec(0, 16380, "30M", 4, name=b"flag4_with_cigar"), rec(0, 16380, "30M", name=b"its_twin"),
+            unmapped(0, 40000, 4, b"placed2"), rec(1, 5, "10M", name=b"m1"), unmapped(1, 5, 4, b"placed3"), unmapped(-1, -1, 4, b"u1"), unmapped(-1, -1, 0, b"u2"), unmapped(-1, 77, 4, b"u3")]
+    out.append(("unmapped, placed and not", 2, one_call(recs)))
+    # beg and end on either side of the bins' boundaries
+    recs = []
+    for k in (14, 17, 20, 23, 26):
+        e = 1 << k
+        recs += [rec(0, e - 10, "5M", name=b"below%d" % k), rec(0, e - 10, "10M", name=b"upto%d" % k), rec(0, e - 10, "11M", name=b"across%d" % k), rec(0, e - 1, "1M", name=b"last%d" % k),
+                 rec(0, e, "7M", name=b"at%d" % k), rec(0, e - 1, "2M", name=b"straddle%d" % k)]
+    recs += [rec(0, 0, "3M", name=b"zero"), rec(0, MAX_END - 5, "5M", name=b"to_the_end"), rec(0, MAX_END - 1, "1M", name=b"last_base"), unmapped(0, MAX_END - 1, 4, b"last_base_u"),
+             rec(0, 0, [(1 << 27, "N")] * 4, name=b"everything"), rec(1, (1 << 26) - 1, [(1, "M"), (1 << 26, "N"), (1, "M")], name=b"two_level1")]
+    out.append(("bin boundaries", 2, one_call(in_order(recs))))
+    # windows: a read over three, a gap of untouched windows, and the last window touched by a longer, earlier read
+    recs = [rec(0, 16000, "20M33000N20M", name=b"three_windows"), rec(0, 16390, "10M", name=b"second"), rec(0, 200000, "10M", name=b"after_a_gap"), rec(0, 200001, "40000M", name=b"long"),
+            rec(0, 200002, "5M", name=b"short_behind_long"), rec(2, 100000, "5M", name=b"far")]
+    out.append(("windows", 3, one_call(recs)))
+    # references without records at the start, in the middle and at the end
+    recs = [rec(1, 7, "9M"), rec(1, 7, "9M", 16), rec(3, 0, "1M"), rec(3, 70000, "9M")]
+    out.append(("empty references", 6, one_call(recs)))
+    out.append(("one record", 1, one_call([rec(0, 5, "7M")])))
+    out.append(("one placed unmapped record", 2, one_call([unmapped(1, 0, 4)])))
+    out.append(("one record without a reference", 2, one_call([unmapped()])))
+    out.append(("nothing", 3, []))
+    out.append(("nothing, no references", 0, []))
+    out.append(("only records without a reference, no references", 0, one_call([unmapped(), unmapped(-1, 5)])))
+    # the chunk rule: two records of one bin with a record of another bin between them
+    recs = [rec(0, 100, "20M", name=b"a1"), rec(0, 150, "20M20000N5M", name=b"b"), rec(0, 200, "20M", name=b"a2"), rec(0, 201, "20M", name=b"a3"), rec(0, 300, "20M20000N5M", name=b"b2"),
+            rec(0, 400, "20M", name=b"a4")]
+    out.append(("chunks", 1, one_call(recs)))
+    # several calls, with and without gaps between them
+    recs = in_order([rec(t, 1000 * k + 13 * t, "%dM" % (20 + k), name=b"r%d" % k) for t in range(3) for k in range(40)]) + [unmapped()] * 3
+    out.append(("three calls", 3, [(recs[:50], HEADER), (recs[50:51], HEADER + sum(len(r) for r in recs[:50])), (recs[51:], HEADER + sum(len(r) for r in recs[:51]))]))
+    out.append(("three calls with gaps", 3, [(recs[:50], HEADER + 5), (recs[50:51], HEADER + 70 + sum(len(r) for r in recs[:50])), (recs[51:], HEADER + 70000 + sum(len(r) for r in recs[:51]))]))
+    return out
+
+
+def tables_for(calls):
+    """(name, blk_uoff, blk_coff): the block tables every case runs with -- blocks shorter than a record, blocks of a few records, the largest
+    blocks, compressed offsets near 2^48, and blocks that end exactly where records do"""
+    total = stream_len(calls)
+    ends, u = [], 0
+    for recs, so in calls:
+        u = so
+        for r in recs:
+            u += len(r)
+            ends.append(u)
+    out = [("blocks of 37", table(total, 37)), ("blocks of 230", table(total, 230)), ("blocks of 65536", table(total, 65536)),
+           ("offsets near 2^48", table(total, 150, (1 << 48) - 26 * (total // 150 + 3) - total - 1)), ("records end at block ends", table(total, 500, 0, ends[::3])),
+           ("an empty block", (lambda t: (np.insert(t[0], 1, t[0][1]), np.insert(t[1], 1, t[1][1] - 1)))(table(total, 100)) if total > 100 else table(total, 100))]
+    return out
+
+
+def all_cases():
+    """(name, n_ref, calls, blk_uoff, blk_coff)"""
+    return [("%s, %s" % (name, tname), n_ref, calls, t[0], t[1]) for name, n_ref, calls in shape_cases() for tname, t in tables_for(calls)]
+
+
+def damaged_cases():
+    """(name, a damaged record of reference 0 near position 900, for a file of 3 references): each kind of damage of include/nabwa.h but the
+    order of the records, which depends on the record in front"""
+    good = rec(0, 900, "25M")
+    return [("block_size one too large", struct.pack("<I", len(good) - 4 + 1) + good[4:]), ("block_size one too small", struct.pack("<I", len(good) - 4 - 1) + good[4:]),
+            ("l_seq beyond the record", record(0, 900, 37, 0, "25M", "A" * 25, l_seq=26)), ("n_cigar_op beyond the record", record(0, 900, 37, 0, "25M", "A" * 25, n_cigar=15)),
+            ("fields beyond an unmapped record", record(0, 900, 0, 4, "*", "ACGT", l_seq=4000)), ("l_seq of 2^31 and more", record(0, 900, 37, 0, "25M", "A" * 25, l_seq=-5)),
+            ("a reference the header does not have", rec(3, 900, "25M")), ("a far reference", rec((1 << 31) - 1, 900, "25M")),
+            ("a negative position on a reference", rec(0, -1, "25M")), ("a very negative position", unmapped(0, -(1 << 31), 4)),
+            ("an end behind 2^29", rec(0, MAX_END - 10, "11M")), ("an end behind 2^29 by one D", rec(0, MAX_END - 10, "10M1D")), ("a placed unmapped record at 2^29", unmapped(0, MAX_END, 4)),
+            ("a huge N", rec(0, 900, [((1 << 28) - 1, "N")] * 3))]
+
+
+def good_records(n=60, seed=3):
+    """sound records of a file of 3 references: the first two thirds on reference 0 below position 900, the rest on reference 1"""
+    rng = np.random.default_rng(seed)
+    recs = []
+    for k in range(n):
+        t = 0 if k < 2 * n // 3 else 1
+        recs.append(rec(t, int(rng.integers(0, 900)), "%dM" % int(rng.integers(5, 60)), 16 * int(rng.integers(0, 2)), name=b"g" * int(rng.integers(1, 9))))
+    return in_order(recs)
+
+
+def random_records(n, seed, n_ref=4, span=300000):
+    """a seeded sorted file: reads of every length up to many windows, placed unmapped reads, an empty reference, reads without a reference"""
+    rng = np.random.default_rng(seed)
+    recs = []
+    for k in range(n):
+        t = int(rng.choice([0, 0, 0, 1, 3][:max(1, min(5, n_ref + 1))])) if n_ref > 3 else int(rng.integers(0, n_ref))
+        pos = int(rng.integers(0, span))
+        kind = int(rng.integers(0, 20))
+        nm = b"q%d" % k
+        if kind == 0:
+            recs.append(unmapped(t, pos, 4, nm))
+        elif kind == 1:
+            recs.append(unmapped(-1, -1, 4, nm))
+        elif kind < 4:
+            recs.append(rec(t, pos, [(int(rng.integers(10, 50)), "M"), (int(rng.integers(100, 70000)), "N"), (int(rng.integers(10, 50)), "M")], 0, nm))
+        else:
+            recs.append(rec(t, pos, "%dM" % int(rng.integers(20, 150)), 16 * int(rng.integers(0, 2)), nm))
+    return in_order(recs)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the CPU builds
+def _build(out, srcs, deps, flags):
+    if os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs + deps):
+        return out
+    subprocess.run(["g++", "-std=c++17", "-I" + EMU_DIR, "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas"] + flags + srcs + ["-o", out, "-lpthread"], check=True)
+    return out
+
+
+BODY = [os.path.join(CSRC, "bai_body.hpp"), os.path.join(T.ROOT, "include", "nabwa.h")]
+
+
+def load_emu():
+    """the bodies as a library"""
+    lib = C.CDLL(_build(os.path.join(EMU_DIR, "libbai_emu.so"), [os.path.join(EMU_DIR, "bai_emu.cpp")], BODY, ["-O2", "-fPIC", "-shared"]))
+    P = C.c_void_p
+    lib.emu_bai_create.restype = P
+    lib.emu_bai_create.argtypes = [C.c_int32]
+    lib.emu_bai_destroy.argtypes = [P]
+    lib.emu_bai_destroy.restype = None
+    lib.emu_bai_clear.argtypes = [P]
+    lib.emu_bai_clear.restype = None
+    lib.emu_bai_add.restype = C.c_int64
+    lib.emu_bai_add.argtypes = [P, C.c_int64, P, P, C.c_int64, C.c_int]
+    lib.emu_bai_finish.restype = C.c_int64
+    lib.emu_bai_finish.argtypes = [P, C.c_int64, P, P, P, C.c_int64, P]
+    return lib
+
+
+def build_main():
+    """the stand-alone program, under AddressSanitizer and UndefinedBehaviorSanitizer"""
+    return _build(os.path.join(EMU_DIR, "bai_main_asan"), [os.path.join(EMU_DIR, "bai_main.cpp"), os.path.join(EMU_DIR, "bai_emu.cpp")], BODY,
+                  ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"])
+
+
+class Emu:
+    """a handle of the emulation, used as nabwa.Bai is"""
+
+    def __init__(self, lib, n_ref, n_blocks=3):
+        self.lib, self.n_blocks = lib, n_blocks
+        self.h = lib.emu_bai_create(n_ref)
+
+    def add(self, recs, stream_off=0):
+        """-> -1, or the lowest damaged record (and nothing added)"""
+        data, off = B.pack(recs)
+        data = data if len(data) else np.zeros(1, np.uint8)
+        bad = int(self.lib.emu_bai_add(self.h, len(recs), T.ptr(data), T.ptr(off), stream_off, self.n_blocks))
+        assert bad >= -1, "the emulation's own check %d" % bad
+        return bad
+
+    def finish(self, blk_uoff, blk_coff):
+        u, c = np.ascontiguousarray(blk_uoff, np.int64), np.ascontiguousarray(blk_coff, np.int64)
+        stats = np.zeros(N_STATS, np.uint64)
+        size = int(self.lib.emu_bai_finish(self.h, u.size - 1, T.ptr(u), T.ptr(c), None, 0, T.ptr(stats)))
+        out = np.zeros(size, np.uint8)
+        assert self.lib.emu_bai_finish(self.h, u.size - 1, T.ptr(u), T.ptr(c), T.ptr(out), size, T.ptr(stats)) == size
+        assert self.lib.emu_bai_finish(self.h, u.size - 1, T.ptr(u), T.ptr(c), T.ptr(out), size - 1, T.ptr(stats)) == -2
+        return out.tobytes(), stats
+
+    def clear(self):
+        self.lib.emu_bai_clear(self.h)
+
+    def close(self):
+        self.lib.emu_bai_destroy(self.h)
+
+
+def describe(data):
+    """a .bai as text, for the message of a failed comparison"""
+    try:
+        refs, n_no_coor = parse_bai(data)
+    except Exception as e:      # noqa: BLE001
+        return "not a whole .bai (%s): %s" % (e, data[:64].hex())
+    lines = []
+    for t, (bins, lin) in enumerate(refs):
+        lines.append("ref %d: %s | lin %s" % (t, " ".join("%d:%s" % (b, ",".join("%x-%x" % c for c in cs)) for b, cs in bins.items()), " ".join("%x" % v for v in lin[:12])))
+    return "\n".join(lines[:8]) + "\nno_coor %d" % n_no_coor
+
+
+def assert_same(got, want, what=""):
+    (data, stats), (wdata, wstats) = got, want
+    if data != wdata:
+        raise AssertionError("%s: another file (%d bytes, expected %d)\ngot\n%s\nexpected\n%s" % (what, len(data), len(wdata), describe(data), describe(wdata)))
+    for k, (a, b) in enumerate(zip(stats, wstats)):
+        assert int(a) == int(b), "%s: stats[%s] is %d, not %d" % (what, STAT_NAMES[k], int(a), int(b))
+
+
+def write_case_file(path, items):
+    """the cases as data for tests/emu/bai_main.cpp.  items: (n_ref, [(records, stream_off, expected damaged index or -1)], blk_uoff, blk_coff,
+    expected file, expected stats)"""
+    with open(path, "wb") as f:
+        f.write(struct.pack("<qq", len(items), N_STATS))
+        for n_ref, calls, blk_uoff, blk_coff, data, stats in items:
+            f.write(struct.pack("<qq", n_ref, len(calls)))
+            for recs, stream_off, bad in calls:
+                raw, off = B.pack(recs)
+                f.write(struct.pack("<qqqq", len(recs), len(raw), stream_off, bad))
+                f.write(off.astype("<i8").tobytes())
+                f.write(raw.tobytes())
+            f.write(struct.pack("<q", len(blk_uoff) - 1))
+            f.write(np.asarray(blk_uoff, "<i8").tobytes())
+            f.write(np.asarray(blk_coff, "<i8").tobytes())
+            f.write(struct.pack("<q", len(data)))
+            f.write(data)
+            f.write(np.asarray(stats, "<u8").tobytes())

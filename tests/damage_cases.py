@@ -23,7 +23,7 @@ NIBBLES = "=ACMGRSVTWYHKDBN"
 DEFAULT_OPT = dict(n_pos=25, min_mapq=0, exclude_flags=0xF04, require_flags=0)
 LENGTHS = (1, 2, 3, 15, 16, 17, 63, 64, 65, 300)
 N_POSS = (1, 2, 25, 256)
-GOLDEN_SAMS = ("se_default", "se_adna", "se_q20", "pe_default", "pe150_default")
+GOLDEN_SAMS = ("se_default", "se_adna", "se_q20", "pe_default", "pe150_default", "peshort_default")
 
 
 def opt_of(**kw):

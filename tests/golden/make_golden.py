@@ -9,6 +9,7 @@ reference's outputs for them (.sai from `aln`, SAM from `samse`, and function-le
 vectors for the rank / SA / DP primitives).  No reference source text is stored.
 
 Usage:  python tests/golden/make_golden.py
+        python tests/golden/make_golden.py pe_chain | pe_chain150 | pe_chainshort | sw_rescue     (one fixture set only)
 """
 import ctypes as C
 import os
@@ -703,22 +704,234 @@ def make_pe_reads(rng, contigs, L=100, mu=300, sd=25, heavy=False):
     return [pairs[i] for i in order]
 
 
+SHORT_EDGE_INSERTS = (30, 50, 76, 77, 120)
+SHORT_EDGE_KINDS = ["edge_%s_%s" % (c, a) for c in ("chr1", "chr2", "chr3") for a in ("s0", "s1", "e0", "e1")] + ["edgedisc_end", "edgedisc_start"]
+
+
+def make_short_pe_reads(rng, contigs, L=76):
+    """Read pairs of the toy genome the way an ancient-DNA or capture library gives them: fragments of 25 - 151 bases read with
+    L = 76 bases from both ends, so the mates overlap or are one stretch of genome read from both strands (same position, opposite
+    strands).  Kinds: contained (insert < L, both reads the whole fragment), overlapping (insert L .. 2L - 1), unequal (one mate cut
+    at its 3' end), damaged (substitutions; 9+ in one mate leave it unmapped), gapped (an indel in one mate of an overlapping pair),
+    rescue (read 1 in chr2's diverged copy, read 2 the chr1 version of its place: the rescued mate overlaps its anchor; every other
+    pair is the mirror image, a reverse-strand anchor with the window to its left), edges
+    (fragments at the first / last two bases of every contig), edge-discordant (an anchor whose rescue window runs off either end
+    of the text, its mate from another contig)."""
+    g = dict(contigs)
+    pairs = []
+
+    def subs(s, n, lo=0, hi=None):
+        s = list(s)
+        hi = len(s) if hi is None else hi
+        for p in rng.choice(np.arange(lo, hi), n, replace=False):
+            s[p] = "ACGT"[("ACGT".index(s[p]) + 1 + int(rng.integers(0, 3))) % 4]
+        return "".join(s)
+
+    def add(tag, r1, r2):
+        if rng.integers(0, 2):                       # which end is read 1 is arbitrary
+            r1, r2 = r2, r1
+        pairs.append(("s%04d_%s" % (len(pairs), tag), r1, r2))
+
+    def frag(contig, start, isize):
+        f = g[contig][start:start + isize] if start >= 0 else ""
+        return f if len(f) == isize and "N" not in f else None
+
+    def place(isize):
+        while True:
+            contig = "chr1" if rng.random() < 0.6 else "chr2"
+            start = int(rng.integers(0, len(g[contig]) - isize - 4))
+            if frag(contig, start, isize + 4):
+                return contig, start
+
+    def n_extra(w1, w2):
+        # 2 - 4 substitutions on top of the copy's own differences, five differences from chr2 in all where that is possible: one
+        # more than `aln` allows at 76 bases, so that only the mate rescue can find the place next to the anchor
+        ndiv = sum(a != b for a, b in zip(w1, w2))
+        return int(rng.integers(max(2, min(4, 5 - ndiv)), 5))
+
+    def ends(f):                                     # reads of min(insert, L) bases
+        return f[:L], revcomp(f[-L:])
+
+    n_kind = {"contained": 280, "overlap": 64, "unequal": 36, "damaged": 36, "gapped": 24, "rescue": 150}
+    for kind, n in n_kind.items():
+        made = 0
+        while made < n:
+            if kind == "contained":
+                isize = int(np.clip(rng.normal(50, 14), 25, L - 1))
+            elif kind == "overlap":
+                isize = (L, L + 1)[made % 2] if made < 8 else int(rng.integers(L, 2 * L))
+            elif kind == "gapped":
+                isize = int(rng.integers(L + 4, 2 * L - 10))
+            else:
+                isize = int(rng.integers(30, 2 * L))
+            contig, start = place(isize)
+            r1, r2 = ends(frag(contig, start, isize))
+            if kind == "unequal":                     # one mate cut at its 3' end by 1 .. 15 bases, down to 20 bases
+                cut = int(rng.integers(1, 16))
+                if rng.integers(0, 2):
+                    r1 = r1[:max(20, len(r1) - cut)]
+                else:
+                    r2 = r2[:max(20, len(r2) - cut)]
+            elif kind == "damaged":
+                if made % 2:                          # too many differences for aln: the end stays unmapped (quirk F4)
+                    r2 = subs(r2, int(rng.integers(9, 14)))
+                    if rng.integers(0, 2):
+                        r1 = subs(r1, 1)
+                else:
+                    k1, k2 = int(rng.integers(0, 3)), int(rng.integers(0, 3))
+                    if k1 + k2 == 0:
+                        k1 = 1
+                    r1, r2 = subs(r1, k1), subs(r2, k2)
+            elif kind == "gapped":                    # a 1 - 2 base indel in one mate, at least 12 bases from either end
+                d = int(rng.integers(1, 3))
+                p = int(rng.integers(12, L - 12 - d))
+                which = int(rng.integers(0, 2))
+                src = frag(contig, start, isize)
+                if which:
+                    src = revcomp(src)                # the fragment as this mate's strand reads it
+                if rng.integers(0, 2):                # deletion from the read: it spans L + d bases of the genome
+                    x = src[:p] + src[p + d:L + d]
+                else:
+                    x = (src[:p] + "".join("ACGT"[i] for i in rng.integers(0, 4, d)) + src[p:])[:L]
+                if which:
+                    r2 = x
+                else:
+                    r1 = x
+            elif kind == "rescue":
+                # a rescued mate is clipped where it overlaps its anchor (the window starts past it) and every clipped base costs it
+                # as much as a third of a mismatch (bwape.c:584-600): only overlaps of a few bases are accepted, so half the inserts
+                # are drawn from the top of the range
+                contig, isize = "chr2", int(rng.integers(80, 151)) if made % 4 < 2 else int(rng.integers(140, 151))
+                start = int(rng.integers(8000 + L - isize, 10000 - isize + 1))
+                e2 = start + isize                    # fragment end on chr2; read 2's window lo..e2 lies inside the copy 8000..10000
+                lo = e2 - L
+                f = frag(contig, start, isize)
+                if f is None or lo < 8000 or e2 > 10000:
+                    continue
+                r1 = f[:L]
+                if start >= 8000 and g["chr1"][5000 + start - 8000:][:L] == r1:      # read 1 has to be told from chr1's copy
+                    continue
+                w1 = g["chr1"][5000 + lo - 8000: 5000 + e2 - 8000]
+                w2 = g["chr2"][lo:e2]
+                if sum(a != b for a, b in zip(w1, w2)) < 1:
+                    continue
+                r2f = list(w1)
+                cand = [i for i in range(0, L - 34) if w1[i] == w2[i]]        # read 2 is the reverse complement: its seed is the window's tail
+                for p in rng.choice(cand, n_extra(w1, w2), replace=False):
+                    r2f[p] = "ACGT"[("ACGT".index(r2f[p]) + 1 + int(rng.integers(0, 3))) % 4]
+                r2 = revcomp("".join(r2f))
+                if made % 2:
+                    # the mirror image: the anchor is the reverse-strand read at the fragment's right end, the forward-strand read at
+                    # its left end carries the chr1 version (its seed is the window's head), so the rescue window lies to the left
+                    start = int(rng.integers(8000, 10000 - L + 1))
+                    e2 = start + isize
+                    f = frag(contig, start, isize)
+                    if f is None:
+                        continue
+                    r1 = revcomp(f[-L:])
+                    if e2 <= 10000 and g["chr1"][5000 + e2 - L - 8000: 5000 + e2 - 8000] == f[-L:]:
+                        continue
+                    w1 = g["chr1"][5000 + start - 8000: 5000 + start - 8000 + L]
+                    w2 = g["chr2"][start:start + L]
+                    if w1 == w2:
+                        continue
+                    r2f = list(w1)
+                    cand = [i for i in range(34, L) if w1[i] == w2[i]]
+                    for p in rng.choice(cand, n_extra(w1, w2), replace=False):
+                        r2f[p] = "ACGT"[("ACGT".index(r2f[p]) + 1 + int(rng.integers(0, 3))) % 4]
+                    r2 = "".join(r2f)
+            add(kind, r1, r2)
+            made += 1
+    # fragments that start at bases 0 and 1 and end at the last and last-but-one base of every contig (chr3's end is the text's)
+    for contig in ("chr1", "chr2", "chr3"):
+        n_c = len(g[contig])
+        for isize in SHORT_EDGE_INSERTS:
+            for anchor, start in (("s0", 0), ("s1", 1), ("e0", n_c - isize), ("e1", n_c - 1 - isize)):
+                add("edge_%s_%s" % (contig, anchor), *ends(frag(contig, start, isize)))
+    # anchors whose rescue window is cut by the end (forward strand, ending < L bases before it) or the start (reverse strand,
+    # starting inside the first L bases) of the text; the mate lies on another contig
+    for t, d in enumerate((0, 1, 9, 30, 50, 61, 70, L - 1)):
+        l_mate = (L, 40, 25, L)[t % 4]
+        for kind in ("edgedisc_end", "edgedisc_start"):
+            while True:
+                other = "chr2" if rng.random() < 0.5 else ("chr1" if kind == "edgedisc_end" else "chr3")
+                m = frag(other, int(rng.integers(200, len(g[other]) - 200)), l_mate)
+                if m:
+                    break
+            if rng.integers(0, 2):
+                m = revcomp(m)
+            n3 = len(g["chr3"])
+            a = g["chr3"][n3 - d - L:n3 - d] if kind == "edgedisc_end" else revcomp(g["chr1"][d:d + L])
+            add(kind, a, m)
+    order = rng.permutation(len(pairs))
+    return [pairs[i] for i in order]
+
+
 PE_F = ("type", "strand", "n_mm", "n_gapo", "n_gape", "score", "sa", "c1", "c2", "pos", "mapQ", "seQ", "extra_flag", "n_cigar",
         "nm", "n_multi", "len")
 
 
-def make_pe_chain(lib=None, tag="", L=100, mu=300, sd=25, heavy=False, seed=4242):
+def check_short_set(out, pairs, L=76):
+    """What the short-insert set has to hold for its tests to mean anything: conditions on what the REFERENCE returned for these
+    inputs (no product code has run).  Prints the counts."""
+    f, cg = out["f_sampe"], out["cig_sampe"]
+    n = len(pairs)
+    a, c = f[0::2], f[1::2]
+    both = (a[:, 0] != 0) & (c[:, 0] != 0)
+    same_pos = int((both & (a[:, 9] == c[:, 9])).sum())
+    attempted = int((both & ((a[:, 12] & 2) == 0) & ((a[:, 10] >= 17) | (c[:, 10] >= 17))).sum())
+    sw = [r for r in range(2 * n) if f[r][0] == 3]
+    sw_clipped = [r for r in sw if any(x >> 14 == 3 for x in cg[r][:f[r][13]])]
+    unequal = int((both & (a[:, 16] != c[:, 16])).sum())
+    gapped = 0
+    for r in range(2 * n):
+        m = f[r ^ 1]
+        if f[r][0] and m[0] and f[r][3] > 0 and f[r][13] > 1 and f[r][9] < m[9] + m[16] and m[9] < f[r][9] + f[r][16]:
+            gapped += 1
+    kinds = {}
+    for i, (name, _, _) in enumerate(pairs):
+        k = name.split("_", 1)[1]
+        kinds.setdefault(k, [0, 0])
+        kinds[k][0] += 1
+        kinds[k][1] += bool(both[i])
+    tlen_le_L = 0
+    for i in range(n):
+        if both[i]:
+            lo, hi = min(a[i][9], c[i][9]), max(a[i][9] + a[i][16], c[i][9] + c[i][16])
+            tlen_le_L += hi - lo <= L
+    sw_fwd = sum(1 for r in sw if f[r][1] == 0)       # rescued to the left of a reverse-strand anchor (__set_left_coor)
+    print("short set: MATESW on the forward strand %d, on the reverse strand %d" % (sw_fwd, len(sw) - sw_fwd))
+    print("short set: %d pairs; same position %d; both mapped, not proper, one end mapQ >= 17: %d; MATESW %d (soft-clipped %d); "
+          "unequal lengths, both mapped %d; gapped with overlapping mate %d; span <= %d: %d; singletons %d; ii_sampe %s; ii_hist %s"
+          % (n, same_pos, attempted, len(sw), len(sw_clipped), unequal, gapped, L, tlen_le_L,
+             int(((a[:, 0] != 0) ^ (c[:, 0] != 0)).sum()), out["ii_sampe"].tolist(), out["ii_hist"].tolist()))
+    print("short set kinds (pairs, both ends mapped):", {k: tuple(v) for k, v in sorted(kinds.items())})
+    assert same_pos >= 200, same_pos
+    assert attempted >= 150, attempted
+    assert len(sw) >= 3 and len(sw_clipped) == len(sw), (len(sw), len(sw_clipped))
+    assert sw_fwd >= 3 and len(sw) - sw_fwd >= 3, (sw_fwd, len(sw))        # both window constructions accept rescues
+    assert unequal >= 20, unequal
+    assert gapped >= 10, gapped
+    assert out["ii_hist"][3] == 1, out["ii_hist"]
+    assert out["ii_sampe"][3] == L, out["ii_sampe"]
+    for k in SHORT_EDGE_KINDS:
+        assert kinds[k][1] >= 1, (k, kinds[k])
+    assert kinds["edgedisc_end"][0] >= 6 and kinds["edgedisc_start"][0] >= 6 and kinds["unequal"][0] >= 30
+
+
+def make_pe_chain(lib=None, tag="", L=100, mu=300, sd=25, heavy=False, seed=4242, short=False):
     """The paired-end chain (bam2bam.c:683-811 / bwape.c:295-425,519-633 / bwase.c:356-423) on toy read pairs:
     reads_pe_[12].fq, pe_[12].sai, pe_default.sam (the reference's `sampe`), vectors_pe_chain.npz (state of every end
     after pass 1 and after pass 2 under three insert-size estimates: sampe's own, bam2bam's histogram one, none).
     tag "150": the same for 2 x 150 bp pairs with config 3's error load (files reads_pe150_[12].fq, pe150_[12].sai,
-    pe150_default.sam, vectors_pe150_chain.npz)."""
+    pe150_default.sam, vectors_pe150_chain.npz).  short: the short-insert set of make_short_pe_reads (tag "short": files
+    reads_peshort_[12].fq.gz, peshort_[12].sai, peshort_default.sam.gz, vectors_peshort_chain.npz), with check_short_set on the result."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import nabwa_testlib as T
     if lib is None:
         lib = C.CDLL(REFLIB)
     rng = np.random.default_rng(seed)
-    pairs = make_pe_reads(rng, read_genome(), L=L, mu=mu, sd=sd, heavy=heavy)
+    pairs = make_short_pe_reads(rng, read_genome(), L=L) if short else make_pe_reads(rng, read_genome(), L=L, mu=mu, sd=sd, heavy=heavy)
     fq = [os.path.join(HERE, "reads_pe%s_%d.fq" % (tag, e)) for e in (1, 2)]
     sai = [os.path.join(HERE, "pe%s_%d.sai" % (tag, e)) for e in (1, 2)]
     for e in range(2):
@@ -805,7 +1018,17 @@ def make_pe_chain(lib=None, tag="", L=100, mu=300, sd=25, heavy=False, seed=4242
         print("pe chain [%s] ii=%s  types=%s  FPP=%d  MATESW=%d" % (mode, ii, np.bincount(fin[0][:, 0], minlength=4),
               int((fin[0][:, 12] & 2).astype(bool).sum()), int((fin[0][:, 0] == 3).sum())))
     check_against_sampe(T, out, read_genome(), pairs, sam_path)
+    if short:
+        check_short_set(out, pairs, L)
     np.savez_compressed(os.path.join(HERE, "vectors_pe%s_chain.npz" % tag), **out)
+    if short:
+        # this set's text files are stored gzip-compressed (as the colour-space set's are): reads_peshort_[12].fq.gz and
+        # peshort_default.sam.gz; no file name or time stamp in the header, so that the bytes are the same on every run
+        import gzip
+        for p in fq + [sam_path]:
+            with open(p, "rb") as fi, open(p + ".gz", "wb") as fo, gzip.GzipFile(filename="", mode="wb", compresslevel=9, fileobj=fo, mtime=0) as z:
+                z.write(fi.read())
+            os.remove(p)
 
 
 def check_against_sampe(T, out, contigs, pairs, sam_path):
@@ -837,6 +1060,8 @@ if __name__ == "__main__":
         make_pe_chain()
     elif len(sys.argv) > 1 and sys.argv[1] == "pe_chain150":
         make_pe_chain(tag="150", L=150, mu=400, sd=40, heavy=True, seed=150150)
+    elif len(sys.argv) > 1 and sys.argv[1] == "pe_chainshort":
+        make_pe_chain(tag="short", L=76, seed=7676, short=True)
     elif len(sys.argv) > 1 and sys.argv[1] == "sw_rescue":
         make_sw_rescue_vectors()
     else:

@@ -2,6 +2,7 @@
 CPU oracle (oracle/liboracle.so) and -- when built -- the compiled reference
 (oracle/_ref/libbwaref.so).  Test infrastructure only."""
 import ctypes as C
+import gzip
 import os
 import subprocess
 
@@ -62,9 +63,19 @@ def default_opt():
     return o
 
 
+def stored(path):
+    """the file as tests/golden holds it: `path`, or `path`.gz where the fixture is stored compressed (the short-insert set's FASTQ and SAM)"""
+    return path if os.path.exists(path) or not os.path.exists(path + ".gz") else path + ".gz"
+
+
+def open_text(path, mode="rt"):
+    p = stored(path)
+    return gzip.open(p, mode) if p.endswith(".gz") else open(p, mode.replace("t", ""))
+
+
 def read_fastq(path):
     out = []
-    with open(path) as f:
+    with open_text(path) as f:
         while True:
             h = f.readline()
             if not h:
@@ -143,7 +154,7 @@ def read_sai(path):
 
 def parse_sam(path):
     recs = []
-    for line in open(path):
+    for line in open_text(path):
         if line.startswith("@"):
             continue
         f = line.rstrip("\n").split("\t")

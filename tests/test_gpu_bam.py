@@ -121,8 +121,8 @@ def test_se_bam_records_match_the_reference_sam(name):
     ix.close()
 
 
-def pe_records():
-    fq = [T.read_fastq(os.path.join(T.GOLDEN, "reads_pe_%d.fq" % e)) for e in (1, 2)]
+def pe_records(tag=""):
+    fq = [T.read_fastq(os.path.join(T.GOLDEN, "reads_pe%s_%d.fq" % (tag, e))) for e in (1, 2)]
     recs = []
     for i in range(len(fq[0])):
         a, b = fq[0][i], fq[1][i]
@@ -158,6 +158,43 @@ def test_pe_bam_records_match_the_reference_sam():
         assert (g["seq"], g["qual"]) == (w["seq"], w["qual"]), r
         assert g["tags"] == w["tags"], (r, g["tags"], w["tags"])
     assert mp[0] == sum(1 for w in sam if w["tags"].get("XT") == "M") and mp[1] == 0
+    ix.close()
+
+
+def test_pe_bam_records_match_the_reference_sam_on_short_inserts():
+    """the short-insert set (make_golden.py pe_chainshort): 25 - 151 bp fragments read with 76 bases, so 318 pairs have both ends at
+    one position and the mates often differ in length.  (1) the front-end's histogram estimate is the reference's, whose low bound
+    is 1 here; (2) under sampe's estimate (low bound 76, the read length) every field of every record is what `sampe` printed:
+    TLEN, PNEXT and the flags of mates at one position, soft-clipped rescued mates that overlap their anchor"""
+    L = bind()
+    opt, _ = T.read_sai(os.path.join(T.GOLDEN, "peshort_1.sai"))
+    sam = T.parse_sam(os.path.join(T.GOLDEN, "peshort_default.sam"))
+    v = np.load(os.path.join(T.GOLDEN, "vectors_peshort_chain.npz"))
+    ix = nabwa.Index.load(T.TOY, 0, True, True)
+    recs, n_pairs = pe_records("short")
+    cuts = [recs[:2 * 101], recs[2 * 101:2 * 430], recs[2 * 430:]]          # unequal batches, cut between pairs
+    out, ii, (tot, mp) = run_batches(L, ix, opt, cuts)
+    iv = v["ii_hist"]
+    assert iv[3] == 1
+    assert (ii.avg, ii.std, ii.ap_prior, ii.low, ii.high, ii.high_bayesian) == tuple(iv)
+    iv = v["ii_sampe"]
+    assert iv[3] == 76
+    blob = np.frombuffer(b"\0" + bytes(8) + bytes(nabwa.IsizeInfo(iv[0], iv[1], iv[2], int(iv[3]), int(iv[4]), int(iv[5]))), np.uint8).copy()
+    out, ii, (tot, mp) = run_batches(L, ix, opt, cuts, table_blob=blob)
+    assert len(out) == len(sam) == 2 * n_pairs
+    same_pos = 0
+    for r, (g, w) in enumerate(zip(out, sam)):
+        assert g["name"] == w["name"].split("/")[0]
+        assert g["flag"] == w["flag"], (r, g["flag"], w["flag"])
+        assert (g["rname"], g["pos"], g["rnext"], g["pnext"], g["tlen"]) == (w["rname"], w["pos"], w["rnext"], w["pnext"], w["tlen"]), r
+        assert (g["mapq"], g["cigar"]) == (w["mapq"], w["cigar"]), r
+        assert (g["seq"], g["qual"]) == (w["seq"], w["qual"]), r
+        assert g["tags"] == w["tags"], (r, g["tags"], w["tags"])
+        same_pos += not (w["flag"] & 12) and w["rnext"] == "=" and w["pos"] == w["pnext"]
+    assert same_pos >= 2 * 200
+    n_sw = sum(1 for w in sam if w["tags"].get("XT") == "M")
+    assert n_sw >= 3 and mp[0] == n_sw and mp[1] == 0
+    assert tot[0] >= 150                                                     # the pairs bwa_paired_sw1 attempts
     ix.close()
 
 

@@ -216,17 +216,17 @@ def pe_fields(r):
     return se_fields(r.se) + (r.extra_flag, r.m_seqid, r.am, r.mapQ_paired, r.m_rpos, r.isize)
 
 
-def run_pe(ix, monkeypatch, mode):
+def run_pe(ix, monkeypatch, mode, tag="150"):
     set_mode(monkeypatch, mode)
-    fq = [T.read_fastq(os.path.join(T.GOLDEN, "reads_pe150_%d.fq" % e)) for e in (1, 2)]
-    sai = [T.read_sai(os.path.join(T.GOLDEN, "pe150_%d.sai" % e)) for e in (1, 2)]
+    fq = [T.read_fastq(os.path.join(T.GOLDEN, "reads_pe%s_%d.fq" % (tag, e))) for e in (1, 2)]
+    sai = [T.read_sai(os.path.join(T.GOLDEN, "pe%s_%d.sai" % (tag, e))) for e in (1, 2)]
     n = len(fq[0])
     inter = [fq[e][i] for i in range(n) for e in range(2)]
     hits = [sai[e][1][i] for i in range(n) for e in range(2)]
     seq, rseq, off, full = T.encode_reads(inter)
     opt = sai[1][0]
     recs, _ = ix.pe_posn(opt, off, full, hits, nabwa.srand48_state(11))
-    iv = np.load(os.path.join(T.GOLDEN, "vectors_pe150_chain.npz"))["ii_sampe"]
+    iv = np.load(os.path.join(T.GOLDEN, "vectors_pe%s_chain.npz" % tag))["ii_sampe"]
     ii = nabwa.IsizeInfo(iv[0], iv[1], iv[2], int(iv[3]), int(iv[4]), int(iv[5]))
     before = nabwa.finish_counts()
     ix.pe_finish(opt, nabwa.pe_opt_default(), ii, seq, rseq, off, hits, recs)
@@ -234,9 +234,12 @@ def run_pe(ix, monkeypatch, mode):
     return recs, 2 * n, [a - b for a, b in zip(after, before)]
 
 
-def test_pe_chain_is_the_same_on_the_device_path(ix, monkeypatch):
-    host, n, moved_host = run_pe(ix, monkeypatch, None)
-    gpu, _, moved_gpu = run_pe(ix, monkeypatch, "gpu")
+@pytest.mark.parametrize("tag", ["150", "short"])
+def test_pe_chain_is_the_same_on_the_device_path(ix, monkeypatch, tag):
+    """tag "short": the short-insert set (make_golden.py pe_chainshort) -- soft-clipped rescued mates that overlap their anchor,
+    mates at one position, mates of unequal length"""
+    host, n, moved_host = run_pe(ix, monkeypatch, None, tag)
+    gpu, _, moved_gpu = run_pe(ix, monkeypatch, "gpu", tag)
     bad = [(i, pe_fields(host[i]), pe_fields(gpu[i])) for i in range(n) if pe_fields(host[i]) != pe_fields(gpu[i])]
     assert not bad, (len(bad), bad[:3])
     ends = [host[i].se for i in range(n)]
@@ -245,14 +248,20 @@ def test_pe_chain_is_the_same_on_the_device_path(ix, monkeypatch):
     assert sum(1 for s in ends if s.type == 3) > 0                                           # and rescued mates: MD / NM without a refinement
     assert moved_host[:3] == [0, 0, 0] and moved_gpu[:3] == [jobs, mapped, 1]
     # and both are what the reference's sampe printed
-    sam = T.parse_sam(os.path.join(T.GOLDEN, "pe150_default.sam"))
-    for r, w in enumerate(sam):
-        s = gpu[r].se
-        assert s.flag == w["flag"], r
-        if s.type == 0:
-            continue
-        assert (T.cigar16_str(s.cigar[:s.n_cigar]) if s.n_cigar else "%dM" % s.len) == w["cigar"] and s.rpos == w["pos"], r
-        assert w["tags"]["MD"] == s.md.decode() and w["tags"]["NM"] == s.nm, r
+    sam = T.parse_sam(os.path.join(T.GOLDEN, "pe%s_default.sam" % tag))
+    assert len(sam) == n
+    for recs in (host, gpu):
+        for r, w in enumerate(sam):
+            s = recs[r].se
+            assert s.flag == w["flag"], r
+            if tag == "short" and (s.type or recs[r ^ 1].se.type):      # mates at one position: the mate fields and the template length too
+                assert (recs[r].m_rpos, recs[r].isize) == (w["pnext"], w["tlen"]), r
+            if s.type == 0:
+                continue
+            assert (T.cigar16_str(s.cigar[:s.n_cigar]) if s.n_cigar else "%dM" % s.len) == w["cigar"] and s.rpos == w["pos"], r
+            assert w["tags"]["MD"] == s.md.decode() and w["tags"]["NM"] == s.nm, r
+    if tag == "short":
+        assert sum(1 for s in ends if s.type == 3 and any(c >> 14 == 3 for c in s.cigar[:s.n_cigar])) == 26     # the set's rescues, every one soft-clipped
 
 
 def test_md_over_the_field_is_ecap_under_both_settings(ix, monkeypatch):

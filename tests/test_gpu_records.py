@@ -252,3 +252,185 @@ def test_pe_chain_at_150bp_with_indels_and_discordant_pairs(ref):
     assert attempts >= 40, attempts
     assert sum(1 for i in range(len(reads)) if want[i].n_cigar > 1) >= 20          # gapped reads went through bwa_refine_gapped
     ix.close()
+
+
+def make_short_insert_pairs(n_pairs, seed, L=76):
+    """Pairs of an ancient-DNA / capture library off the toy genome: fragments of 25 - 151 bases read with L = 76 bases from both
+    ends, so the mates overlap or are one stretch read from both strands (one position, opposite strands).  Of every 20 pairs:
+    9 contained (insert < L, both reads the whole fragment), 3 overlapping (insert L .. 2L - 1; L and L + 1 exactly come first),
+    1 unequal (one mate cut at its 3' end by 1 - 15 bases, down to 20), 1 damaged (1 - 2 substitutions, or 9+ in one mate: unmapped),
+    1 gapped (a 1 - 2 base indel >= 12 bases from either end of one mate of an overlapping pair), 3 rescue (read 1 in chr2's diverged
+    copy of chr1:5000-7000 at chr2:8000-10000, read 2 the chr1 version of its place with 2 - 4 more substitutions outside the seed;
+    inserts 80 - 150, so a rescued mate overlaps its anchor), 1 edge (fragments at the first / last two bases of a contig, inserts
+    30, 50, 76, 77, 120), 1 edge-discordant (a forward anchor ending < L bases before the end of the text or a reverse anchor
+    starting inside its first L bases, the mate from another contig: the rescue window's clamps at l_pac and 0)"""
+    rng = np.random.default_rng(seed)
+    g = dict(T.read_fasta(T.TOY + ".fa"))
+    comp = str.maketrans("ACGTN", "TGCAN")
+    rc = lambda s: s[::-1].translate(comp)
+    sub1 = lambda c: "ACGT"[("ACGT".index(c) + 1 + int(rng.integers(0, 3))) % 4]
+
+    def subs(s, n, lo=0, hi=None):
+        s = list(s)
+        for p in rng.choice(np.arange(lo, len(s) if hi is None else hi), n, replace=False):
+            s[p] = sub1(s[p])
+        return "".join(s)
+
+    def n_extra(w1, w2):
+        # five differences from chr2 in all where 2 - 4 more allow it: one more than the search takes at 76 bases, so only the rescue finds it
+        return int(rng.integers(max(2, min(4, 5 - sum(x != y for x, y in zip(w1, w2)))), 5))
+
+    def frag(isize, contig=None, start=None):
+        while True:
+            c = contig or ("chr1" if rng.random() < 0.6 else "chr2")
+            p = int(rng.integers(0, len(g[c]) - isize - 4)) if start is None else start
+            f = g[c][p:p + isize]
+            if "N" not in f:
+                assert len(f) == isize
+                return f
+
+    edge_cases = [(c, a, i) for i in (30, 50, 76, 77, 120) for c in ("chr1", "chr2", "chr3") for a in range(4)]
+    r1, r2 = [], []
+    n_of = {}
+    for i in range(n_pairs):
+        k = i % 20
+        kind = ("contained",) * 9 + ("overlap",) * 3 + ("unequal", "damaged", "gapped") + ("rescue",) * 3 + ("edge", "edgedisc")
+        kind = kind[k]
+        t = n_of[kind] = n_of.get(kind, -1) + 1                # how many of this kind came before
+        if kind == "contained":
+            f = frag(int(rng.integers(25, L)))
+        elif kind == "overlap":
+            f = frag((L, L + 1)[t] if t < 2 else int(rng.integers(L, 2 * L)))
+        elif kind == "gapped":
+            f = frag(int(rng.integers(L + 4, 2 * L - 10)))
+        elif kind == "edge":
+            c, a, isize = edge_cases[t % len(edge_cases)]
+            f = frag(isize, c, (0, 1, len(g[c]) - isize, len(g[c]) - 1 - isize)[a])
+        else:
+            f = frag(int(rng.integers(30, 2 * L)))
+        a, b = f[:L], rc(f[-L:])
+        if kind == "unequal":
+            cut = int(rng.integers(1, 16))
+            if rng.random() < 0.5:
+                a = a[:max(20, len(a) - cut)]
+            else:
+                b = b[:max(20, len(b) - cut)]
+        elif kind == "damaged":
+            if t % 2:
+                b = subs(b, int(rng.integers(9, 14)))
+            else:
+                a, b = subs(a, int(rng.integers(1, 3))), subs(b, int(rng.integers(0, 3)))
+        elif kind == "gapped":
+            d, src = int(rng.integers(1, 3)), (f, rc(f))[t % 2]
+            p = int(rng.integers(12, L - 12 - d))
+            x = src[:p] + src[p + d:L + d] if rng.random() < 0.5 else (src[:p] + "ACGT"[int(rng.integers(0, 4))] * d + src[p:])[:L]
+            a, b = (x, b) if t % 2 == 0 else (a, x)
+        elif kind == "rescue":
+            while True:
+                isize = int(rng.integers(80, 151)) if t % 4 < 2 else int(rng.integers(140, 151))      # few clipped bases: accepted rescues
+                start = int(rng.integers(8000 + L - isize, 10000 - isize + 1))
+                lo = start + isize - L                          # read 2's window on chr2, inside the copy
+                a = g["chr2"][start:start + L]
+                w1, w2 = g["chr1"][5000 + lo - 8000:5000 + lo - 8000 + L], g["chr2"][lo:lo + L]
+                if w1 != w2 and not (start >= 8000 and g["chr1"][5000 + start - 8000:][:L] == a):
+                    break
+            w = list(w1)
+            for p in rng.choice([j for j in range(L - 34) if w1[j] == w2[j]], n_extra(w1, w2), replace=False):
+                w[p] = sub1(w[p])                               # read 2 is the reverse complement: its seed is the window's tail
+            b = rc("".join(w))
+            while t % 2:                                        # the mirror image: a reverse-strand anchor, the window to its left
+                isize = int(rng.integers(80, 151)) if t % 4 < 2 else int(rng.integers(140, 151))      # few clipped bases: accepted rescues
+                start = int(rng.integers(8000, 10000 - L + 1))
+                f = g["chr2"][start:start + isize]
+                w1, w2 = g["chr1"][5000 + start - 8000:5000 + start - 8000 + L], f[:L]
+                if w1 != w2 and not (start + isize <= 10000 and g["chr1"][5000 + start + isize - L - 8000:][:L] == f[-L:]):
+                    w = list(w1)
+                    for p in rng.choice([j for j in range(34, L) if w1[j] == w2[j]], n_extra(w1, w2), replace=False):
+                        w[p] = sub1(w[p])                       # a forward read: its seed is the window's head
+                    a, b = rc(f[-L:]), "".join(w)
+                    break
+        elif kind == "edgedisc":
+            d = (0, 1, 9, 30, 50, 61, 70, L - 1)[(t // 2) % 8]
+            m = frag((L, 40, 25, L)[(t // 2) % 4], "chr2", None)
+            b = m if rng.random() < 0.5 else rc(m)
+            a = g["chr3"][len(g["chr3"]) - d - L:len(g["chr3"]) - d] if t % 2 == 0 else rc(g["chr1"][d:d + L])
+        if rng.random() < 0.5:
+            a, b = b, a
+        r1.append(("p%d_%s" % (i, kind), a, "I" * len(a)))
+        r2.append(("p%d_%s" % (i, kind), b, "I" * len(b)))
+    return r1, r2
+
+
+def pe_chain_against_the_reference(rlib, rix, ix, opt, r1, r2, estimates, tag):
+    """the search of both ends against ref_cal_sa_reg_gap, then nabwa_bwa_posn_pe / nabwa_bwa_finish_pe against ref_pe_records on the
+    reference's own records under every estimate, every field.  Returns the rescue attempts under the first estimate and the
+    reference's records under the last one."""
+    n_pairs = len(r1)
+    reads = [r for pr in zip(r1, r2) for r in pr]
+    seq, rseq, off, full = T.encode_reads(reads)
+    g = nabwa.GapOpt()
+    C.memmove(C.byref(g), C.byref(opt), 64)
+    hits, _ = ix.cal_sa_reg_gap(g, seq, rseq, off, per_read=True)
+    na = np.zeros(len(reads), np.int32); rows = np.zeros(512 * len(reads), T.ALN_DT); maxe = np.zeros(len(reads), np.int32)
+    tot = rlib.ref_cal_sa_reg_gap(rix, C.byref(opt), len(reads), T.ptr(off), T.ptr(seq), T.ptr(rseq), 1, T.ptr(na), T.ptr(rows), len(rows), T.ptr(maxe))
+    assert tot >= 0
+    bnd = np.concatenate([[0], np.cumsum(na)])
+    for i in range(len(reads)):
+        assert hits[i].tobytes() == rows[bnd[i]:bnd[i + 1]].tobytes(), (tag, reads[i][0], i & 1)
+    extra = [1 | (64 if i % 2 == 0 else 128) for i in range(len(reads))]
+    L = nabwa.lib()
+    L.nabwa_bwa_posn_pe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.nabwa_bwa_finish_pe.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    attempts = None
+    for iiv in estimates:
+        want, k1 = make_records(reads, seq, rseq, off, hits, full, extra)
+        rlib.ref_seed48(11)
+        rlib.ref_pe_records(rix, C.byref(opt), (C.c_double * 6)(*iiv), n_pairs, want)
+        got, k2 = make_records(reads, seq, rseq, off, hits, full, extra)
+        st = C.c_uint64(nabwa.srand48_state(11))
+        assert L.nabwa_bwa_posn_pe(ix._h, C.byref(g), n_pairs, got, C.byref(st)) == 0, L.nabwa_last_error()
+        ii = nabwa.IsizeInfo(iiv[0], iiv[1], iiv[2], int(iiv[3]), int(iiv[4]), int(iiv[5]))
+        po = nabwa.pe_opt_default()
+        tot2, mapped = (C.c_uint64 * 2)(), (C.c_uint64 * 2)()
+        assert L.nabwa_bwa_finish_pe(ix._h, C.byref(g), C.byref(po), C.byref(ii), n_pairs, got, tot2, mapped) == 0, L.nabwa_last_error()
+        bad = []
+        for i in range(len(reads)):
+            n_i = int(off[i + 1] - off[i])
+            a, b = record_fields(got[i], n_i), record_fields(want[i], n_i)
+            if (want[i].bits0 >> 21 & 3) == 0:             # an unmapped end: nothing else is defined (as in the tests above)
+                a = {k: a[k] for k in ("n_multi", "cigar", "md")}
+                b = {k: b[k] for k in ("n_multi", "cigar", "md")}
+            if a != b:
+                bad.append((reads[i][0], i & 1, iiv[0], {k: (a[k], b[k]) for k in a if a[k] != b[k] and k != "seq"},
+                            "types", want[i].bits0 >> 21 & 3, want[i ^ 1].bits0 >> 21 & 3, "pos", want[i].pos, want[i ^ 1].pos))
+        print("pe chain [%s] estimate %s: %d records, %d differ, rescue attempts %d + %d, accepted %d + %d"
+              % (tag, iiv, len(reads), len(bad), tot2[0], tot2[1], mapped[0], mapped[1]))
+        assert not bad, (tag, len(bad), bad[:6])
+        if attempts is None:
+            attempts = int(tot2[0] + tot2[1])
+    return attempts, want, (k1, k2)
+
+
+SHORT_ESTIMATES = ([88.0, 15.0, 1e-5, 76.0, 132.0, 169.0],      # as `sampe` infers on such pairs: low is the read length
+                   [61.5, 20.8, 1e-5, 1.0, 132.0, 176.0],       # as the histogram route does: low is 1
+                   [0.0] * 6)
+
+
+def test_pe_chain_on_short_inserts_with_overlapping_mates(ref):
+    """500 short-insert pairs made here (another seed than the committed set's): mates at one position on opposite strands, mates of
+    unequal length, rescued mates that overlap their anchor, fragments and rescue windows at the ends of the contigs and of the text.
+    Search, then posn_pair / finish_pair against the reference's own functions on its own records, every field, under three
+    estimates; and once more under the ancient-DNA options (-n 0.01 -o 2 -l 16500) on the pairs of 25 - 50 bp"""
+    rlib, rix = ref
+    r1, r2 = make_short_insert_pairs(500, 2025)
+    ix = nabwa.Index.load(T.TOY, 0, True, True)
+    attempts, want, keep = pe_chain_against_the_reference(rlib, rix, ix, T.default_opt(), r1, r2, SHORT_ESTIMATES, "default")
+    assert attempts >= 100, attempts
+    tp = lambda q: q.bits0 >> 21 & 3
+    same_pos = sum(1 for i in range(len(r1)) if tp(want[2 * i]) and tp(want[2 * i + 1]) and want[2 * i].pos == want[2 * i + 1].pos)
+    assert same_pos >= 150, same_pos
+    opt_adna, _ = T.read_sai(os.path.join(T.GOLDEN, "se_adna.sai"))
+    short = [i for i in range(len(r1)) if 25 <= len(r1[i][1]) <= 50 and 25 <= len(r2[i][1]) <= 50]
+    assert len(short) >= 80, len(short)
+    pe_chain_against_the_reference(rlib, rix, ix, opt_adna, [r1[i] for i in short], [r2[i] for i in short], SHORT_ESTIMATES, "adna")
+    ix.close()

@@ -74,11 +74,11 @@ def test_samse_equals_the_reference_goldens(name):
     assert_same_sam(r.stdout, open(os.path.join(T.GOLDEN, name + ".sam"), "rb").read())
 
 
-@pytest.mark.parametrize("tag", ["", "150"])
+@pytest.mark.parametrize("tag", ["", "150", "short"])
 def test_sampe_equals_the_reference_goldens(tag):
-    g = lambda x: os.path.join(T.GOLDEN, x % tag)
+    g = lambda x: T.stored(os.path.join(T.GOLDEN, x % tag))              # the short set's FASTQ and SAM are stored gzip-compressed
     r = run([SAMPE, T.TOY, g("pe%s_1.sai"), g("pe%s_2.sai"), g("reads_pe%s_1.fq"), g("reads_pe%s_2.fq")], timeout=300)
-    assert_same_sam(r.stdout, open(g("pe%s_default.sam"), "rb").read())
+    assert_same_sam(r.stdout, T.open_text(g("pe%s_default.sam"), "rb").read())
     assert len(isize_lines(r.stderr)) == 5
 
 

@@ -5,6 +5,7 @@ import importlib
 import os
 
 import numpy as np
+import pytest
 
 import nabwa_testlib as T
 
@@ -36,6 +37,39 @@ def test_isize_bin():
     assert nabwa.lib().nabwa_isize_bin(2, 37, 19, 1000, 100, 1300, 100) == -1      # both ends need mapQ >= 20
     assert nabwa.lib().nabwa_isize_bin(1, 25, 0, 5, 76, 0, 0) == 76                # single read: its length
     assert nabwa.lib().nabwa_isize_bin(2, 37, 37, 1000, 100, 200000, 100) == -1    # >= MAX_ISIZE
+
+
+def test_isize_bin_of_mates_at_one_position():
+    """a.pos < c.pos ? c.pos + c.len - a.pos : a.pos + a.len - c.pos (insert_size.c:141-165): at equal positions the second branch
+    runs, and the bin is the FIRST end's length"""
+    L = nabwa.lib()
+    assert L.nabwa_isize_bin(2, 37, 37, 1000, 40, 1000, 60) == 40
+    assert L.nabwa_isize_bin(2, 37, 37, 1000, 60, 1000, 40) == 60
+    assert L.nabwa_isize_bin(2, 37, 37, 1000, 40, 1001, 60) == 61
+    assert L.nabwa_isize_bin(2, 37, 37, 1001, 40, 1000, 60) == 41
+
+
+@pytest.mark.parametrize("tag", ["", "150", "short"])
+def test_histogram_route_equals_the_reference_estimate(tag):
+    """nabwa_isize_add_pairs + nabwa_isize_infer on the pairs as the reference positioned them (posn_f of the chain vectors) give the
+    estimate the reference's infer_isize made from the same pairs binned by the expression above (ii_hist).  The short-insert set has
+    318 pairs at one position, 44 with mates of unequal length, and a low bound of 1."""
+    v = np.load(os.path.join(T.GOLDEN, "vectors_pe%s_chain.npz" % tag))
+    f = v["posn_f"]
+    recs = (nabwa.PeRec * len(f))()
+    for r in range(len(f)):
+        s = recs[r].se
+        s.type, s.pos, s.mapQ, s.len = int(f[r][0]), int(f[r][9]), int(f[r][10]), int(f[r][16])
+    h = np.zeros(100000, np.uint16)
+    L = nabwa.lib()
+    L.nabwa_isize_add_pairs.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    assert L.nabwa_isize_add_pairs(len(f) // 2, recs, T.ptr(h)) == 0
+    assert int(h.sum()) > 100
+    rc, ii = nabwa.isize_infer(h, 1e-5, int(open(T.TOY + ".ann").read().split()[0]))
+    assert rc == 0
+    assert (ii.avg, ii.std, ii.ap_prior, ii.low, ii.high, ii.high_bayesian) == tuple(v["ii_hist"])
+    if tag == "short":
+        assert ii.low == 1
 
 
 def test_pairing_golden():

@@ -21,7 +21,7 @@ def toy_l_pac():
     return int(open(T.TOY + ".ann").read().split()[0])
 
 
-@pytest.mark.parametrize("tag", ["", "150"])
+@pytest.mark.parametrize("tag", ["", "150", "short"])
 def test_isize_infer_pairs_equals_the_reference_estimate(tag):
     v = np.load(os.path.join(T.GOLDEN, "vectors_pe%s_chain.npz" % tag))
     f = v["posn_f"]

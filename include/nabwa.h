@@ -167,6 +167,11 @@ int nabwa_batch_sure0_stats(nabwa_batch_t *b, uint64_t out[4]);
  * that occurs exactly, replaced by its hit), out[5] levels leapt over, out[6] such entries that walked instead because their text position was
  * short of the levels left (expected 0), out[7] 0. */
 int nabwa_batch_sure0_stats_ex(nabwa_batch_t *b, uint64_t out[8]);
+/* tests, profiles: with NABWA_W_STATS=1, the trip counts of kernel W's last launch of this batch (nabwa_batch_run followed by nabwa_batch_sync,
+ * or nabwa_batch_width_records): out[0] wave-trips, out[1] the trips of the work item that took most, out[2] text trips << 32 | their positions,
+ * out[3] table trips << 32 | their positions, out[4] text trips begun in a seed pass << 32 | single steps with a rank query, out[5] single steps
+ * without one (search_slots.hpp: TS_W_*; a single step is one position).  The same line goes to stderr.  All 0 without the variable. */
+int nabwa_batch_w_stats(nabwa_batch_t *b, unsigned long long out[6]);
 /* what NABWA_DEDUP did for this batch: out[0] reads given, out[1] reads searched, out[2] reads that shared a hash with an earlier read of the
  * batch but differ from the first read of that hash (each is searched on its own and counts in out[1]), out[3] 1 when the batch was created
  * with the switch on, else 0.  Without the switch: { n, n, 0, 0 }. */

@@ -52,7 +52,7 @@
 #define KEYM 0xffffffffu  // l of an interval carried in key form (k = path key: the reference symbols matched so far as base-4 digits)
 #define LVO(t_) ((size_t)((((uint64_t)1 << (2 * (t_))) - 4ull) / 3ull))   /* offset of level t in the interval table */
 #ifndef NABWA_W_WAVES
-#define NABWA_W_WAVES 5   // kernel W: waves per SIMD the register budget is bounded for (102 VGPRs)
+#define NABWA_W_WAVES 5   // kernel W: waves per SIMD the register budget is bounded for (96 VGPRs)
 #endif
 #ifndef NABWA_WORK_CHUNK
 #define NABWA_WORK_CHUNK 64u
@@ -91,7 +91,13 @@ extern __shared__ uint16_t s_head[];   // search kernel, first pass only: [score
 //   Bd [2][WLB] bound bytes: min(bid,127) | (w[i-1]==w[i]) << 7
 //   SBd[2][SLB] the same for the seed passes
 // =====================================================================================
-template <bool COUNT>
+// WF: the forms of its trips, bits TM_W_RUNS / TM_W_TRIP8 of text_mode shifted down to bit 0 -- one instantiation per combination,
+// picked at the launch (with_width_kernel): with the forms as run-time flags the old and the new paths together spilled 28 VGPRs at
+// 5 waves; as instantiations WF = 0 has the paths of the kernel before v15 and no other (its end-of-pass block alone has moved, to the end
+// of the loop body), and every other one holds the paths it can take alone.
+// STATS (NABWA_W_STATS, TM_W_STATS): the same kernel, tables and all, that also counts its trips into slots TS_W_* of P.touch_counter.
+#define W_FORMS(tm_) (((tm_) / TM_W_RUNS) & 3)
+template <bool COUNT, int WF, bool STATS = false>
 __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_kernel(const SearchParams P)
 {
 	const uint32_t lane = threadIdx.x & 63u;
@@ -113,11 +119,16 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 	const bool quads = (P.text_mode & TM_W_QUADS) && P.ixtab;
 	if (threadIdx.x < 2 * NABWA_PK_LEVELS) s_pk[threadIdx.x] = quads ? P.ixtab[NABWA_IXTAB_WORDS + threadIdx.x] : 0xffffffffu;
 	__syncthreads();
+	// the forms of this kernel's trips (fm_search.hpp: TM_W_*); with both off every path is the one before v15
+	constexpr bool w_trip8 = (WF & 2) != 0, w_runs = (WF & 1) != 0;      // (a run needs the packed read: nflag is set where there is none)
+	// STATS: lane-trips [path] and positions [path] of this lane (paths: 0 text trip, 1 table trip, 2 single step with a rank query, 3 without),
+	// text trips begun in a seed pass, this item's trips, this wave's trips
+	uint32_t st_lt[4] = { 0u, 0u, 0u, 0u }, st_pos[2] = { 0u, 0u }, st_tx1 = 0u, st_item = 0u, st_max = 0u, st_wave = 0u;
 	bool nflag = true;                                          // this strand has an N (word PW-1 of its packed bases), read once when the item is taken
 	// after a restart (bwtaln.c:66-70) the pattern begins anew at the next position: its key comes from the packed read
 	auto rekey = [&](int from) {
 		tok = false; tbase = from;
-		if (nflag || from + 4 >= n) return;                       // an N somewhere in this strand (or no table, no packed reads): step by step
+		if (nflag || from + (w_trip8 ? 0 : 4) >= n) return;       // an N somewhere in this strand (or no table, no packed reads): step by step
 		const int PW = P.pack_stride / 2;
 		const uint32_t *const pk = P.rd_pack + (size_t)rid * P.pack_stride + x * PW;
 		const int q = sbase + from;
@@ -164,6 +175,7 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 			}
 		}
 		if (__ballot(!done) == 0ull) break;
+		if (STATS) { ++st_wave; if (run) ++st_item; }
 		// output of position p: width, bound byte, 16-byte chunk flushes; `last` = the terminator {w = 0, bid = ++bid}
 		// after the final position (bwtaln.c:73-74)
 		auto out_pos = [&](int p, bool last) {
@@ -181,11 +193,101 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 				blo = bhi = 0;
 			}
 		};
+		// The same output for SEVERAL finished positions at once (the text runs and the 8-level table trips), without a turn per position:
+		// the cnt bound bytes of positions p .. p+cnt-1 arrive as one 128-bit value (byte j = position p+j, zero from cnt on; the
+		// terminator, where the pass ends, is the last of them), are shifted to their place behind the bytes the accumulator holds
+		// and merged; the 16-byte chunk that became complete is stored, the rest stays in the accumulator.  cnt <= 16.
+		auto put_bytes = [&](int p, int cnt, uint64_t nlo, uint64_t nhi, bool fin) {
+			uint8_t *const dst = WREC + (phase ? P.woff_sbid + x * P.SLB : P.woff_bid + x * P.WLB) + (p & ~15);
+			const uint32_t o = (uint32_t)p & 15u, s = (o & 7u) << 3;
+			const uint64_t a0 = nlo << s, a1 = nhi << s | (s ? nlo >> (64u - s) : 0ull), a2 = s ? nhi >> (64u - s) : 0ull;
+			const bool up = (o & 8u) != 0u;
+			const uint64_t q0 = blo | (up ? 0ull : a0), q1 = bhi | (up ? a0 : a1), q2 = up ? a1 : a2, q3 = up ? a2 : 0ull;
+			const uint32_t e = o + (uint32_t)cnt;
+			const bool full = e >= 16u;
+			if (full) *(uint4*)dst = make_uint4((uint32_t)q0, (uint32_t)(q0 >> 32), (uint32_t)q1, (uint32_t)(q1 >> 32));
+			blo = full ? q2 : q0; bhi = full ? q3 : q1;
+			if (fin) {
+				if (e & 15u) *(uint4*)(dst + (full ? 16 : 0)) = make_uint4((uint32_t)blo, (uint32_t)(blo >> 32), (uint32_t)bhi, (uint32_t)(bhi >> 32));
+				blo = bhi = 0;
+			}
+		};
+		// ... and their widths (full pass only): w[0 .. cnt-1], entries from cnt on are never stored before they are written again.
+		// The values move up by p & 3 places in two select stages, the accumulator's entries go in front, whole chunks are stored.
+		auto put_widths = [&](int p, int cnt, const auto &w, bool fin) {
+			constexpr int NW = (int)(sizeof(w) / sizeof(w[0])), NC = (NW + 6) / 4;
+			uint32_t *const dst = (uint32_t*)WREC + x * P.WL + (p & ~3);
+			const uint32_t o = (uint32_t)p & 3u;
+			uint32_t s1[NW + 1], c[4 * NC];
+#pragma unroll
+			for (int j = 0; j <= NW; ++j) { const uint32_t a = j < NW ? w[j] : 0u, b = j ? w[j - 1] : 0u; s1[j] = (o & 1u) ? b : a; }
+#pragma unroll
+			for (int j = 0; j < 4 * NC; ++j) { const uint32_t a = j <= NW ? s1[j] : 0u, b = (j >= 2 && j - 2 <= NW) ? s1[j - 2] : 0u; c[j] = (o & 2u) ? b : a; }
+			c[0] = o > 0u ? wacc.x : c[0]; c[1] = o > 1u ? wacc.y : c[1]; c[2] = o > 2u ? wacc.z : c[2];
+			const uint32_t e = o + (uint32_t)cnt;
+#pragma unroll
+			for (int j = 0; j < NC; ++j)
+				if (4u * j + 4u <= e || (fin && 4u * j < e)) *(uint4*)(dst + 4 * j) = make_uint4(c[4 * j], c[4 * j + 1], c[4 * j + 2], c[4 * j + 3]);
+			uint4 r = make_uint4(c[0], c[1], c[2], c[3]);
+#pragma unroll
+			for (int j = 1; j < NC; ++j) if ((e >> 2) == (uint32_t)j) r = make_uint4(c[4 * j], c[4 * j + 1], c[4 * j + 2], c[4 * j + 3]);
+			wacc = r;
+		};
+		// ... and the widths of a text run: all 1, the terminator's 0 at position term (-1: none in this run).  cnt <= 16: five chunks.
+		auto put_ones = [&](int p, int cnt, int term, bool fin) {
+			uint32_t *const dst = (uint32_t*)WREC + x * P.WL + (p & ~3);
+			const uint32_t o = (uint32_t)p & 3u, e = o + (uint32_t)cnt;
+			const int t = term - (p & ~3);
+			uint4 c0 = make_uint4(t == 0 ? 0u : 1u, t == 1 ? 0u : 1u, t == 2 ? 0u : 1u, t == 3 ? 0u : 1u);
+			c0.x = o > 0u ? wacc.x : c0.x; c0.y = o > 1u ? wacc.y : c0.y; c0.z = o > 2u ? wacc.z : c0.z;
+			if (4u <= e || fin) *(uint4*)dst = c0;
+#pragma unroll
+			for (int j = 1; j < 5; ++j)
+				if (4u * j + 4u <= e || (fin && 4u * j < e))
+					*(uint4*)(dst + 4 * j) = make_uint4(t == 4 * j ? 0u : 1u, t == 4 * j + 1 ? 0u : 1u, t == 4 * j + 2 ? 0u : 1u, t == 4 * j + 3 ? 0u : 1u);
+			wacc = e < 4u ? c0 : make_uint4(1u, 1u, 1u, 1u);
+		};
 		// bulk text trip: a full pass in text mode at a 16-position chunk boundary -- compare the chunk's 16 read symbols
 		// with the 16 text bases to the left of the suffix as packed words; if all match, every width is 1, every bound
 		// byte repeats (no restart, w[i-1] == w[i]) and the chunk's output is five 16-byte stores
-		bool bulk = run && phase == 0 && tmode && (wi & 15) == 0 && wi + 16 < n && tp >= 16u && pw == 1u;
-		if (bulk) {
+		bool bulk = !w_runs && run && phase == 0 && tmode && (wi & 15) == 0 && wi + 16 < n && tp >= 16u && pw == 1u;
+		// text run (TM_W_RUNS), in place of the bulk trip: up to 16 positions from ANY position of either pass.  The read's next 16
+		// symbols are one extract from its packed words (as rekey takes them), the 16 text bases to the left of the suffix one from
+		// the text's; the run is the number of leading 2-bit groups that agree, clamped to what the pass and the text have left.
+		// A mismatch ends the run in front of it: that position restarts in the single step below, in the next trip or -- a run
+		// of no position -- in this one.
+		if constexpr (w_runs) if (run && tmode && !nflag && pw == 1u && tp > 0u) {
+			const uint32_t *const pk = P.rd_pack + (size_t)rid * P.pack_stride + x * (P.pack_stride / 2);
+			const int q = sbase + wi;
+			const uint32_t r0 = pk[q >> 4], r1 = pk[(q >> 4) + 1], sh = ((uint32_t)q & 15u) << 1;
+			const uint32_t rd = sh ? (r0 << sh) | (r1 >> (32u - sh)) : r0;
+			const uint32_t b0 = tp >= 16u ? tp - 16u : 0u, ts = (b0 & 15u) << 1;
+			const uint32_t *const txt = BX(text);
+			const uint32_t t0 = txt[b0 >> 4], t1 = ts ? txt[(b0 >> 4) + 1u] : 0u;      // (the second word only where the 16 bases reach into it)
+			uint32_t tx = (uint32_t)(((uint64_t)t1 << 32 | t0) >> ts);                // text bases b0 .. b0+15, base b0+m at bits 2m
+			if (tp < 16u) tx <<= (16u - tp) << 1;                                     // base tp-1 at the top, where the read's next symbol is: the walk goes down the text
+			const uint32_t df = tx ^ rd, same = df ? (uint32_t)__clz((int)df) >> 1 : 16u;
+			const uint32_t left = (uint32_t)(n - wi);
+			uint32_t kmax = min(min(16u, left), tp);
+			if (left == 16u) kmax = min(kmax, 15u);                                   // (a run and its terminator are 16 bytes at the most)
+			const uint32_t r = min(same, kmax);
+			if (r) {
+				const bool fin = r == left;
+				const uint64_t b8 = (uint64_t)((uint32_t)(bid > 127 ? 127 : bid) | 128u) * 0x0101010101010101ull;
+				const uint64_t mlo = r >= 8u ? ~0ull : (1ull << (r << 3)) - 1ull, mhi = r <= 8u ? 0ull : (r >= 16u ? ~0ull : (1ull << ((r - 8u) << 3)) - 1ull);
+				uint64_t nlo = b8 & mlo, nhi = b8 & mhi;
+				if (fin) {                                                            // the terminator {w = 0, bid = ++bid}: 0 is not the width before it
+					++bid;
+					const uint64_t tb = (uint64_t)(bid > 127 ? 127 : bid);
+					if (r < 8u) nlo |= tb << (r << 3); else nhi |= tb << ((r - 8u) << 3);
+				}
+				if (phase == 0) put_ones(wi, (int)r + (fin ? 1 : 0), fin ? n : -1, fin);
+				put_bytes(wi, (int)r + (fin ? 1 : 0), nlo, nhi, fin);
+				if (STATS) { ++st_lt[0]; st_pos[0] += r; if (phase) ++st_tx1; }
+				tp -= r; wi += (int)r; bulk = true;
+			}
+		}
+		if constexpr (!w_runs) if (bulk) {
 			if ((wi >> 4) != stag) { const uint4 q = *(const uint4*)((x ? P.rseq : P.seq) + sq_off + wi); WIN_SET(slo, shi, q.x, q.y, q.z, q.w); stag = wi >> 4; }
 			const uint32_t w0 = (tp - 16u) >> 4;
 			const uint32_t *const txt = BX(text);
@@ -209,11 +311,78 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 				for (int u = 0; u < 4; ++u) *(uint4*)(wp + 4 * u) = make_uint4(1u, 1u, 1u, 1u);
 				const uint32_t b4 = ((uint32_t)(bid > 127 ? 127 : bid) | 128u) * 0x01010101u;
 				*(uint4*)(rec + P.woff_bid + x * P.WLB + wi) = make_uint4(b4, b4, b4, b4);
+				if (STATS) { ++st_lt[0]; st_pos[0] += 16u; if (phase) ++st_tx1; }
 				tp -= 16u; wi += 16;
 			}
 		}
 		if (bulk) { /* chunk done */ }
-		else if (run && tok && wi - tbase + 4 <= LW && wi + 4 < n) {
+		else if (w_trip8 && run && tok && wi - tbase < LW) {
+			// table trip of up to 8 levels (TM_W_TRIP8; the instantiations without it take the 4-level trip below, these never), clamped to
+			// the levels the table has left for this pattern and to the positions the pass has left -- so a pass may end inside it, and the terminator goes out in the same append.  Quads as below, one 32-byte load per two levels; where the
+			// trip's last level is the table's last, its entry is loaded itself: the interval left behind is always the real one.
+			const int t1 = wi - tbase + 1, m = min(min(8, LW - (wi - tbase)), n - wi);
+			const uint2 *const lo = BX(kmer_lo);
+			uint2 tv[8];
+#pragma unroll
+			for (int u = 0; u < 8; ++u) tv[u] = make_uint2(1u, 0u);
+			if (quads) {
+				uint4 qd[4][2];
+#pragma unroll
+				for (int h = 0; h < 4; ++h) {
+					const int t = t1 + 2 * h;
+					qd[h][0] = qd[h][1] = make_uint4(1u, 0u, 1u, 0u);
+					if (2 * h + 1 < m) {
+						const uint4 *const p = (const uint4*)(lo + LVO(t + 1) + 4 * (size_t)(wkey >> (2 * (KT - t))));
+						qd[h][0] = p[0]; qd[h][1] = p[1];
+					} else if (2 * h < m) {
+						const uint2 v = (lo + LVO(t))[wkey >> (2 * (KT - t))];
+						qd[h][0].x = v.x; qd[h][0].y = v.y;
+					}
+				}
+#pragma unroll
+				for (int h = 0; h < 4; ++h) {
+					const int t = t1 + 2 * h;
+					if (2 * h + 1 < m) {
+						const uint32_t ch = wkey >> (2 * (KT - t - 1)), c = ch & 3u;
+						const uint4 a = qd[h][0], b = qd[h][1];
+						const uint32_t sum = (a.y - a.x) + (a.w - a.z) + (b.y - b.x) + (b.w - b.z) + 4u + ((ch >> 2) == s_pk[x * NABWA_PK_LEVELS + t] ? 1u : 0u);
+						tv[2 * h] = make_uint2(1u, sum);
+						tv[2 * h + 1] = c == 0u ? make_uint2(a.x, a.y) : (c == 1u ? make_uint2(a.z, a.w) : (c == 2u ? make_uint2(b.x, b.y) : make_uint2(b.z, b.w)));
+					} else tv[2 * h] = make_uint2(qd[h][0].x, qd[h][0].y);
+				}
+			} else {
+#pragma unroll
+				for (int u = 0; u < 8; ++u)
+					if (u < m) { const int t = t1 + u; tv[u] = (lo + LVO(t))[wkey >> (2 * (KT - t))]; }
+			}
+			// the levels as values: a level is part of the trip while no level before it was empty (the restart, bwtaln.c:66-70)
+			const uint32_t full1 = BX(seq_len) + 1u, bb = (uint32_t)(bid > 127 ? 127 : bid), bb1 = (uint32_t)(bid + 1 > 127 ? 127 : bid + 1);
+			uint32_t wv[9], pv = pw, nk = kk, nl = ll; uint64_t nlo = 0ull; int cnt = 0; bool alive = true, died = false;
+#pragma unroll
+			for (int u = 0; u < 8; ++u) {
+				const bool act = alive && u < m, dead = tv[u].x > tv[u].y;
+				const uint32_t w = dead ? full1 : tv[u].y - tv[u].x + 1u;
+				const uint32_t by = (dead ? bb1 : bb) | ((wi + u > 0 && w == pv) ? 128u : 0u);
+				wv[u] = act ? w : 0u;
+				if (act) { nlo |= (uint64_t)by << (8 * u); pv = w; nk = tv[u].x; nl = tv[u].y; ++cnt; died = dead; }
+				alive = act && !dead;
+			}
+			wv[8] = 0u;
+			const int p0 = wi;
+			if (STATS) { ++st_lt[1]; st_pos[1] += (uint32_t)cnt; }
+			wi += cnt; pw = pv;
+			if (died) { kk = 0; ll = BX(seq_len); ++bid; rekey(wi); } else { kk = nk; ll = nl; }
+			const bool fin = wi == n;
+			uint64_t nhi = 0ull;
+			if (fin) {
+				++bid;
+				const uint64_t tb = (uint64_t)(bid > 127 ? 127 : bid);
+				if (cnt < 8) nlo |= tb << (8 * cnt); else nhi = tb;
+			}
+			if (phase == 0) put_widths(p0, cnt + (fin ? 1 : 0), wv, fin);
+			put_bytes(p0, cnt + (fin ? 1 : 0), nlo, nhi, fin);
+		}
+		else if (!w_trip8 && run && tok && wi - tbase + 4 <= LW && wi + 4 < n) {
 			// table trip: the intervals after wi+1 .. wi+4 symbols of this phase are entries of levels wi+1 .. wi+4 of the
 			// interval table (fm_index.hip) -- four independent 8-byte loads, the low levels cache-resident -- instead
 			// of four dependent rank queries.  An empty entry is the reference's restart (bwtaln.c:66-70): from there on
@@ -257,17 +426,21 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 				if (dead) { kk = 0; ll = BX(seq_len); ++bid; }
 				out_pos(wi, false);
 				++wi;
+				if (STATS) ++st_pos[1];
 				if (dead) { rekey(wi); break; }
 			}
+			if (STATS) ++st_lt[1];
 		} else if (run) {
 			const int pos = sbase + wi;
 			if ((pos >> 4) != stag) { const uint4 q = *(const uint4*)((x ? P.rseq : P.seq) + sq_off + (pos & ~15)); WIN_SET(slo, shi, q.x, q.y, q.z, q.w); stag = pos >> 4; }
 			const int cc = (int)byte_of(slo, shi, (uint32_t)pos & 15u);
 			// issue the loads of this step before consuming any (one memory latency per trip)
 			uint4 qa[4], qb[4]; uint32_t rk = 0, rl = 0, sav = 0; bool kval = false, two = false;
+			// (qa and qb are read only where q, and two, loaded them -- but left unset they cost 68 spilled VGPRs and 208 bytes of scratch)
 #pragma unroll
 			for (int u = 0; u < 4; ++u) { qa[u] = make_uint4(0, 0, 0, 0); qb[u] = make_uint4(0, 0, 0, 0); }
 			const bool q = cc < 4 && !tmode;
+			if (STATS) { if (q) ++st_lt[2]; else ++st_lt[3]; }
 			if (q) {
 				const uint32_t primary = BX(primary), kq = kk - 1u, lq = ll;
 				const uint32_t kp = kq - (kq >= primary ? 1u : 0u), lp = lq - (lq >= primary ? 1u : 0u);
@@ -321,15 +494,32 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_W_WAVES) void fm_width_ke
 			out_pos(wi, false);
 			if (wi + 1 == n) out_pos(wi + 1, true);
 			++wi;
-			if (wi == n) {
-				if (phase == 0 && P.rd_cls) P.rd_cls[2 * (size_t)rid + x] = (uint8_t)(bid - 1 > 4 ? 4 : bid - 1);   // restarts of this strand's pass (bid counts the terminator too, bwtaln.c:66-74)
-				if (phase == 0 && len > P.seed_len) {
-					phase = 1; wi = 0; n = P.seed_len; sbase = len - P.seed_len; tmode = false;
-					if (KT) { wkey = P.rd_key[6 * (size_t)rid + 4 + x]; tok = wkey != 0xffffffffu; }
-					tbase = 0;
-					kk = 0; ll = BX(seq_len); bid = 0; pw = 0;
-				} else { if (x == 0u) P.rd_nN[rid] = (uint8_t)(nN > 255 ? 255 : nN); run = false; }
+		}
+		// the end of a pass, whichever trip reached it (before v15: the single step alone)
+		if (run && wi == n) {
+			if (phase == 0 && P.rd_cls) P.rd_cls[2 * (size_t)rid + x] = (uint8_t)(bid - 1 > 4 ? 4 : bid - 1);   // restarts of this strand's pass (bid counts the terminator too, bwtaln.c:66-74)
+			if (phase == 0 && len > P.seed_len) {
+				phase = 1; wi = 0; n = P.seed_len; sbase = len - P.seed_len; tmode = false;
+				if (KT) { wkey = P.rd_key[6 * (size_t)rid + 4 + x]; tok = wkey != 0xffffffffu; }
+				tbase = 0;
+				kk = 0; ll = BX(seq_len); bid = 0; pw = 0;
+			} else {
+				if (x == 0u) P.rd_nN[rid] = (uint8_t)(nN > 255 ? 255 : nN); run = false;
+				if (STATS) { st_max = max(st_max, st_item); st_item = 0u; }
 			}
+		}
+	}
+	if (STATS && P.touch_counter) {      // positions of the single steps = their lane-trips: slots TS_W_RANK and TS_W_STEP carry the seed-pass text trips and nothing above them
+		unsigned long long v[4] = { (unsigned long long)st_lt[0] << 32 | st_pos[0], (unsigned long long)st_lt[1] << 32 | st_pos[1],
+									(unsigned long long)st_tx1 << 32 | st_lt[2], (unsigned long long)st_lt[3] };
+		for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+			for (int u = 0; u < 4; ++u) v[u] += __shfl_down(v[u], o);
+			st_max = max(st_max, (uint32_t)__shfl_down((int)st_max, o));
+		}
+		if (lane == 0) {
+			atomicAdd(P.touch_counter + TS_W_TRIPS, (unsigned long long)st_wave); atomicMax(P.touch_counter + TS_W_MAX, (unsigned long long)st_max);
+			atomicAdd(P.touch_counter + TS_W_TEXT, v[0]); atomicAdd(P.touch_counter + TS_W_TABLE, v[1]); atomicAdd(P.touch_counter + TS_W_RANK, v[2]); atomicAdd(P.touch_counter + TS_W_STEP, v[3]);
 		}
 	}
 	if (COUNT) {
@@ -1138,16 +1328,33 @@ __global__ __launch_bounds__(NABWA_SEARCH_BLOCK, NABWA_MIN_WAVES) void fm_search
 #undef REC
 #undef MD_READ
 #undef MG_READ
-extern "C" void nabwa_launch_fm_width(const SearchParams *P, int n_blocks, hipStream_t s)
+// kernel W's instantiation for the forms text_mode asks for (W_FORMS), as f(kernel).  Twelve in all: four forms, plain, touch-counting and
+// statistics.  The single-knob forms stay in the two diagnostic builds as well: the statistics test runs every knob setting
+// (tests/test_gpu_width_spans.py), and the touch-counting run with NABWA_TRIP_STATS=jump keeps the batch's text_mode, whatever its knobs.
+template <bool COUNT, bool STATS = false, typename F> static auto with_width_kernel(int text_mode, F f)
 {
-	if (P->touch_counter) hipLaunchKernelGGL((fm_width_kernel<true>), dim3(n_blocks), dim3(NABWA_SEARCH_BLOCK), 0, s, *P);
-	else hipLaunchKernelGGL((fm_width_kernel<false>), dim3(n_blocks), dim3(NABWA_SEARCH_BLOCK), 0, s, *P);
+	switch (W_FORMS(text_mode)) {
+	case 1: return f(fm_width_kernel<COUNT, 1, STATS>);
+	case 2: return f(fm_width_kernel<COUNT, 2, STATS>);
+	case 3: return f(fm_width_kernel<COUNT, 3, STATS>);
+	default: return f(fm_width_kernel<COUNT, 0, STATS>);
+	}
 }
 
-extern "C" int nabwa_width_occupancy(void)
+extern "C" void nabwa_launch_fm_width(const SearchParams *P, int n_blocks, hipStream_t s)
 {
-	int nb = 0;
-	return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fm_width_kernel<false>, NABWA_SEARCH_BLOCK, 0) == hipSuccess ? nb : 0;
+	auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(n_blocks), dim3(NABWA_SEARCH_BLOCK), 0, s, *P); return 0; };
+	if ((P->text_mode & TM_W_STATS) && P->touch_counter) with_width_kernel<false, true>(P->text_mode, go);      /* the trip statistics: NOT the counting build, which runs without tables */
+	else if (P->touch_counter) with_width_kernel<true>(P->text_mode, go);
+	else with_width_kernel<false>(P->text_mode, go);
+}
+
+extern "C" int nabwa_width_occupancy(int text_mode)
+{
+	return with_width_kernel<false>(text_mode, [](auto k) {
+		int nb = 0;
+		return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, NABWA_SEARCH_BLOCK, 0) == hipSuccess ? nb : 0;
+	});
 }
 
 extern "C" void nabwa_launch_fm_search(const SearchParams *P, int n_blocks, hipStream_t s)

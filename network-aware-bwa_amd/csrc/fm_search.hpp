@@ -13,6 +13,9 @@
 #define NABWA_ST_GROWN     5   // resolved by such a second search: the rows are the block grown[wide_idx[read]] names
 
 #define TM_W_QUADS 8
+#define TM_W_RUNS 16
+#define TM_W_TRIP8 32
+#define TM_W_STATS 64   /* NABWA_W_STATS: kernel W's statistics instantiation, counts into slots TS_W_* behind touch_counter (its launches only) */
 
 struct SearchParams {
 	DevBwt bwt[2];
@@ -33,6 +36,9 @@ struct SearchParams {
 	uint32_t WL, WLB, SLB;
 	int text_mode;                            // 0: never leave the FM-index (the touch-counting run); bit 0 / 1: text mode in kernel W / S where the index has it; bit 2: key form in S;
 	                                          // bit 3 (TM_W_QUADS, NABWA_W_QUADS): kernel W's table trips load two levels per 32 bytes
+	                                          // bit 4 (TM_W_RUNS, NABWA_W_RUNS): kernel W's text runs of up to 16 positions at any alignment in both passes, in place of the bulk trip
+	                                          // bit 5 (TM_W_TRIP8, NABWA_W_TRIP8): its table trips of up to 8 levels, clamped to the table and to the pass
+	                                          // (both append their outputs as values, no call per position; one instantiation of the kernel per combination)
 	const uint32_t *rd_key;                   // per read six interval-table keys [6*rid + ..] (see pad_reads_kernel), ~0u = none
 	uint8_t *rd_nN;                           // per read: number of N in the read, saturated at 255
 	// per-lane scratch of kernel S: the arena

@@ -18,7 +18,7 @@ void nabwa_launch_occ4(const DevBwt *B, int n, const uint32_t *k, uint32_t *out,
 /* fm_search.hip */
 void nabwa_launch_fm_search(const SearchParams *P, int n_blocks, hipStream_t s);
 void nabwa_launch_fm_width(const SearchParams *P, int n_blocks, hipStream_t s);
-int nabwa_width_occupancy(void);
+int nabwa_width_occupancy(int text_mode);      /* of kernel W's instantiation for these forms (fm_search.hpp: TM_W_*) */
 int nabwa_search_occupancy(int ns);
 /* batch_kernels.hip */
 /* map (checksum, gather): null, or for each of the n reads the read whose results it takes (NABWA_DEDUP: the caller's read -> the read searched);

@@ -357,6 +357,11 @@ static int working_buffers(nabwa_batch *b, const BatchShape &s)
 	/* kernel W (fm_search.hip; profiles/width_requests_bench.txt): NABWA_W_QUADS -- a table trip takes two levels from each 32 bytes it loads, the
 	 * parent's width as the sum over its children (0: one 8-byte entry per level, as before v14) */
 	if (env_int("NABWA_W_QUADS", 1)) P.text_mode |= TM_W_QUADS;
+	/* (profiles/width_spans_bench.txt) NABWA_W_RUNS -- text runs of up to 16 positions from any position of either pass; NABWA_W_TRIP8 -- table trips
+	 * of up to 8 levels that may end a pass; the outputs of either are appended to the record's accumulators as values, in one shift and merge.
+	 * Both 0: the kernel before v15 */
+	if (env_int("NABWA_W_RUNS", 1)) P.text_mode |= TM_W_RUNS;
+	if (env_int("NABWA_W_TRIP8", 1)) P.text_mode |= TM_W_TRIP8;
 	if (ix->bwt[0].kmer_T != ix->bwt[1].kmer_T) P.bwt[0].kmer_T = P.bwt[1].kmer_T = 0;
 	P.ids = 0; P.n = n;
 	P.s_mm = opt->s_mm; P.s_gapo = opt->s_gapo; P.s_gape = opt->s_gape; P.mode = opt->mode;
@@ -406,7 +411,7 @@ static int working_buffers(nabwa_batch *b, const BatchShape &s)
 	if (getenv("NABWA_TIMING")) fprintf(stderr, "[nabwa] search kernel: %u score levels, %d blocks per CU (LDS %zu B per block), %ld blocks\n", s.NS1, occ,
 										(size_t)s.NS1 * NABWA_SEARCH_BLOCK * 2 + NABWA_SEARCH_BLOCK * 80, blocks);
 	HIP_CHECK(b->d_scratch.get(ix, (size_t)blocks * NABWA_SEARCH_BLOCK * P.lane_stride));
-	int occw = nabwa_width_occupancy(); if (occw < 1) occw = 1;
+	int occw = nabwa_width_occupancy(P.text_mode); if (occw < 1) occw = 1;
 	long blocks_w = (long)prop.multiProcessorCount * occw;
 	if (blocks_w > 2 * need) blocks_w = 2 * need;        /* kernel W: one lane per strand of a read */
 	if (blocks_w < 1) blocks_w = 1;
@@ -479,6 +484,34 @@ extern "C" int nabwa_batch_create(nabwa_index_t *ix, const nabwa_gap_opt_t *opt,
 	return NABWA_OK;
 }
 
+/* NABWA_W_STATS=1: this launch of kernel W is its statistics instantiation (fm_search.hip: with tables, unlike the counting run); its counts, slots
+ * TS_W_* of d_sum, are read and printed at the next synchronisation of the stream */
+static int w_stats_arm(nabwa_batch *b, SearchParams &PW)
+{
+	if (!env_int("NABWA_W_STATS", 0) || PW.touch_counter) return NABWA_OK;
+	HIP_CHECK(hipMemsetAsync(b->d_sum + TS_W_TRIPS, 0, 6 * sizeof(unsigned long long), b->stream));
+	PW.touch_counter = b->d_sum; PW.text_mode |= TM_W_STATS; b->w_stats_armed = 1;
+	return NABWA_OK;
+}
+static int w_stats_collect(nabwa_batch *b)
+{
+	if (!b->w_stats_armed) return NABWA_OK;
+	b->w_stats_armed = 0;
+	unsigned long long *t = b->w_stats;
+	HIP_CHECK(hipMemcpy(t, b->d_sum + TS_W_TRIPS, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	const unsigned long long lo = 0xffffffffull;
+	fprintf(stderr, "[nabwa] width kernel: wave-trips %llu; lane-trips / positions: text %llu / %llu (in seed passes: %llu trips), table %llu / %llu, step with a rank query %llu, step without %llu; longest item %llu trips\n",
+			t[0], t[2] >> 32, t[2] & lo, t[4] >> 32, t[3] >> 32, t[3] & lo, t[4] & lo, t[5], t[1]);
+	return NABWA_OK;
+}
+/* Tests and profiles: the six words TS_W_TRIPS .. TS_W_STEP (search_slots.hpp) of the last launch of kernel W that ran with NABWA_W_STATS=1 */
+extern "C" int nabwa_batch_w_stats(nabwa_batch_t *b, unsigned long long *out)
+{
+	if (!b || !out) return nabwa_fail(NABWA_EINVAL, "bad argument");
+	memcpy(out, b->w_stats, sizeof b->w_stats);
+	return NABWA_OK;
+}
+
 extern "C" int nabwa_batch_run(nabwa_batch_t *b)
 {
 	if (!b) return nabwa_fail(NABWA_EINVAL, "null batch");
@@ -494,6 +527,7 @@ extern "C" int nabwa_batch_run(nabwa_batch_t *b)
 	HIP_CHECK(hipMemsetAsync(b->d_novf, 0, 4, b->stream));
 	HIP_CHECK(hipEventRecord(b->evw, b->stream));
 	SearchParams PW = b->P; PW.ids = 0; PW.rd_cls = b->class_sort ? b->d_cls : 0;
+	if (int r = w_stats_arm(b, PW)) return r;
 	nabwa_launch_fm_width(&PW, b->n_blocks_w, b->stream);
 	if (b->class_sort) {      /* work order of the search: reads with an exact occurrence first, in lockstep waves */
 		HIP_CHECK(hipMemsetAsync(b->d_ncls, 0, NCLS_WORDS * sizeof(unsigned int), b->stream));
@@ -623,6 +657,7 @@ static int sync_searches(nabwa_batch_t *b, int *n_second_pass)
 	unsigned int novf = 0;
 	HIP_CHECK(hipMemcpyAsync(&novf, b->d_novf, 4, hipMemcpyDeviceToHost, b->stream));
 	HIP_CHECK(hipStreamSynchronize(b->stream));
+	if (int r = w_stats_collect(b)) return r;
 	HIP_CHECK(hipEventElapsedTime(&b->last_ms, b->ev0, b->ev1));
 	HIP_CHECK(hipEventElapsedTime(&b->last_ms_w, b->evw, b->ev0));
 	if (n_second_pass) *n_second_pass = (int)novf;
@@ -692,6 +727,7 @@ extern "C" int nabwa_batch_width_records(nabwa_batch_t *b, int first, int n, uin
 	}
 	HIP_CHECK(hipMemsetAsync(b->d_counter, 0, WC_WORDS * sizeof(unsigned int), b->stream));
 	SearchParams PW = b->P; PW.ids = 0; PW.rd_cls = 0; PW.touch_counter = 0;
+	if (int r = w_stats_arm(b, PW)) return r;
 	nabwa_launch_fm_width(&PW, b->n_blocks_w, b->stream);
 	HIP_CHECK(hipGetLastError());
 	/* first and n are the caller's read indices: with a map (NABWA_DEDUP) the records of all reads searched come down and are picked from */
@@ -701,6 +737,7 @@ extern "C" int nabwa_batch_width_records(nabwa_batch_t *b, int first, int n, uin
 	if (b->d_map) HIP_CHECK(hipMemcpyAsync(src.data(), b->d_map + first, (size_t)n * 4, hipMemcpyDeviceToHost, b->stream));
 	HIP_CHECK(hipMemcpyAsync(rec.data(), b->d_wdata + rec0 * b->P.wstride, rec.size(), hipMemcpyDeviceToHost, b->stream));
 	HIP_CHECK(hipStreamSynchronize(b->stream));
+	if (int r = w_stats_collect(b)) return r;
 	const int W = b->max_len + 1, SW = b->opt.seed_len + 1;
 	for (int i = 0; i < n; ++i) {
 		const uint8_t *r = rec.data() + (size_t)(b->d_map ? src[i] : i) * b->P.wstride;

@@ -39,6 +39,7 @@ struct nabwa_batch {
 	// wide pass (allocated on demand)
 	int n2 = 0, aln_cap2 = 0; PoolBuf<uint8_t> d_scratch2; size_t scratch2_bytes = 0; PoolBuf<int32_t> d_naln2, d_maxent2; PoolBuf<uint8_t> d_status2; PoolBuf<uint4> d_aln2;
 	int unresolved = 0;
+	int w_stats_armed = 0; unsigned long long w_stats[6] = { 0, 0, 0, 0, 0, 0 };      /* NABWA_W_STATS: slots TS_W_TRIPS .. TS_W_STEP of kernel W's last launch with statistics */
 	PoolBuf<unsigned long long> d_sum;
 	// kernel D (deep searches): page pool, per-wave page lists and staging, counters; allocated on demand, kept for the next run
 	PoolBuf<uint4> d_pages; PoolBuf<uint32_t> d_page_prev, d_deep_own; PoolBuf<uint4> d_deep_stage; PoolBuf<unsigned long long> d_deep_ctr;

@@ -49,6 +49,14 @@ enum {
 	TS_LONG_TAIL   = 23,   // exact-tail steps, on rows or on the text
 	TS_LONG_JUMP   = 24,   // table jumps
 	TS_LONG_GAP    = 25,   // of all their expansions: those of entries with a gap
+	// kernel W's trip statistics (NABWA_W_STATS; the statistics instantiation of fm_width_kernel, with tables).  A text trip is a bulk trip or a text
+	// run, a table trip one of 4 or of up to 8 levels; positions do not count terminators.  The packed halves wrap at 2^32 (about 16 M reads of 100 bp).
+	TS_W_TRIPS     = 26,   // wave-trips
+	TS_W_MAX       = 27,   // the trips of the item (one strand of one read, both passes) that took most (a maximum)
+	TS_W_TEXT      = 28,   // text trips: lane-trips << 32 | positions
+	TS_W_TABLE     = 29,   // table trips: lane-trips << 32 | positions
+	TS_W_RANK      = 30,   // single steps with a rank query: lane-trips (= positions); << 32: the text trips begun in a seed pass
+	TS_W_STEP      = 31,   // single steps without one (text mode, or an N): lane-trips (= positions)
 	TS_WORDS       = 32
 };
 

@@ -685,7 +685,7 @@ void nabwa_bgzf_destroy(nabwa_bgzf_t *z);
 int nabwa_bgzf_compress_ex(int device, int codes, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
 int nabwa_bgzf_handle_compress_ex(nabwa_bgzf_t *z, int codes, const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int64_t *n_out, int64_t *n_blocks);
 
-/* ---- coordinate sort of finished BAM records on the GPU (bam_sort.hip, bam_sort_body.hpp).  Record i is
+/* ---- coordinate sort of finished BAM records on the GPU (bam_sort.hip, bam_sort_body.hpp, rec_stream.hpp).  Record i is
  * in[in_off[i] .. in_off[i + 1]) as it stands in an uncompressed BAM stream: u32 block_size, then the block (refID at byte 4 and pos at
  * byte 8 of the record, little-endian int32); the offsets are those nabwa_bam_batch_output writes.  `out` receives the same records in
  * non-decreasing key order, records of equal key in the order they had in `in` (the sort is stable); out_off (n_rec + 1, may be NULL)
@@ -710,7 +710,7 @@ int nabwa_bam_sort_run(nabwa_bam_sort_t *s, int64_t n_rec, const uint8_t *in, co
 int nabwa_bam_sort(int device, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out);
 int nabwa_bam_sort_times(const nabwa_bam_sort_t *s, float ms[6]);
 
-/* ---- damage profile of finished BAM records on the GPU (nabwa_damage.hip, damage_kernels.hip, damage_body.hpp): the
+/* ---- damage profile of finished BAM records on the GPU (nabwa_damage.hip, damage_kernels.hip, damage_body.hpp, rec_stream.hpp, rec_body.hpp): the
  * substitutions of the mapped reads against the reference by distance from the read's ends, and the read lengths.  Records and offsets are
  * those of nabwa_bam_sort.  A record falls into the first class that fits, each with its counter in stats[]:
  *   skipped_flags  flag & exclude_flags, or (flag & require_flags) != require_flags
@@ -762,7 +762,7 @@ int nabwa_damage_times(const nabwa_damage_t *d, float ms[3]);
 int nabwa_bam_sort_run_ex(nabwa_bam_sort_t *s, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out, uint32_t *perm_out);
 int nabwa_bam_sort_ex(int device, int64_t n_rec, const uint8_t *in, const int64_t *in_off, uint8_t *out, int64_t cap, int64_t *out_off, uint64_t *keys_out, uint32_t *perm_out);
 
-/* ---- duplicate marking of finished BAM records on the GPU (nabwa_markdup.hip, markdup_kernels.hip, markdup_body.hpp).
+/* ---- duplicate marking of finished BAM records on the GPU (nabwa_markdup.hip, markdup_kernels.hip, markdup_body.hpp, rec_stream.hpp, rec_body.hpp).
  * Records and offsets are those of nabwa_bam_sort.  The records get ordinals 0, 1, ... in the order they are added to a handle, across
  * calls; at most 0x7fffffff between create / clear.  A record falls into the first class that fits, each with its counter in stats[]:
  *   skipped_flags  flag & exclude_flags: never marked, in no group
@@ -815,7 +815,7 @@ void nabwa_markdup_destroy(nabwa_markdup_t *m);
 int nabwa_markdup_times(const nabwa_markdup_t *m, float ms[5]);
 
 /* ---- the BAM index (.bai, SAM specification 5.2) of finished, coordinate-sorted BAM records on the GPU (nabwa_bai.hip, bai_kernels.hip,
- * bai_body.hpp).  Records and offsets are those of nabwa_bam_sort; n_ref is the number of reference sequences of the header.
+ * bai_body.hpp, rec_stream.hpp, rec_body.hpp).  Records and offsets are those of nabwa_bam_sort; n_ref is the number of reference sequences of the header.
  * nabwa_bai_add takes records in the order of the file.  stream_off is where in[in_off[0]] lies in the uncompressed BAM stream, the header
  * included; it is not below the end of the records added before (gaps are allowed).
  * A record.  tid, pos and flag are its fields; end = pos + the lengths of its M, D, N, = and X operations, or pos + 1 with flag 0x4, without

@@ -1,10 +1,10 @@
 // bai_body.hpp -- the bodies of the BAM index (.bai, SAM specification 5.2) of finished, coordinate-sorted BAM records (bai_kernels.hip,
 // nabwa_bai*; the semantics: include/nabwa.h):
 //
-//   bai_record_part  lane t of the BAI_LANES lanes that take one record: its fields checked, its key against the record's in front of it,
+//   bai_record_part  lane t of the REC_LANES lanes that take one record: its fields checked, its key against the record's in front of it,
 //                    CIGAR operations t, t + 16, ... summed into the group's word of LDS (the cross-lane sum of the reference length)
-//   bai_block        one workgroup of the persistent grid: BAI_GROUPS records per trip; lane 0 of a group writes the record's tuple
-//   bai_ref_block    a workgroup of BAI_BLOCK tuples in stream order: both virtual offsets of each (binary search in the block table), and
+//   bai_block        one workgroup of the persistent grid: REC_GROUPS records per trip; lane 0 of a group writes the record's tuple
+//   bai_ref_block    a workgroup of REC_BLOCK tuples in stream order: both virtual offsets of each (binary search in the block table), and
 //                    per reference the highest window, the records with flag 0x4, the first and the last ordinal -- one atomic per run of
 //                    equal references in the workgroup, not one per record
 //   bai_head_one     position j of the tuples sorted by (tid, bin): does a bin start here, does a chunk
@@ -31,34 +31,15 @@
 #pragma once
 #include <stdint.h>
 #include "../../include/nabwa.h"
+#include "rec_body.hpp"        /* the macro layer, REC_LANES ... REC_MIN_REC, rec_u32, rec_op_ref, REC_HEAD */
 #ifdef NABWA_EMU
-#define BAI_FN static inline
-#define BAI_HD static inline
 #define BAI_MEMBER inline
-#define BAI_THREADS for (int tid = 0; tid < BAI_BLOCK; ++tid)
-#define BAI_SYNC ((void)0)
-#define BAI_ADD64(p, v) (*(p) += (v))
-#define BAI_ADD32(p, v) (*(p) += (v))
-#define BAI_MIN32(p, v) (*(p) = *(p) < (v) ? *(p) : (v))
-#define BAI_MAX32(p, v) (*(p) = *(p) > (v) ? *(p) : (v))
-#define BAI_MIN64(p, v) (*(p) = *(p) < (v) ? *(p) : (v))
+#define BAI_GROUPS REC_GROUPS      /* (tests/emu/bai_emu.cpp sizes its arrays by these names) */
+#define BAI_BLOCK  REC_BLOCK
 #else
-#define BAI_FN __device__ __forceinline__
-#define BAI_HD __host__ __device__ __forceinline__
 #define BAI_MEMBER __host__ __device__ __forceinline__
-#define BAI_THREADS for (int tid = (int)threadIdx.x, once_ = 1; once_; once_ = 0)
-#define BAI_SYNC __syncthreads()
-#define BAI_ADD64(p, v) ((void)atomicAdd((p), (v)))
-#define BAI_ADD32(p, v) ((void)atomicAdd((p), (v)))
-#define BAI_MIN32(p, v) ((void)atomicMin((p), (v)))
-#define BAI_MAX32(p, v) ((void)atomicMax((p), (v)))
-#define BAI_MIN64(p, v) ((void)atomicMin((p), (v)))
 #endif
 
-#define BAI_LANES      16                       /* lanes per record, as the sort's gather, the damage and the duplicate kernels */
-#define BAI_BLOCK      256
-#define BAI_GROUPS     (BAI_BLOCK / BAI_LANES)  /* records per workgroup and trip */
-#define BAI_MIN_REC    36                       /* block_size + the 32 fixed bytes of a record */
 #define BAI_MAX_END    ((int64_t)1 << 29)       /* the last coordinate a .bai addresses */
 #define BAI_PSEUDO_BIN 37450u
 #define BAI_KEY_NONE   (~(uint64_t)0)
@@ -97,10 +78,8 @@ struct BaiFin {
 	uint32_t *out;
 };
 
-BAI_FN uint32_t bai_u32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-BAI_HD bool bai_op_ref(uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }     /* M D N = X */
 /* reg2bin of the specification, for [beg, end) with 0 <= beg < end <= 2^29 */
-BAI_HD uint32_t bai_reg2bin(int64_t beg, int64_t end)
+REC_HD uint32_t bai_reg2bin(int64_t beg, int64_t end)
 {
 	--end;
 	if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
@@ -111,63 +90,57 @@ BAI_HD uint32_t bai_reg2bin(int64_t beg, int64_t end)
 	return 0;
 }
 /* a record's end from its fields and the reference length of its CIGAR */
-BAI_HD int64_t bai_end(int32_t pos, uint32_t flag, uint32_t n_cig, uint64_t ref_len)
+REC_HD int64_t bai_end(int32_t pos, uint32_t flag, uint32_t n_cig, uint64_t ref_len)
 {
 	return (flag & 4u) || n_cig == 0 || ref_len == 0 ? (int64_t)pos + 1 : (int64_t)pos + (int64_t)ref_len;
 }
 
-/* lane t of the group of record i, `rec` of `size` >= BAI_MIN_REC bytes; prev: the record in front of it, or null for the call's first.
+/* lane t of the group of record i, `rec` of `size` >= REC_MIN_REC bytes; prev: the record in front of it, or null for the call's first.
  * sum: the group's word of LDS (zero).  BAI_BAD for a record that is damaged whatever its CIGAR says (every lane says so, before any lane
  * has touched sum), else BAI_OK */
-BAI_FN int bai_record_part(const BaiParams &P, const uint8_t *rec, int64_t size, const uint8_t *prev, int t, unsigned long long *sum)
+REC_FN int bai_record_part(const BaiParams &P, const uint8_t *rec, int64_t size, const uint8_t *prev, int t, unsigned long long *sum)
 {
-	if ((int64_t)bai_u32(rec) + 4 != size) return BAI_BAD;
-	const int32_t ref_id = (int32_t)bai_u32(rec + 4), pos = (int32_t)bai_u32(rec + 8);
-	const uint32_t w12 = bai_u32(rec + 12), w16 = bai_u32(rec + 16);
-	const uint32_t l_name = w12 & 0xffu, n_cig = w16 & 0xffffu, flag = w16 >> 16;
-	const uint64_t L = bai_u32(rec + 20);
-	if ((uint64_t)BAI_MIN_REC + l_name + 4 * (uint64_t)n_cig + (L + 1) / 2 + L > (uint64_t)size) return BAI_BAD;
+	REC_HEAD(rec, size, BAI_BAD);
 	if (ref_id >= P.n_ref || (ref_id >= 0 && pos < 0)) return BAI_BAD;
-	const uint64_t before = prev ? NABWA_BAM_SORT_KEY((int32_t)bai_u32(prev + 4), (int32_t)bai_u32(prev + 8)) : P.last_key;
+	const uint64_t before = prev ? NABWA_BAM_SORT_KEY((int32_t)rec_u32(prev + 4), (int32_t)rec_u32(prev + 8)) : P.last_key;
 	if (NABWA_BAM_SORT_KEY(ref_id, pos) < before) return BAI_BAD;
 	if (ref_id >= 0 && !(flag & 4u)) {
-		const uint8_t *cig = rec + BAI_MIN_REC + l_name;
+		const uint8_t *cig = rec + REC_MIN_REC + l_name;
 		uint64_t s = 0;                         /* (operations of 28 bits, at most 65535 of them: no sum leaves 64 bits) */
-		for (uint32_t c = (uint32_t)t; c < n_cig; c += BAI_LANES) { const uint32_t w = bai_u32(cig + 4 * c); if (bai_op_ref(w & 15u)) s += w >> 4; }
-		if (s) BAI_ADD64(sum, (unsigned long long)s);
+		for (uint32_t c = (uint32_t)t; c < n_cig; c += REC_LANES) { const uint32_t w = rec_u32(cig + 4 * c); if (rec_op_ref(w & 15u)) s += w >> 4; }
+		if (s) REC_ADD64(sum, (unsigned long long)s);
 	}
 	return BAI_OK;
 }
 
-/* workgroup `block` of `n_blocks`: trips block, block + n_blocks, ... of BAI_GROUPS records each.  sum, state: BAI_GROUPS words of LDS each */
-BAI_FN void bai_block(const BaiParams &P, unsigned long long *sum, uint32_t *state, int block, int n_blocks)
+/* workgroup `block` of `n_blocks`: trips block, block + n_blocks, ... of REC_GROUPS records each.  sum, state: REC_GROUPS words of LDS each */
+REC_FN void bai_block(const BaiParams &P, unsigned long long *sum, uint32_t *state, int block, int n_blocks)
 {
-	BAI_THREADS { if (tid < BAI_GROUPS) { sum[tid] = 0; state[tid] = BAI_ST_IDLE; } }
-	BAI_SYNC;
-	for (int64_t first = (int64_t)block * BAI_GROUPS; first < P.n_rec; first += (int64_t)n_blocks * BAI_GROUPS) {
-		BAI_THREADS {
-			const int g = tid / BAI_LANES, t = tid % BAI_LANES;
+	REC_THREADS { if (tid < REC_GROUPS) { sum[tid] = 0; state[tid] = BAI_ST_IDLE; } }
+	REC_SYNC;
+	for (int64_t first = (int64_t)block * REC_GROUPS; first < P.n_rec; first += (int64_t)n_blocks * REC_GROUPS) {
+		REC_THREADS {
+			const int g = tid / REC_LANES, t = tid % REC_LANES;
 			const int64_t i = first + g;
 			if (i < P.n_rec) {
 				const int64_t o = P.off[i];
 				const int r = bai_record_part(P, P.in + (o - P.base), P.off[i + 1] - o, i ? P.in + (P.off[i - 1] - P.base) : (const uint8_t*)0, t, sum + g);
-				if (t == 0) { state[g] = r == BAI_OK ? BAI_ST_OK : BAI_ST_BAD; if (r != BAI_OK) BAI_MIN32(P.cnt, (unsigned int)i); }
+				if (t == 0) { state[g] = r == BAI_OK ? BAI_ST_OK : BAI_ST_BAD; if (r != BAI_OK) REC_MIN32(P.cnt, (unsigned int)i); }
 			}
 		}
-		BAI_SYNC;
-		BAI_THREADS {                                   /* the group's sum is whole: the record's end, bin and tuple, and the words as they were */
-			const int g = tid / BAI_LANES;
+		REC_SYNC;
+		REC_THREADS {                                   /* the group's sum is whole: the record's end, bin and tuple, and the words as they were */
+			const int g = tid / REC_LANES;
 			const int64_t i = first + g;
-			if (tid % BAI_LANES == 0 && i < P.n_rec) {
+			if (tid % REC_LANES == 0 && i < P.n_rec) {
 				if (state[g] == BAI_ST_OK) {
 					const int64_t o = P.off[i];
 					const uint8_t *rec = P.in + (o - P.base);
-					const int32_t ref_id = (int32_t)bai_u32(rec + 4), pos = (int32_t)bai_u32(rec + 8);
-					const uint32_t w16 = bai_u32(rec + 16), flag = w16 >> 16;
-					const int64_t end = bai_end(pos, flag, w16 & 0xffffu, sum[g]);
+					REC_FIELDS(rec);                    /* (it has passed REC_HEAD: the fields alone) */
+					const int64_t end = bai_end(pos, flag, n_cig, sum[g]);
 					const int64_t us = P.stream_off + (o - P.base);
-					if (ref_id < 0) { P.key[i] = BAI_KEY_NONE; P.be[i] = 0; BAI_ADD32(P.cnt + 1, 1u); }
-					else if (end > BAI_MAX_END) BAI_MIN32(P.cnt, (unsigned int)i);
+					if (ref_id < 0) { P.key[i] = BAI_KEY_NONE; P.be[i] = 0; REC_ADD32(P.cnt + 1, 1u); }
+					else if (end > BAI_MAX_END) REC_MIN32(P.cnt, (unsigned int)i);
 					else { P.key[i] = (uint64_t)(uint32_t)ref_id << 16 | bai_reg2bin(pos, end); P.be[i] = (uint64_t)end << 32 | (uint32_t)pos; }
 					P.us[i] = us;
 					P.ue[i] = (uint64_t)(us + (P.off[i + 1] - o)) | ((flag & 4u) ? BAI_UNMAPPED : 0);
@@ -175,23 +148,23 @@ BAI_FN void bai_block(const BaiParams &P, unsigned long long *sum, uint32_t *sta
 				sum[g] = 0; state[g] = BAI_ST_IDLE;
 			}
 		}
-		BAI_SYNC;
+		REC_SYNC;
 	}
 }
 
 /* the virtual offset of stream offset u, blk_u[0] <= u <= blk_u[n_blk]: the last block that starts at or before u */
-BAI_FN uint64_t bai_voff(const BaiFin &F, int64_t u)
+REC_FN uint64_t bai_voff(const BaiFin &F, int64_t u)
 {
 	int64_t lo = 0, hi = F.n_blk + 1;
 	while (hi - lo > 1) { const int64_t mid = lo + (hi - lo) / 2; if (F.blk_u[mid] <= u) lo = mid; else hi = mid; }
 	return (uint64_t)F.blk_c[lo] << 16 | (uint64_t)(u - F.blk_u[lo]);
 }
 
-/* workgroup `block`: tuples block * BAI_BLOCK ... in stream order.  l_tid, l_win, l_unm: BAI_BLOCK words of LDS each */
-BAI_FN void bai_ref_block(const BaiFin &F, int *l_tid, int *l_win, unsigned int *l_unm, int64_t block)
+/* workgroup `block`: tuples block * REC_BLOCK ... in stream order.  l_tid, l_win, l_unm: REC_BLOCK words of LDS each */
+REC_FN void bai_ref_block(const BaiFin &F, int *l_tid, int *l_win, unsigned int *l_unm, int64_t block)
 {
-	BAI_THREADS {
-		const int64_t o = block * BAI_BLOCK + tid;
+	REC_THREADS {
+		const int64_t o = block * REC_BLOCK + tid;
 		l_tid[tid] = -1;
 		if (o < F.n) {
 			const uint64_t ue = F.ue[o];
@@ -202,16 +175,16 @@ BAI_FN void bai_ref_block(const BaiFin &F, int *l_tid, int *l_win, unsigned int 
 			l_unm[tid] = (unsigned int)(ue >> 63);
 		}
 	}
-	BAI_SYNC;
-	BAI_THREADS {
-		const int64_t o = block * BAI_BLOCK + tid;
+	REC_SYNC;
+	REC_THREADS {
+		const int64_t o = block * REC_BLOCK + tid;
 		const int r = l_tid[tid];
 		if (r >= 0 && (tid == 0 || l_tid[tid - 1] != r)) {     /* the first of a run of one reference in this workgroup: the run's maximum and count */
 			int win = l_win[tid]; unsigned int unm = l_unm[tid];
 			int k = tid + 1;
-			for (; k < BAI_BLOCK && l_tid[k] == r; ++k) { win = l_win[k] > win ? l_win[k] : win; unm += l_unm[k]; }
-			BAI_MAX32(F.maxwin + r, win);
-			if (unm) BAI_ADD32(F.unm + r, unm);
+			for (; k < REC_BLOCK && l_tid[k] == r; ++k) { win = l_win[k] > win ? l_win[k] : win; unm += l_unm[k]; }
+			REC_MAX32(F.maxwin + r, win);
+			if (unm) REC_ADD32(F.unm + r, unm);
 			if (o == 0 || (int)(F.key[o - 1] >> 16) != r) F.o0[r] = (unsigned int)o;
 			const int64_t last = o + (k - tid) - 1;
 			if (last == F.n - 1 || (int)(F.key[last + 1] >> 16) != r) F.o1[r] = (unsigned int)last;
@@ -219,14 +192,14 @@ BAI_FN void bai_ref_block(const BaiFin &F, int *l_tid, int *l_win, unsigned int 
 	}
 }
 
-BAI_FN void bai_head_one(const BaiFin &F, int64_t j)
+REC_FN void bai_head_one(const BaiFin &F, int64_t j)
 {
 	const bool hb = j == 0 || F.skey[j - 1] != F.skey[j];
 	const bool hc = hb || (F.ve[F.sidx[j - 1]] >> 16) != (F.vb[F.sidx[j]] >> 16);
 	F.heads[j] = (unsigned long long)hb << 32 | (unsigned long long)hc;
 }
 
-BAI_FN void bai_place_one(const BaiFin &F, int64_t j)
+REC_FN void bai_place_one(const BaiFin &F, int64_t j)
 {
 	const unsigned long long sc = F.sc[j];
 	const unsigned int b = (unsigned int)(sc >> 32) - 1, c = (unsigned int)sc - 1;
@@ -239,7 +212,7 @@ BAI_FN void bai_place_one(const BaiFin &F, int64_t j)
 }
 
 /* reference r of n_ref + 1: the last is the end of both sums */
-BAI_FN void bai_refsize_one(const BaiFin &F, int64_t r)
+REC_FN void bai_refsize_one(const BaiFin &F, int64_t r)
 {
 	unsigned long long size = 0, nintv = 0;
 	if (r < F.n_ref) {
@@ -252,12 +225,12 @@ BAI_FN void bai_refsize_one(const BaiFin &F, int64_t r)
 	F.ref_size[r] = size; F.ref_nintv[r] = nintv;
 }
 
-BAI_FN void bai_lin_one(const BaiFin &F, int64_t o)
+REC_FN void bai_lin_one(const BaiFin &F, int64_t o)
 {
 	const uint64_t be = F.be[o];
 	const int64_t beg = (int64_t)(uint32_t)be, end = (int64_t)(be >> 32);
 	const unsigned long long base = F.lin_off[F.key[o] >> 16], v = F.vb[o];
-	for (int64_t w = beg >> 14; w <= (end - 1) >> 14; ++w) BAI_MIN64(F.lin + (F.n_lin - 1 - (int64_t)(base + (unsigned long long)w)), v);
+	for (int64_t w = beg >> 14; w <= (end - 1) >> 14; ++w) REC_MIN64(F.lin + (F.n_lin - 1 - (int64_t)(base + (unsigned long long)w)), v);
 }
 
 /* over the reversed table, front to back: an untouched window takes what the window before it (the next one of the file) came to.  The
@@ -266,10 +239,10 @@ struct BaiNextTouched {
 	BAI_MEMBER unsigned long long operator()(unsigned long long a, unsigned long long b) const { return b != BAI_UNTOUCHED ? b : a; }
 };
 
-BAI_FN void bai_put64(uint32_t *out, unsigned long long at, unsigned long long v) { out[at / 4] = (uint32_t)v; out[at / 4 + 1] = (uint32_t)(v >> 32); }
+REC_FN void bai_put64(uint32_t *out, unsigned long long at, unsigned long long v) { out[at / 4] = (uint32_t)v; out[at / 4 + 1] = (uint32_t)(v >> 32); }
 
 /* reference r of n_ref + 1: its bin count, its pseudo-bin, its window count; the last writes the header and the trailer */
-BAI_FN void bai_write_ref(const BaiFin &F, int64_t r)
+REC_FN void bai_write_ref(const BaiFin &F, int64_t r)
 {
 	if (r == F.n_ref) {
 		F.out[0] = 0x01494142u; F.out[1] = (uint32_t)F.n_ref;       /* "BAI\1" */
@@ -288,7 +261,7 @@ BAI_FN void bai_write_ref(const BaiFin &F, int64_t r)
 }
 
 /* position j of the sorted tuples: the head of a bin writes the bin's number and chunk count, the head of a chunk its start, its last its end */
-BAI_FN void bai_write_tuple(const BaiFin &F, int64_t j)
+REC_FN void bai_write_tuple(const BaiFin &F, int64_t j)
 {
 	const unsigned long long sc = F.sc[j], h = F.heads[j];
 	const unsigned int b = (unsigned int)(sc >> 32) - 1, c = (unsigned int)sc - 1;
@@ -304,7 +277,7 @@ BAI_FN void bai_write_tuple(const BaiFin &F, int64_t j)
 }
 
 /* window g of all references' windows back to back */
-BAI_FN void bai_write_lin(const BaiFin &F, int64_t g)
+REC_FN void bai_write_lin(const BaiFin &F, int64_t g)
 {
 	int64_t lo = 0, hi = F.n_ref;                       /* the last reference whose windows start at or before g */
 	while (hi - lo > 1) { const int64_t mid = lo + (hi - lo) / 2; if (F.lin_off[mid] <= (unsigned long long)g) lo = mid; else hi = mid; }

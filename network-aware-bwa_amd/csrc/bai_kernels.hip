@@ -1,9 +1,9 @@
 // bai_kernels.hip -- the kernels of the BAM index (bodies: bai_body.hpp; host side: nabwa_bai.hip).
 //
-//   bai_sig_kernel         a persistent grid of workgroups of BAI_BLOCK threads, BAI_LANES lanes per record, the CIGAR's operations split over
+//   bai_sig_kernel         a persistent grid of workgroups of REC_BLOCK threads, REC_LANES lanes per record, the CIGAR's operations split over
 //                          the lanes: every record's tuple into the arena, the lowest damaged record and the records without a reference counted
 //   bai_iota_kernel        the ordinals beside the keys of the radix sort
-//   bai_ref_kernel         a workgroup per BAI_BLOCK tuples in stream order: virtual offsets, and what a reference's pseudo-bin and window count need
+//   bai_ref_kernel         a workgroup per REC_BLOCK tuples in stream order: virtual offsets, and what a reference's pseudo-bin and window count need
 //   bai_head_kernel, bai_place_kernel    one lane per sorted tuple: bin and chunk heads; where bins and chunks start once the heads are scanned
 //   bai_refsize_kernel     one lane per reference: the bytes and windows of its part
 //   bai_lin_kernel         one lane per tuple: its virtual start into the windows it touches
@@ -12,10 +12,10 @@
 #include "launchers.hpp"
 #include "bai_body.hpp"
 
-__global__ __launch_bounds__(BAI_BLOCK) void bai_sig_kernel(const BaiParams P)
+__global__ __launch_bounds__(REC_BLOCK) void bai_sig_kernel(const BaiParams P)
 {
-	__shared__ unsigned long long sum[BAI_GROUPS];
-	__shared__ uint32_t state[BAI_GROUPS];
+	__shared__ unsigned long long sum[REC_GROUPS];
+	__shared__ uint32_t state[REC_GROUPS];
 	bai_block(P, sum, state, (int)blockIdx.x, (int)gridDim.x);
 }
 
@@ -25,10 +25,10 @@ __global__ __launch_bounds__(256) void bai_iota_kernel(int64_t n, uint32_t *__re
 	if (j < n) idx[j] = (uint32_t)j;
 }
 
-__global__ __launch_bounds__(BAI_BLOCK) void bai_ref_kernel(const BaiFin F)
+__global__ __launch_bounds__(REC_BLOCK) void bai_ref_kernel(const BaiFin F)
 {
-	__shared__ int l_tid[BAI_BLOCK], l_win[BAI_BLOCK];
-	__shared__ unsigned int l_unm[BAI_BLOCK];
+	__shared__ int l_tid[REC_BLOCK], l_win[REC_BLOCK];
+	__shared__ unsigned int l_unm[REC_BLOCK];
 	bai_ref_block(F, l_tid, l_win, l_unm, (int64_t)blockIdx.x);
 }
 
@@ -51,7 +51,7 @@ static inline dim3 grid_of(int64_t n) { return dim3((unsigned int)((n + 255) / 2
 extern "C" {
 void nabwa_launch_bai_sig(const BaiParams *P, int n_blocks, hipStream_t s)
 {
-	hipLaunchKernelGGL(bai_sig_kernel, dim3(n_blocks), dim3(BAI_BLOCK), 0, s, *P);
+	hipLaunchKernelGGL(bai_sig_kernel, dim3(n_blocks), dim3(REC_BLOCK), 0, s, *P);
 }
 void nabwa_launch_bai_iota(int64_t n, uint32_t *idx, hipStream_t s)
 {
@@ -60,7 +60,7 @@ void nabwa_launch_bai_iota(int64_t n, uint32_t *idx, hipStream_t s)
 void nabwa_launch_bai_step(int step, const BaiFin *F, hipStream_t s)
 {
 	switch (step) {
-		case NABWA_BAI_STEP_REF: hipLaunchKernelGGL(bai_ref_kernel, dim3((unsigned int)((F->n + BAI_BLOCK - 1) / BAI_BLOCK)), dim3(BAI_BLOCK), 0, s, *F); break;
+		case NABWA_BAI_STEP_REF: hipLaunchKernelGGL(bai_ref_kernel, dim3((unsigned int)((F->n + REC_BLOCK - 1) / REC_BLOCK)), dim3(REC_BLOCK), 0, s, *F); break;
 		case NABWA_BAI_STEP_HEAD: hipLaunchKernelGGL(bai_head_kernel, grid_of(F->n), dim3(256), 0, s, *F); break;
 		case NABWA_BAI_STEP_PLACE: hipLaunchKernelGGL(bai_place_kernel, grid_of(F->n), dim3(256), 0, s, *F); break;
 		case NABWA_BAI_STEP_REFSIZE: hipLaunchKernelGGL(bai_refsize_kernel, grid_of((int64_t)F->n_ref + 1), dim3(256), 0, s, *F); break;

@@ -2,7 +2,7 @@
 //
 //   bsort_u32        a little-endian word at any byte address, read byte by byte (a record starts wherever the one before it ended)
 //   bsort_key        the sort key of the record at `rec`: NABWA_BAM_SORT_KEY(refID, pos), refID at byte 4 and pos at byte 8
-//   bsort_copy_part  lane t of the BSORT_LANES lanes that copy one record of n bytes from src to dst, both at any byte alignment
+//   bsort_copy_part  lane t of the REC_LANES lanes that copy one record of n bytes from src to dst, both at any byte alignment
 //
 // The copy: the bytes up to dst's first 16-byte boundary go singly (lane t takes byte t), then whole 16-byte chunks, chunk c by lane
 // c mod 16 -- the store is a 16-byte aligned one, the load takes its 16 bytes from wherever the source has them (the hardware reads a
@@ -21,9 +21,10 @@
 #include <hip/hip_runtime.h>
 #define BSORT_FN __device__ __forceinline__
 #endif
-
-#define BSORT_LANES   16      /* lanes per record in the gather, as the dedup stage's hash and compaction */
-#define BSORT_MIN_REC 36      /* block_size + the 32 fixed bytes of a record */
+#include "rec_body.hpp"        /* REC_LANES, the lanes per record in the gather, and REC_MIN_REC; nothing else of it */
+#ifdef NABWA_EMU
+#define BSORT_LANES REC_LANES      /* (tests/emu/bam_sort_emu.cpp counts its lanes by this name) */
+#endif
 
 BSORT_FN uint32_t bsort_u32(const uint8_t *p)
 {
@@ -41,7 +42,7 @@ BSORT_FN void bsort_copy_part(const uint8_t *src, uint8_t *dst, int64_t n, int t
 	if (head > n) head = n;
 	if (t < head) dst[t] = src[t];
 	const int64_t n_chunks = (n - head) >> 4;
-	for (int64_t c = t; c < n_chunks; c += BSORT_LANES) {
+	for (int64_t c = t; c < n_chunks; c += REC_LANES) {
 		uint32_t w[4];
 		__builtin_memcpy(w, src + head + 16 * c, 16);
 		__builtin_memcpy(__builtin_assume_aligned(dst + head + 16 * c, 16), w, 16);

@@ -1,10 +1,10 @@
 // damage_body.hpp -- the bodies of the damage profile of finished BAM records (damage_kernels.hip, nabwa_damage*; the
 // semantics: include/nabwa.h):
 //
-//   dmg_record_part  lane t of the DMG_LANES lanes that take one record: its fields, its class, the CIGAR walked twice -- once for what it
+//   dmg_record_part  lane t of the REC_LANES lanes that take one record: its fields, its class, the CIGAR walked twice -- once for what it
 //                    consumes (a CIGAR that does not consume l_seq read bases is damage) and for the holes under its reference span, once
 //                    for the columns -- and the counts into the workgroup's table
-//   dmg_block        one workgroup of the persistent grid: DMG_GROUPS records per trip, the table flushed into the call's 64-bit table
+//   dmg_block        one workgroup of the persistent grid: REC_GROUPS records per trip, the table flushed into the call's 64-bit table
 //
 // A record starts at any byte, so nothing in it is aligned; the hardware reads a global word at any byte address.  The fields come as 32-bit
 // words.  An M run's columns go to the lanes in pieces of DMG_COLS = 8: lane t takes pieces t, t + 16, ...; a piece's read bases (2 per byte, at
@@ -28,31 +28,9 @@
 #include <stdint.h>
 #include "../../include/nabwa.h"
 #include "finish_body.hpp"          /* FinRef, FinHole, fin_pac_at */
-#ifdef NABWA_EMU
-#define DMG_FN static inline
-#define DMG_HD static inline
-#define DMG_THREADS for (int tid = 0; tid < DMG_BLOCK; ++tid)
-#define DMG_SYNC ((void)0)
-#define DMG_INC(p) (++*(p))
-#define DMG_ADD(p, v) (*(p) += (v))
-#define DMG_ADD64(p, v) (*(p) += (v))
-#define DMG_MIN(p, v) (*(p) = *(p) < (v) ? *(p) : (v))
-#else
-#define DMG_FN __device__ __forceinline__
-#define DMG_HD __host__ __device__ __forceinline__
-#define DMG_THREADS for (int tid = (int)threadIdx.x, once_ = 1; once_; once_ = 0)
-#define DMG_SYNC __syncthreads()
-#define DMG_INC(p) ((void)atomicAdd((p), 1u))
-#define DMG_ADD(p, v) ((void)atomicAdd((p), (v)))
-#define DMG_ADD64(p, v) ((void)atomicAdd((p), (v)))
-#define DMG_MIN(p, v) ((void)atomicMin((p), (v)))
-#endif
+#include "rec_body.hpp"        /* the macro layer, REC_LANES ... REC_MIN_REC, rec_u32, rec_op_read / rec_op_ref, REC_HEAD */
 
-#define DMG_LANES   16                          /* lanes per record, as the sort's gather */
-#define DMG_BLOCK   256
-#define DMG_GROUPS  (DMG_BLOCK / DMG_LANES)     /* records per workgroup and trip */
 #define DMG_COLS    8                           /* columns per lane and piece */
-#define DMG_MIN_REC 36                          /* block_size + the 32 fixed bytes of a record */
 #ifndef DMG_FLUSH_BYTES
 #define DMG_FLUSH_BYTES 0x100000000ull          /* (the emulation also runs with a small value, to take every path of dmg_block) */
 #endif
@@ -62,7 +40,7 @@
 /* the table of n_pos, in words: sub5 at 0, sub3 at sub3, the length bins at len, the stats at stats; `words` in all.  The workgroup's table
  * (32-bit), the call's and the handle's (64-bit) share it. */
 struct DmgTab { int32_t sub3, len, stats, words; };
-DMG_HD DmgTab dmg_tab(int n_pos)
+REC_HD DmgTab dmg_tab(int n_pos)
 {
 	DmgTab t; t.sub3 = (n_pos + 1) * 16; t.len = 2 * t.sub3; t.stats = t.len + NABWA_DAMAGE_LEN_BINS; t.words = t.stats + NABWA_DAMAGE_N_STATS;
 	return t;
@@ -76,9 +54,8 @@ struct DmgParams {
 	int32_t n_pos, min_mapq; uint32_t exclude_flags, require_flags;
 };
 
-DMG_FN uint32_t dmg_u32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 /* the `need` (1..8) bytes at p, little-endian, of which `avail` exist (the rest reads as 0): one 8-byte load where 8 exist */
-DMG_FN uint64_t dmg_load(const uint8_t *p, int64_t avail, int need)
+REC_FN uint64_t dmg_load(const uint8_t *p, int64_t avail, int need)
 {
 	uint64_t w = 0;
 	if (avail >= 8) { __builtin_memcpy(&w, p, 8); return w; }
@@ -86,36 +63,29 @@ DMG_FN uint64_t dmg_load(const uint8_t *p, int64_t avail, int need)
 	for (int b = 0; b < n; ++b) w |= (uint64_t)p[b] << (8 * b);
 	return w;
 }
-DMG_FN bool dmg_op_read(uint32_t op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }     /* M I S = X */
-DMG_FN bool dmg_op_ref(uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }      /* M D N = X */
-DMG_FN bool dmg_op_col(uint32_t op) { return op == 0 || op == 7 || op == 8; }                            /* M = X */
+REC_FN bool dmg_op_col(uint32_t op) { return op == 0 || op == 7 || op == 8; }                            /* M = X */
 
-/* lane t of the group of record `rec` of `size` >= DMG_MIN_REC bytes; tab: the workgroup's table.  DMG_BAD for a damaged record (every lane
+/* lane t of the group of record `rec` of `size` >= REC_MIN_REC bytes; tab: the workgroup's table.  DMG_BAD for a damaged record (every lane
  * says so, nothing is counted), else DMG_OK */
-DMG_FN int dmg_record_part(const DmgParams &P, const DmgTab &T, const uint8_t *rec, int64_t size, int t, uint32_t *tab)
+REC_FN int dmg_record_part(const DmgParams &P, const DmgTab &T, const uint8_t *rec, int64_t size, int t, uint32_t *tab)
 {
-	if ((int64_t)dmg_u32(rec) + 4 != size) return DMG_BAD;
-	const int32_t ref_id = (int32_t)dmg_u32(rec + 4), pos = (int32_t)dmg_u32(rec + 8);
-	const uint32_t w12 = dmg_u32(rec + 12), w16 = dmg_u32(rec + 16);
-	const uint32_t l_name = w12 & 0xffu, mapq = w12 >> 8 & 0xffu, n_cig = w16 & 0xffffu, flag = w16 >> 16;
-	const uint64_t L = dmg_u32(rec + 20);
-	if ((uint64_t)DMG_MIN_REC + l_name + 4 * (uint64_t)n_cig + (L + 1) / 2 + L > (uint64_t)size) return DMG_BAD;
+	REC_HEAD(rec, size, DMG_BAD);
 	int cls = NABWA_DAMAGE_STAT_COUNTED;
 	if ((flag & P.exclude_flags) || (flag & P.require_flags) != P.require_flags) cls = NABWA_DAMAGE_STAT_SKIPPED_FLAGS;
 	else if (ref_id < 0 || ref_id >= P.n_contigs || pos < 0) cls = NABWA_DAMAGE_STAT_SKIPPED_PLACE;
 	else if ((int32_t)mapq < P.min_mapq) cls = NABWA_DAMAGE_STAT_SKIPPED_MAPQ;
 	else if (L == 0 || n_cig == 0) cls = NABWA_DAMAGE_STAT_SKIPPED_EMPTY;
 	if (cls != NABWA_DAMAGE_STAT_COUNTED) {
-		if (t == 0) { DMG_INC(tab + T.stats + NABWA_DAMAGE_STAT_SEEN); DMG_INC(tab + T.stats + cls); }
+		if (t == 0) { REC_INC(tab + T.stats + NABWA_DAMAGE_STAT_SEEN); REC_INC(tab + T.stats + cls); }
 		return DMG_OK;
 	}
-	const uint8_t *cig = rec + DMG_MIN_REC + l_name, *seq = cig + 4 * n_cig, *end = rec + size;
+	const uint8_t *cig = rec + REC_MIN_REC + l_name, *seq = cig + 4 * n_cig, *end = rec + size;
 	/* what the CIGAR consumes (operations of 28 bits, at most 65535 of them: no sum leaves 64 bits) */
 	uint64_t n_read = 0, n_ref = 0;
 	for (uint32_t c = 0; c < n_cig; ++c) {
-		const uint32_t w = dmg_u32(cig + 4 * c), op = w & 15u, len = w >> 4;
-		if (dmg_op_read(op)) n_read += len;
-		if (dmg_op_ref(op)) n_ref += len;
+		const uint32_t w = rec_u32(cig + 4 * c), op = w & 15u, len = w >> 4;
+		if (rec_op_read(op)) n_read += len;
+		if (rec_op_ref(op)) n_ref += len;
 	}
 	if (n_read != L) return DMG_BAD;
 	const int64_t rp = P.contig_off[ref_id] + pos, rp_end = rp + (int64_t)n_ref, l_pac = P.R.l_pac, pac_bytes = l_pac / 4 + 1;
@@ -130,10 +100,10 @@ DMG_FN int dmg_record_part(const DmgParams &P, const DmgTab &T, const uint8_t *r
 	uint32_t n_cols = 0, n_skip_read = 0, n_skip_ref = 0;
 	int64_t qi = 0, k = rp;
 	for (uint32_t c = 0; c < n_cig; ++c) {
-		const uint32_t w = dmg_u32(cig + 4 * c), op = w & 15u;
+		const uint32_t w = rec_u32(cig + 4 * c), op = w & 15u;
 		const int64_t len = (int64_t)(w >> 4);
 		if (dmg_op_col(op)) {
-			for (int64_t at = (int64_t)DMG_COLS * t; at < len; at += DMG_COLS * DMG_LANES) {
+			for (int64_t at = (int64_t)DMG_COLS * t; at < len; at += DMG_COLS * REC_LANES) {
 				const int64_t qs = qi + at, ks = k + at;
 				const int nc = len - at < DMG_COLS ? (int)(len - at) : DMG_COLS;
 				const uint8_t *sp = seq + (qs >> 1);
@@ -153,51 +123,51 @@ DMG_FN int dmg_record_part(const DmgParams &P, const DmgTab &T, const uint8_t *r
 					int64_t d5 = qs + j, d3 = (int64_t)L - 1 - d5;
 					if (rev) { r = 3u - r; q = 3u - q; const int64_t x = d5; d5 = d3; d3 = x; }
 					const int p5 = d5 < P.n_pos ? (int)d5 : P.n_pos, p3 = d3 < P.n_pos ? (int)d3 : P.n_pos;
-					DMG_INC(tab + (p5 * 4 + (int)r) * 4 + (int)q);
-					DMG_INC(tab + T.sub3 + (p3 * 4 + (int)r) * 4 + (int)q);
+					REC_INC(tab + (p5 * 4 + (int)r) * 4 + (int)q);
+					REC_INC(tab + T.sub3 + (p3 * 4 + (int)r) * 4 + (int)q);
 					++n_cols;
 				}
 			}
 		}
-		if (dmg_op_read(op)) qi += len;
-		if (dmg_op_ref(op)) k += len;
+		if (rec_op_read(op)) qi += len;
+		if (rec_op_ref(op)) k += len;
 	}
-	if (n_cols) DMG_ADD(tab + T.stats + NABWA_DAMAGE_STAT_COLUMNS_COUNTED, n_cols);
-	if (n_skip_read) DMG_ADD(tab + T.stats + NABWA_DAMAGE_STAT_COLUMNS_SKIPPED_READ, n_skip_read);
-	if (n_skip_ref) DMG_ADD(tab + T.stats + NABWA_DAMAGE_STAT_COLUMNS_SKIPPED_REF, n_skip_ref);
+	if (n_cols) REC_ADD32(tab + T.stats + NABWA_DAMAGE_STAT_COLUMNS_COUNTED, n_cols);
+	if (n_skip_read) REC_ADD32(tab + T.stats + NABWA_DAMAGE_STAT_COLUMNS_SKIPPED_READ, n_skip_read);
+	if (n_skip_ref) REC_ADD32(tab + T.stats + NABWA_DAMAGE_STAT_COLUMNS_SKIPPED_REF, n_skip_ref);
 	if (t == 0) {
-		DMG_INC(tab + T.stats + NABWA_DAMAGE_STAT_SEEN); DMG_INC(tab + T.stats + NABWA_DAMAGE_STAT_COUNTED);
-		DMG_INC(tab + T.len + (int)(L < NABWA_DAMAGE_LEN_BINS - 1 ? L : NABWA_DAMAGE_LEN_BINS - 1));
+		REC_INC(tab + T.stats + NABWA_DAMAGE_STAT_SEEN); REC_INC(tab + T.stats + NABWA_DAMAGE_STAT_COUNTED);
+		REC_INC(tab + T.len + (int)(L < NABWA_DAMAGE_LEN_BINS - 1 ? L : NABWA_DAMAGE_LEN_BINS - 1));
 	}
 	return DMG_OK;
 }
 
 /* the workgroup's non-zero words into the call's table, and zero again; a barrier on either side */
 #define DMG_FLUSH() do { \
-	DMG_SYNC; \
-	DMG_THREADS { for (int w = tid; w < T.words; w += DMG_BLOCK) { const uint32_t v = tab[w]; if (v) { DMG_ADD64(call + w, (unsigned long long)v); tab[w] = 0; } } } \
-	DMG_SYNC; \
+	REC_SYNC; \
+	REC_THREADS { for (int w = tid; w < T.words; w += REC_BLOCK) { const uint32_t v = tab[w]; if (v) { REC_ADD64(call + w, (unsigned long long)v); tab[w] = 0; } } } \
+	REC_SYNC; \
 } while (0)
 
-/* workgroup `block` of `n_blocks`: trips block, block + n_blocks, ... of DMG_GROUPS records each.  tab: T.words words of LDS; call: the call's
+/* workgroup `block` of `n_blocks`: trips block, block + n_blocks, ... of REC_GROUPS records each.  tab: T.words words of LDS; call: the call's
  * table, zero before the kernel; *bad: 0xffffffff before it, the lowest damaged record after it.  Everything that decides a flush is the same
  * in every thread of the workgroup. */
-DMG_FN void dmg_block(const DmgParams &P, uint32_t *tab, unsigned long long *call, unsigned int *bad, int block, int n_blocks)
+REC_FN void dmg_block(const DmgParams &P, uint32_t *tab, unsigned long long *call, unsigned int *bad, int block, int n_blocks)
 {
 	const DmgTab T = dmg_tab(P.n_pos);
-	DMG_THREADS { for (int w = tid; w < T.words; w += DMG_BLOCK) tab[w] = 0; }
-	DMG_SYNC;
+	REC_THREADS { for (int w = tid; w < T.words; w += REC_BLOCK) tab[w] = 0; }
+	REC_SYNC;
 	uint64_t held = 0;                                  /* bytes of the records taken since the last flush */
-	for (int64_t first = (int64_t)block * DMG_GROUPS; first < P.n_rec; first += (int64_t)n_blocks * DMG_GROUPS) {
-		const int64_t last = first + DMG_GROUPS < P.n_rec ? first + DMG_GROUPS : P.n_rec;
+	for (int64_t first = (int64_t)block * REC_GROUPS; first < P.n_rec; first += (int64_t)n_blocks * REC_GROUPS) {
+		const int64_t last = first + REC_GROUPS < P.n_rec ? first + REC_GROUPS : P.n_rec;
 		const uint64_t bytes = (uint64_t)(P.off[last] - P.off[first]);
 		if (bytes >= DMG_FLUSH_BYTES) {                 /* records of gigabytes: one at a time, a flush around each */
 			for (int64_t i = first; i < last; ++i) {
 				DMG_FLUSH();
-				DMG_THREADS {
-					if (tid < DMG_LANES) {
+				REC_THREADS {
+					if (tid < REC_LANES) {
 						const int64_t o = P.off[i];
-						if (dmg_record_part(P, T, P.in + (o - P.base), P.off[i + 1] - o, tid, tab) != DMG_OK && tid == 0) DMG_MIN(bad, (unsigned int)i);
+						if (dmg_record_part(P, T, P.in + (o - P.base), P.off[i + 1] - o, tid, tab) != DMG_OK && tid == 0) REC_MIN32(bad, (unsigned int)i);
 					}
 				}
 			}
@@ -207,11 +177,11 @@ DMG_FN void dmg_block(const DmgParams &P, uint32_t *tab, unsigned long long *cal
 		}
 		if (held + bytes >= DMG_FLUSH_BYTES) { DMG_FLUSH(); held = 0; }
 		held += bytes;
-		DMG_THREADS {
-			const int64_t i = first + tid / DMG_LANES;
+		REC_THREADS {
+			const int64_t i = first + tid / REC_LANES;
 			if (i < last) {
 				const int64_t o = P.off[i];
-				if (dmg_record_part(P, T, P.in + (o - P.base), P.off[i + 1] - o, tid % DMG_LANES, tab) != DMG_OK && tid % DMG_LANES == 0) DMG_MIN(bad, (unsigned int)i);
+				if (dmg_record_part(P, T, P.in + (o - P.base), P.off[i + 1] - o, tid % REC_LANES, tab) != DMG_OK && tid % REC_LANES == 0) REC_MIN32(bad, (unsigned int)i);
 			}
 		}
 	}

@@ -89,12 +89,12 @@ void nabwa_launch_md_count(const struct FinRef *R, const struct FinRec *recs, in
 						   int32_t *nm, int32_t *len_out, hipStream_t s);
 void nabwa_launch_md_write(const struct FinRef *R, const struct FinRec *recs, int n, const uint8_t *reads0, const uint8_t *reads1, const uint16_t *cigar,
 						   const int64_t *md_off, char *md, hipStream_t s);
-/* damage_kernels.hip (damage_body.hpp): the records of *P counted into the call's table (zero before), *bad (0xffffffff before) = the lowest
+/* damage_kernels.hip (damage_body.hpp, rec_body.hpp): the records of *P counted into the call's table (zero before), *bad (0xffffffff before) = the lowest
  * damaged record; n_blocks workgroups share the records whatever their number.  Then the call's table onto the totals */
 struct DmgParams;
 void nabwa_launch_damage(const struct DmgParams *P, int n_blocks, unsigned long long *call, unsigned int *bad, hipStream_t s);
 void nabwa_launch_damage_add(int words, const unsigned long long *call, unsigned long long *total, hipStream_t s);
-/* markdup_kernels.hip (markdup_body.hpp): the records of *P into the call's scratch, *bad (0xffffffff before) = the lowest damaged record;
+/* markdup_kernels.hip (markdup_body.hpp, rec_body.hpp): the records of *P into the call's scratch, *bad (0xffffffff before) = the lowest damaged record;
  * then, for a sound call, their tuples onto the arena.  The resolve: the index column, the key column of the next radix pass, the marks of
  * the n sorted tuples, the marks of the n records' unmapped mates */
 struct MdParams; struct MdArena;
@@ -104,7 +104,7 @@ void nabwa_launch_markdup_iota(int64_t n, uint32_t *idx, hipStream_t s);
 void nabwa_launch_markdup_gather(int64_t n, const uint32_t *idx, const uint64_t *src, uint64_t *keys, hipStream_t s);
 void nabwa_launch_markdup_mark(int64_t n, const uint32_t *idx, const uint64_t *hi, const uint64_t *lo, const uint64_t *k3, uint8_t *dup, unsigned long long *stats, hipStream_t s);
 void nabwa_launch_markdup_prop(int64_t n, const uint8_t *link, uint8_t *dup, unsigned long long *stats, hipStream_t s);
-/* bai_kernels.hip (bai_body.hpp): the records of *P as tuples into the arena, P->cnt[0] (0xffffffff before) = the lowest damaged record,
+/* bai_kernels.hip (bai_body.hpp, rec_body.hpp): the records of *P as tuples into the arena, P->cnt[0] (0xffffffff before) = the lowest damaged record,
  * P->cnt[1] (0 before) = the records without a reference.  The finish: the ordinal column, then the steps of *F in the order of the enum,
  * a sort and three scans between them (nabwa_bai.hip) */
 struct BaiParams; struct BaiFin;

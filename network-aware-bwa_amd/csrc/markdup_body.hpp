@@ -1,9 +1,9 @@
 // markdup_body.hpp -- the bodies of duplicate marking of finished BAM records (markdup_kernels.hip, nabwa_markdup*; the
 // semantics: include/nabwa.h):
 //
-//   md_record_part   lane t of the MD_LANES lanes that take one record: its fields, its class, the CIGAR walked for its two unclipped ends,
+//   md_record_part   lane t of the REC_LANES lanes that take one record: its fields, its class, the CIGAR walked for its two unclipped ends,
 //                    its piece of the base qualities and of the read-name comparison with the record behind it
-//   md_block         one workgroup of the persistent grid: MD_GROUPS records per trip; what a record came to goes into the call's scratch
+//   md_block         one workgroup of the persistent grid: REC_GROUPS records per trip; what a record came to goes into the call's scratch
 //   md_emit_record   one record of a call whose records were all sound: mates found from the neighbours' scratch, the record's tuples appended
 //                    to the handle's arena, its class counted
 //   md_mark_one      position j of the sorted tuples: not the head of its group and not a shadow -> dup[ordinal] (a pair's: both mates)
@@ -28,30 +28,11 @@
 #pragma once
 #include <stdint.h>
 #include "../../include/nabwa.h"
+#include "rec_body.hpp"        /* the macro layer, REC_LANES ... REC_MIN_REC, rec_u32, rec_op_read / rec_op_ref, REC_HEAD */
 #ifdef NABWA_EMU
-#define MD_FN static inline
-#define MD_HD static inline
-#define MD_THREADS for (int tid = 0; tid < MD_BLOCK; ++tid)
-#define MD_SYNC ((void)0)
-#define MD_ADD64(p, v) (*(p) += (v))
-#define MD_OR(p, v) (*(p) |= (v))
-#define MD_MIN(p, v) (*(p) = *(p) < (v) ? *(p) : (v))
-static inline unsigned int md_fetch_add(unsigned int *p, unsigned int v) { const unsigned int o = *p; *p = o + v; return o; }
-#else
-#define MD_FN __device__ __forceinline__
-#define MD_HD __host__ __device__ __forceinline__
-#define MD_THREADS for (int tid = (int)threadIdx.x, once_ = 1; once_; once_ = 0)
-#define MD_SYNC __syncthreads()
-#define MD_ADD64(p, v) ((void)atomicAdd((p), (v)))
-#define MD_OR(p, v) ((void)atomicOr((p), (v)))
-#define MD_MIN(p, v) ((void)atomicMin((p), (v)))
-#define md_fetch_add(p, v) atomicAdd((p), (v))
+#define MD_GROUPS REC_GROUPS       /* (tests/emu/markdup_emu.cpp sizes its arrays by this name) */
 #endif
 
-#define MD_LANES     16                         /* lanes per record, as the sort's gather and the damage kernel */
-#define MD_BLOCK     256
-#define MD_GROUPS    (MD_BLOCK / MD_LANES)      /* records per workgroup and trip */
-#define MD_MIN_REC   36                         /* block_size + the 32 fixed bytes of a record */
 #define MD_SCORE_CAP 0xfffffffeu                /* the highest score of a record or pair; 0xffffffff is a shadow's */
 #define MD_COORD_LO  (-((int64_t)1 << 30))      /* a coordinate lies in [MD_COORD_LO, MD_COORD_HI): 32 bits once MD_COORD_LO is taken off */
 #define MD_COORD_HI  (((int64_t)1 << 31) + ((int64_t)1 << 30))
@@ -90,43 +71,35 @@ struct MdParams {
  * records get the ordinals ord_base, ord_base + 1, ... */
 struct MdArena { uint64_t *hi, *lo, *k3; uint8_t *link; unsigned int *n_tup; unsigned long long *stats; uint32_t ord_base; };
 
-MD_FN uint32_t md_u32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 /* the `need` (1..8) bytes at p, little-endian, of which `avail` >= need exist; the bytes above them read as 0.  One 8-byte load where 8 exist */
-MD_FN uint64_t md_load(const uint8_t *p, int64_t avail, int need)
+REC_FN uint64_t md_load(const uint8_t *p, int64_t avail, int need)
 {
 	uint64_t w = 0;
 	if (avail >= 8) { __builtin_memcpy(&w, p, 8); return need < 8 ? w & ((((uint64_t)1) << (8 * need)) - 1) : w; }
 	for (int b = 0; b < need; ++b) w |= (uint64_t)p[b] << (8 * b);
 	return w;
 }
-MD_HD bool md_op_read(uint32_t op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }     /* M I S = X */
-MD_HD bool md_op_ref(uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }      /* M D N = X */
 
-/* lane t of the group of record i, `rec` of `size` >= MD_MIN_REC bytes; nsize: the size of record i + 1, which lies at rec + size, or 0 where
+/* lane t of the group of record i, `rec` of `size` >= REC_MIN_REC bytes; nsize: the size of record i + 1, which lies at rec + size, or 0 where
  * there is none.  sum, diff, meta: the group's words of LDS (sum and diff zero).  MD_BAD for a damaged record (every lane says so, before any
  * lane has touched sum or diff), else MD_OK */
-MD_FN int md_record_part(const MdParams &P, int64_t i, const uint8_t *rec, int64_t size, int64_t nsize, int t, unsigned long long *sum, uint32_t *diff, uint32_t *meta)
+REC_FN int md_record_part(const MdParams &P, int64_t i, const uint8_t *rec, int64_t size, int64_t nsize, int t, unsigned long long *sum, uint32_t *diff, uint32_t *meta)
 {
-	if ((int64_t)md_u32(rec) + 4 != size) return MD_BAD;
-	const int32_t ref_id = (int32_t)md_u32(rec + 4), pos = (int32_t)md_u32(rec + 8);
-	const uint32_t w12 = md_u32(rec + 12), w16 = md_u32(rec + 16);
-	const uint32_t l_name = w12 & 0xffu, n_cig = w16 & 0xffffu, flag = w16 >> 16;
-	const uint64_t L = md_u32(rec + 20);
-	if ((uint64_t)MD_MIN_REC + l_name + 4 * (uint64_t)n_cig + (L + 1) / 2 + L > (uint64_t)size) return MD_BAD;
+	REC_HEAD(rec, size, MD_BAD);
 	uint32_t m = MD_CLS_MAPPED;
 	if (flag & P.exclude_flags) m = MD_CLS_SKIPPED;
 	else if (flag & 0x400u) m = MD_CLS_ALREADY;
 	else if ((flag & 0x4u) || ref_id < 0 || pos < 0 || n_cig == 0) m = MD_CLS_UNMAPPED;
-	const uint8_t *cig = rec + MD_MIN_REC + l_name, *end = rec + size;
+	const uint8_t *cig = rec + REC_MIN_REC + l_name, *end = rec + size;
 	uint64_t e5 = 0; uint32_t c3w = 0;
 	if (m == MD_CLS_MAPPED) {
 		/* what the CIGAR consumes, and the clips outside its reference span (operations of 28 bits, at most 65535 of them: no sum leaves 64 bits) */
 		uint64_t n_read = 0, n_ref = 0, lead = 0, trail = 0;
 		bool seen = false;
 		for (uint32_t c = 0; c < n_cig; ++c) {
-			const uint32_t w = md_u32(cig + 4 * c), op = w & 15u, len = w >> 4;
-			if (md_op_read(op)) n_read += len;
-			if (md_op_ref(op)) { n_ref += len; seen = true; trail = 0; }
+			const uint32_t w = rec_u32(cig + 4 * c), op = w & 15u, len = w >> 4;
+			if (rec_op_read(op)) n_read += len;
+			if (rec_op_ref(op)) { n_ref += len; seen = true; trail = 0; }
 			else if (op == 4 || op == 5) { if (seen) trail += len; else lead += len; }
 		}
 		if (L > 0 && n_read != L) return MD_BAD;
@@ -138,12 +111,12 @@ MD_FN int md_record_part(const MdParams &P, int64_t i, const uint8_t *rec, int64
 		/* the qualities that count, this lane's pieces */
 		const uint8_t *q = cig + 4 * (uint64_t)n_cig + (L + 1) / 2;
 		uint64_t s = 0;
-		for (int64_t at = 8 * (int64_t)t; at < (int64_t)L; at += 8 * MD_LANES) {
+		for (int64_t at = 8 * (int64_t)t; at < (int64_t)L; at += 8 * REC_LANES) {
 			const int nb = (int64_t)L - at < 8 ? (int)((int64_t)L - at) : 8;
 			const uint64_t w = md_load(q + at, end - (q + at), nb);
 			for (int b = 0; b < nb; ++b) { const uint32_t v = (uint32_t)(w >> (8 * b)) & 0xffu; if (v != 0xffu && (int32_t)v >= P.min_qual) s += v; }
 		}
-		if (s) MD_ADD64(sum, (unsigned long long)s);
+		if (s) REC_ADD64(sum, (unsigned long long)s);
 	}
 	if ((flag & 0xC1u) == 0x41u) m |= MD_M_FIRST;
 	if ((flag & 0xC1u) == 0x81u) m |= MD_M_SECOND;
@@ -151,39 +124,39 @@ MD_FN int md_record_part(const MdParams &P, int64_t i, const uint8_t *rec, int64
 	if ((m & MD_M_FIRST) && (m & MD_CLS_MASK) >= MD_CLS_UNMAPPED && nsize) {      /* a first mate that can have one: is the next record's name this one's? */
 		m |= MD_M_COMPARED;
 		const uint8_t *nxt = rec + size;
-		if ((nxt[12] != l_name || (int64_t)MD_MIN_REC + l_name > nsize)) { if (t == 0) MD_OR(diff, 1u); }
+		if ((nxt[12] != l_name || (int64_t)REC_MIN_REC + l_name > nsize)) { if (t == 0) REC_OR(diff, 1u); }
 		else
-			for (int at = 8 * t; at < (int)l_name; at += 8 * MD_LANES) {
+			for (int at = 8 * t; at < (int)l_name; at += 8 * REC_LANES) {
 				const int nb = (int)l_name - at < 8 ? (int)l_name - at : 8;
-				const uint8_t *a = rec + MD_MIN_REC + at, *b = nxt + MD_MIN_REC + at;
-				if (md_load(a, end - a, nb) != md_load(b, nxt + nsize - b, nb)) MD_OR(diff, 1u);
+				const uint8_t *a = rec + REC_MIN_REC + at, *b = nxt + REC_MIN_REC + at;
+				if (md_load(a, end - a, nb) != md_load(b, nxt + nsize - b, nb)) REC_OR(diff, 1u);
 			}
 	}
 	if (t == 0) { P.end[i] = e5; P.c3[i] = c3w; *meta = m; }
 	return MD_OK;
 }
 
-/* workgroup `block` of `n_blocks`: trips block, block + n_blocks, ... of MD_GROUPS records each.  sum, diff, meta: MD_GROUPS words of LDS
+/* workgroup `block` of `n_blocks`: trips block, block + n_blocks, ... of REC_GROUPS records each.  sum, diff, meta: REC_GROUPS words of LDS
  * each; *bad: 0xffffffff before the kernel, the lowest damaged record after it */
-MD_FN void md_block(const MdParams &P, unsigned long long *sum, uint32_t *diff, uint32_t *meta, unsigned int *bad, int block, int n_blocks)
+REC_FN void md_block(const MdParams &P, unsigned long long *sum, uint32_t *diff, uint32_t *meta, unsigned int *bad, int block, int n_blocks)
 {
-	MD_THREADS { if (tid < MD_GROUPS) { sum[tid] = 0; diff[tid] = 0; meta[tid] = 0; } }
-	MD_SYNC;
-	for (int64_t first = (int64_t)block * MD_GROUPS; first < P.n_rec; first += (int64_t)n_blocks * MD_GROUPS) {
-		MD_THREADS {
-			const int g = tid / MD_LANES, t = tid % MD_LANES;
+	REC_THREADS { if (tid < REC_GROUPS) { sum[tid] = 0; diff[tid] = 0; meta[tid] = 0; } }
+	REC_SYNC;
+	for (int64_t first = (int64_t)block * REC_GROUPS; first < P.n_rec; first += (int64_t)n_blocks * REC_GROUPS) {
+		REC_THREADS {
+			const int g = tid / REC_LANES, t = tid % REC_LANES;
 			const int64_t i = first + g;
 			if (i < P.n_rec) {
 				const int64_t o = P.off[i], o1 = P.off[i + 1];
 				const int64_t nsize = i + 1 < P.n_rec ? P.off[i + 2] - o1 : 0;
-				if (md_record_part(P, i, P.in + (o - P.base), o1 - o, nsize, t, sum + g, diff + g, meta + g) != MD_OK && t == 0) { MD_MIN(bad, (unsigned int)i); meta[g] = MD_CLS_SKIPPED; }
+				if (md_record_part(P, i, P.in + (o - P.base), o1 - o, nsize, t, sum + g, diff + g, meta + g) != MD_OK && t == 0) { REC_MIN32(bad, (unsigned int)i); meta[g] = MD_CLS_SKIPPED; }
 			}
 		}
-		MD_SYNC;
-		MD_THREADS {                                    /* the group's sums are whole: the record's score and the name's verdict, and the words zero again */
-			const int g = tid / MD_LANES;
+		REC_SYNC;
+		REC_THREADS {                                    /* the group's sums are whole: the record's score and the name's verdict, and the words zero again */
+			const int g = tid / REC_LANES;
 			const int64_t i = first + g;
-			if (tid % MD_LANES == 0 && i < P.n_rec) {
+			if (tid % REC_LANES == 0 && i < P.n_rec) {
 				const unsigned long long s = sum[g];
 				uint32_t m = meta[g];
 				if ((m & MD_M_COMPARED) && diff[g] == 0) m |= MD_M_SAME_NEXT;
@@ -192,13 +165,13 @@ MD_FN void md_block(const MdParams &P, unsigned long long *sum, uint32_t *diff, 
 				sum[g] = 0; diff[g] = 0;
 			}
 		}
-		MD_SYNC;
+		REC_SYNC;
 	}
 }
 
 /* record i of a sound call.  Records i and i + 1 are mates when i is a first and i + 1 a second mate of the same name and neither is
  * skipped or already marked; a record is in at most one such couple, since none is both first and second */
-MD_FN void md_emit_record(const MdParams &P, const MdArena &A, int64_t i)
+REC_FN void md_emit_record(const MdParams &P, const MdArena &A, int64_t i)
 {
 	const uint32_t m = P.meta[i], cls = m & MD_CLS_MASK;
 	const uint32_t ord = A.ord_base + (uint32_t)i;
@@ -208,36 +181,36 @@ MD_FN void md_emit_record(const MdParams &P, const MdArena &A, int64_t i)
 		if ((m & MD_M_FIRST) && (m & MD_M_SAME_NEXT) && i + 1 < P.n_rec) { const uint32_t x = P.meta[i + 1]; if ((x & MD_M_SECOND) && (x & MD_CLS_MASK) >= MD_CLS_UNMAPPED) mate = i + 1; }
 		if ((m & MD_M_SECOND) && i > 0) { const uint32_t x = P.meta[i - 1]; if ((x & MD_M_FIRST) && (x & MD_M_SAME_NEXT) && (x & MD_CLS_MASK) >= MD_CLS_UNMAPPED) mate = i - 1; }
 	}
-	MD_ADD64(A.stats + NABWA_MARKDUP_STAT_SEEN, 1ull);
+	REC_ADD64(A.stats + NABWA_MARKDUP_STAT_SEEN, 1ull);
 	const bool mate_mapped = mate >= 0 && (P.meta[mate] & MD_CLS_MASK) == MD_CLS_MAPPED;
-	if (cls == MD_CLS_SKIPPED) MD_ADD64(A.stats + NABWA_MARKDUP_STAT_SKIPPED_FLAGS, 1ull);
-	else if (cls == MD_CLS_ALREADY) MD_ADD64(A.stats + NABWA_MARKDUP_STAT_ALREADY, 1ull);
+	if (cls == MD_CLS_SKIPPED) REC_ADD64(A.stats + NABWA_MARKDUP_STAT_SKIPPED_FLAGS, 1ull);
+	else if (cls == MD_CLS_ALREADY) REC_ADD64(A.stats + NABWA_MARKDUP_STAT_ALREADY, 1ull);
 	else if (cls == MD_CLS_UNMAPPED) {
-		MD_ADD64(A.stats + NABWA_MARKDUP_STAT_UNMAPPED, 1ull);
+		REC_ADD64(A.stats + NABWA_MARKDUP_STAT_UNMAPPED, 1ull);
 		if (mate_mapped) link = mate > i ? MD_LINK_NEXT : MD_LINK_PREV;       /* a half pair's unmapped mate */
 	} else if (mate_mapped) {                                                  /* a pair: its tuple with the first mate, a shadow at either end */
 		const bool first = mate > i, shadow = P.single_ends == NABWA_MARKDUP_ENDS_5P;
-		const unsigned int at = md_fetch_add(A.n_tup, (first ? 1u : 0u) + (shadow ? 1u : 0u));
+		const unsigned int at = rec_fetch_add(A.n_tup, (first ? 1u : 0u) + (shadow ? 1u : 0u));
 		unsigned int w = at;
 		if (first) {
 			const uint64_t a = P.end[i], b = P.end[mate];
 			const uint64_t s = (uint64_t)P.score[i] + P.score[mate];
 			A.hi[w] = a < b ? a : b; A.lo[w] = a < b ? b : a; A.k3[w] = MD_K3(true, s > MD_SCORE_CAP ? MD_SCORE_CAP : (uint32_t)s, ord);
 			++w;
-			MD_ADD64(A.stats + NABWA_MARKDUP_STAT_PAIRS, 1ull);
+			REC_ADD64(A.stats + NABWA_MARKDUP_STAT_PAIRS, 1ull);
 		}
 		if (shadow) { A.hi[w] = P.end[i]; A.lo[w] = 0; A.k3[w] = MD_K3(false, 0xffffffffu, ord); }
 	} else {                                                                   /* a fragment: a single read, a half pair's mapped mate, an orphan */
-		const unsigned int w = md_fetch_add(A.n_tup, 1u);
+		const unsigned int w = rec_fetch_add(A.n_tup, 1u);
 		A.hi[w] = P.end[i]; A.lo[w] = P.single_ends == NABWA_MARKDUP_ENDS_BOTH ? (uint64_t)P.c3[i] : 0; A.k3[w] = MD_K3(false, P.score[i], ord);
-		MD_ADD64(A.stats + NABWA_MARKDUP_STAT_FRAGMENTS, 1ull);
-		if ((m & MD_M_PAIRED) && mate < 0) MD_ADD64(A.stats + NABWA_MARKDUP_STAT_ORPHANS, 1ull);
+		REC_ADD64(A.stats + NABWA_MARKDUP_STAT_FRAGMENTS, 1ull);
+		if ((m & MD_M_PAIRED) && mate < 0) REC_ADD64(A.stats + NABWA_MARKDUP_STAT_ORPHANS, 1ull);
 	}
 	A.link[ord] = link;
 }
 
 /* position j of the n tuples in (hi, lo, k3) order, idx[j] being the tuple there.  The first of a group wins; every other real member is marked */
-MD_FN void md_mark_one(int64_t j, const uint32_t *idx, const uint64_t *hi, const uint64_t *lo, const uint64_t *k3, uint8_t *dup, unsigned long long *stats)
+REC_FN void md_mark_one(int64_t j, const uint32_t *idx, const uint64_t *hi, const uint64_t *lo, const uint64_t *k3, uint8_t *dup, unsigned long long *stats)
 {
 	if (j == 0) return;
 	const uint32_t t = idx[j], u = idx[j - 1];
@@ -248,17 +221,17 @@ MD_FN void md_mark_one(int64_t j, const uint32_t *idx, const uint64_t *hi, const
 	const uint32_t ord = MD_K3_ORD(k);
 	dup[ord] = 1;
 	if (pair) dup[ord + 1] = 1;
-	MD_ADD64(stats + (pair ? NABWA_MARKDUP_STAT_DUP_PAIRS : NABWA_MARKDUP_STAT_DUP_FRAGMENTS), 1ull);
+	REC_ADD64(stats + (pair ? NABWA_MARKDUP_STAT_DUP_PAIRS : NABWA_MARKDUP_STAT_DUP_FRAGMENTS), 1ull);
 }
 
 /* ordinal o of the n records added: a half pair's unmapped mate (which no tuple names, so nobody else writes dup[o]) takes the mark of its
  * mate (a fragment, which this pass does not write) */
-MD_FN void md_prop_one(int64_t o, const uint8_t *link, uint8_t *dup, unsigned long long *stats)
+REC_FN void md_prop_one(int64_t o, const uint8_t *link, uint8_t *dup, unsigned long long *stats)
 {
 	const uint8_t l = link[o];
 	uint8_t d = dup[o];
 	if (l == MD_LINK_NEXT) d = dup[o + 1];
 	else if (l == MD_LINK_PREV) d = dup[o - 1];
 	if (l != MD_LINK_NONE) dup[o] = d;
-	if (d) MD_ADD64(stats + NABWA_MARKDUP_STAT_DUP_RECORDS, 1ull);
+	if (d) REC_ADD64(stats + NABWA_MARKDUP_STAT_DUP_RECORDS, 1ull);
 }

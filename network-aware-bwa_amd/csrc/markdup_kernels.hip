@@ -1,6 +1,6 @@
 // markdup_kernels.hip -- the kernels of duplicate marking (bodies: markdup_body.hpp; host side: nabwa_markdup.hip).
 //
-//   markdup_sig_kernel     a persistent grid of workgroups of MD_BLOCK threads, MD_LANES lanes per record: every record's class, ends and score
+//   markdup_sig_kernel     a persistent grid of workgroups of REC_BLOCK threads, REC_LANES lanes per record: every record's class, ends and score
 //                          into the call's scratch, the lowest damaged record into *bad
 //   markdup_emit_kernel    one lane per record of a sound call: mates from the neighbours' scratch, tuples appended to the handle's arena
 //   markdup_iota_kernel, markdup_gather_kernel    the index column and the key column of the next radix pass of the resolve
@@ -10,10 +10,10 @@
 #include "launchers.hpp"
 #include "markdup_body.hpp"
 
-__global__ __launch_bounds__(MD_BLOCK) void markdup_sig_kernel(const MdParams P, unsigned int *__restrict__ bad)
+__global__ __launch_bounds__(REC_BLOCK) void markdup_sig_kernel(const MdParams P, unsigned int *__restrict__ bad)
 {
-	__shared__ unsigned long long sum[MD_GROUPS];
-	__shared__ uint32_t diff[MD_GROUPS], meta[MD_GROUPS];
+	__shared__ unsigned long long sum[REC_GROUPS];
+	__shared__ uint32_t diff[REC_GROUPS], meta[REC_GROUPS];
 	md_block(P, sum, diff, meta, bad, (int)blockIdx.x, (int)gridDim.x);
 }
 
@@ -53,7 +53,7 @@ static inline dim3 grid_of(int64_t n) { return dim3((unsigned int)((n + 255) / 2
 extern "C" {
 void nabwa_launch_markdup_sig(const MdParams *P, int n_blocks, unsigned int *bad, hipStream_t s)
 {
-	hipLaunchKernelGGL(markdup_sig_kernel, dim3(n_blocks), dim3(MD_BLOCK), 0, s, *P, bad);
+	hipLaunchKernelGGL(markdup_sig_kernel, dim3(n_blocks), dim3(REC_BLOCK), 0, s, *P, bad);
 }
 void nabwa_launch_markdup_emit(const MdParams *P, const MdArena *A, hipStream_t s)
 {

@@ -12,19 +12,19 @@
 // arguments alone, before any device call.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
-#include <stdio.h>
 #include <string.h>
-#include <initializer_list>
-#include <utility>
-#include "../../include/nabwa.h"
 #include "launchers.hpp"
-#include "nabwa_internal.hpp"
-#include "dev_pool.hpp"
+#include "rec_stream.hpp"
 #include "bai_body.hpp"
 
+#define BAI_FIT "the records do not fit the device: a buffer of %lld bytes could not be had"
+/* the handle's pinned words: bad and n_no_coor of a call, then three 64-bit totals of a finish (at a multiple of 8 bytes) */
+enum { BAI_H_CNT = 2, BAI_H_TOT = 3, BAI_H_WORDS = BAI_H_CNT + 2 * BAI_H_TOT };
+static_assert(BAI_H_CNT % 2 == 0, "h_tot lies at a multiple of 8 bytes");
+
 struct nabwa_bai {
-	int device = 0, n_blocks = 1; int32_t n_ref = 0;
-	DevStream st;
+	RecStream rs;                                               /* h_words: bad, n_no_coor of a call; then h_tot */
+	int32_t n_ref = 0;
 	DevBuf d_in, d_off, d_cnt;                                  /* a call: its bytes, its offsets; bad and n_no_coor */
 	DevBuf a_key, a_be, a_us, a_ue;                             /* the arena: a tuple per ordinal */
 	DevBuf f_blk_u, f_blk_c, f_vb, f_ve, f_keys[2], f_idx[2], f_heads, f_sc, f_bin_c0, f_tmp, f_lin, f_out;      /* a finish */
@@ -32,43 +32,21 @@ struct nabwa_bai {
 	int64_t cap_bytes = 0, cap_rec = 0, cap_ord = 0, cap_blk = 0, cap_fin = 0, cap_lin = 0, cap_out = 0; size_t cap_tmp = 0;
 	int64_t n_ord = 0, n_no_coor = 0;                           /* records added; those of them without a reference */
 	int64_t first_start = 0, last_end = 0; uint64_t last_key = 0;      /* of the records added: where they start and end in the stream; the last one's key */
-	unsigned int *h_cnt = nullptr;                              /* pinned: bad, n_no_coor of a call */
-	unsigned long long *h_tot = nullptr;                        /* pinned: the last scanned heads word, the file's bytes, the windows */
-	hipEvent_t ev[9] = {};
+	unsigned long long *h_tot = nullptr;                        /* pinned, behind the BAI_H_CNT words of rs.h_words: the last scanned heads word, the file's bytes, the windows */
 	float ms[7] = { 0, 0, 0, 0, 0, 0, 0 };
-	~nabwa_bai()
-	{
-		(void)hipSetDevice(device);
-		if (st.s) (void)hipStreamSynchronize(st.s);
-		if (h_cnt) (void)hipHostFree(h_cnt);
-		if (h_tot) (void)hipHostFree(h_tot);
-		for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-	}
+	~nabwa_bai() { rs.quiesce(); }
 };
-
-static int fail_fmt(int code, const char *fmt, long long a, long long b = 0, long long c = 0)
-{
-	char m[256]; snprintf(m, sizeof m, fmt, a, b, c);
-	return nabwa_fail(code, "%s", m);
-}
 
 extern "C" int nabwa_bai_create(int device, int32_t n_ref, nabwa_bai_t **out)
 {
 	if (out) *out = nullptr;
 	if (!out) return nabwa_fail(NABWA_EINVAL, "null argument");
 	if (n_ref < 0) return fail_fmt(NABWA_EINVAL, "n_ref %lld: the number of reference sequences", n_ref);
-	const hipError_t e0 = hipSetDevice(device);
-	if (e0 != hipSuccess) { (void)hipGetLastError(); return nabwa_hip_fail(e0, "hipSetDevice(device)", __FILE__, __LINE__); }
 	nabwa_bai_t *b = new nabwa_bai_t;
-	b->device = device; b->n_ref = n_ref;
-	int n_cu = 0;
-	hipError_t e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device);
-	b->n_blocks = 8 * (n_cu > 0 ? n_cu : 1);                  /* the persistent grid: eight workgroups of 256 fill a compute unit's wave slots */
-	if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->st.s, hipStreamNonBlocking);
-	if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_cnt, 2 * sizeof(unsigned int), hipHostMallocDefault);
-	if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_tot, 3 * sizeof(unsigned long long), hipHostMallocDefault);
-	for (int k = 0; k < 9 && e == hipSuccess; ++k) e = hipEventCreate(&b->ev[k]);
-	int r = e == hipSuccess ? NABWA_OK : nabwa_hip_fail(e, "setting up the BAM index", __FILE__, __LINE__);
+	b->n_ref = n_ref;
+	/* the persistent grid: eight workgroups of 256 fill a compute unit's wave slots */
+	int r = b->rs.setup(device, 8, BAI_H_WORDS, 9, "setting up the BAM index");
+	if (r == NABWA_OK) b->h_tot = (unsigned long long*)(b->rs.h_words + BAI_H_CNT);
 	if (r == NABWA_OK) r = b->d_cnt.get(2 * sizeof(unsigned int));
 	for (int k = 0; k < 8 && r == NABWA_OK; ++k) r = b->r_i32[k].get(((size_t)n_ref + 1) * 4);
 	for (int k = 0; k < 4 && r == NABWA_OK; ++k) r = b->r_u64[k].get(((size_t)n_ref + 1) * 8);
@@ -79,42 +57,12 @@ extern "C" int nabwa_bai_create(int device, int32_t n_ref, nabwa_bai_t **out)
 
 extern "C" void nabwa_bai_destroy(nabwa_bai_t *b) { delete b; }
 
-/* b, which holds `keep` bytes worth keeping, becomes a buffer of at least `bytes`; out of device memory is the caller's to act on */
-static int bai_grow(DevBuf &b, size_t keep, size_t bytes, hipStream_t st)
-{
-	if (!keep) { const hipError_t e = b.release(); if (e != hipSuccess) return nabwa_hip_fail(e, "hipFree", __FILE__, __LINE__); }
-	void *p = nullptr;
-	const hipError_t m = hipMalloc(&p, bytes ? bytes : 1);
-	if (m == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail_fmt(NABWA_ENOMEM, "the records do not fit the device: a buffer of %lld bytes could not be had", (long long)bytes); }
-	if (m != hipSuccess) return nabwa_hip_fail(m, "hipMalloc", __FILE__, __LINE__);
-	hipError_t e = hipSuccess;
-	if (keep && b.p) { e = hipMemcpyAsync(p, b.p, keep, hipMemcpyDeviceToDevice, st); if (e == hipSuccess) e = hipStreamSynchronize(st); }
-	if (e == hipSuccess) e = b.release();
-	if (e != hipSuccess) { (void)hipFree(p); return nabwa_hip_fail(e, "moving the arena", __FILE__, __LINE__); }
-	b.p = p;
-	return NABWA_OK;
-}
-/* `cap` units of `unit` bytes each in every buffer of `bufs` (what they hold of `have` units is kept) become at least `want`, a quarter more */
-static int bai_reserve(int64_t &cap, int64_t want, int64_t have, hipStream_t st, std::initializer_list<std::pair<DevBuf*, int>> bufs, int extra = 0)
-{
-	if (want <= cap) return NABWA_OK;
-	HIP_CHECK(hipStreamSynchronize(st));
-	const int64_t to = want + want / 4;
-	cap = have;                                                /* (a failure half-way: what is kept still fits every buffer) */
-	for (const auto &b : bufs) if (int r = bai_grow(*b.first, (size_t)have * (size_t)b.second, (size_t)(to + extra) * (size_t)b.second, st)) return r;
-	cap = to;
-	return NABWA_OK;
-}
-
 /* which kind of damage record i has, from its bytes on the host, for the message.  before: the key of the record in front of it */
 static int damaged(int64_t i, const uint8_t *rec, int64_t size, int32_t n_ref, uint64_t before)
 {
-	uint32_t bs, w12, w16, L; int32_t tid, pos;
-	memcpy(&bs, rec, 4); memcpy(&tid, rec + 4, 4); memcpy(&pos, rec + 8, 4); memcpy(&w12, rec + 12, 4); memcpy(&w16, rec + 16, 4); memcpy(&L, rec + 20, 4);
-	if ((int64_t)bs + 4 != size) return fail_fmt(NABWA_EDATA, "record %lld: its block_size says %lld bytes, its offsets %lld", (long long)i, (long long)bs + 4, (long long)size);
-	const uint32_t l_name = w12 & 0xffu, n_cig = w16 & 0xffffu;
-	const uint64_t need = (uint64_t)BAI_MIN_REC + l_name + 4 * (uint64_t)n_cig + ((uint64_t)L + 1) / 2 + L;
-	if (need > (uint64_t)size) return fail_fmt(NABWA_EDATA, "record %lld: its name, CIGAR, bases and qualities need %lld bytes, it has %lld", (long long)i, (long long)need, (long long)size);
+	if (int r = rec_damaged_head(i, rec, size)) return r;
+	REC_FIELDS(rec);
+	const int32_t tid = ref_id;
 	if (tid >= n_ref) return fail_fmt(NABWA_EDATA, "record %lld: reference %lld of %lld", (long long)i, (long long)tid, (long long)n_ref);
 	if (tid >= 0 && pos < 0) return fail_fmt(NABWA_EDATA, "record %lld: position %lld on reference %lld", (long long)i, (long long)pos, (long long)tid);
 	if (NABWA_BAM_SORT_KEY(tid, pos) < before) return fail_fmt(NABWA_EDATA, "record %lld: out of coordinate order (reference %lld, position %lld behind a higher one)", (long long)i, (long long)tid, (long long)pos);
@@ -122,61 +70,49 @@ static int damaged(int64_t i, const uint8_t *rec, int64_t size, int32_t n_ref, u
 }
 static uint64_t key_of(const uint8_t *rec)
 {
-	int32_t tid, pos;
-	memcpy(&tid, rec + 4, 4); memcpy(&pos, rec + 8, 4);
-	return NABWA_BAM_SORT_KEY(tid, pos);
+	return NABWA_BAM_SORT_KEY((int32_t)rec_u32(rec + 4), (int32_t)rec_u32(rec + 8));
 }
 
 extern "C" int nabwa_bai_add(nabwa_bai_t *b, int64_t n_rec, const uint8_t *in, const int64_t *in_off, int64_t stream_off)
 {
 	if (!b) return nabwa_fail(NABWA_EINVAL, "null argument");
-	if (n_rec < 0 || n_rec > 0x7fffffff) return fail_fmt(NABWA_EINVAL, "n_rec %lld: 0 .. 2147483647 records", (long long)n_rec);
-	if (!in_off || (n_rec && !in)) return nabwa_fail(NABWA_EINVAL, "null argument");
-	if (in_off[0] < 0) return nabwa_fail(NABWA_EINVAL, "the first offset is negative");
-	for (int64_t i = 0; i < n_rec; ++i) {
-		if (in_off[i + 1] <= in_off[i]) return fail_fmt(NABWA_EINVAL, "the offsets do not increase at record %lld", (long long)i);
-		if (in_off[i + 1] - in_off[i] < BAI_MIN_REC) return fail_fmt(NABWA_EINVAL, "record %lld has %lld bytes: a BAM record has at least 36", (long long)i, (long long)(in_off[i + 1] - in_off[i]));
-	}
+	if (int r = rec_check_offsets(n_rec, in, in_off)) return r;
 	if (stream_off < 0) return fail_fmt(NABWA_EINVAL, "stream_off %lld is negative", (long long)stream_off);
 	if (b->n_ord && stream_off < b->last_end) return fail_fmt(NABWA_EINVAL, "stream_off %lld lies before the end of the records added so far, %lld", (long long)stream_off, (long long)b->last_end);
 	if (n_rec == 0) return NABWA_OK;
 	if (b->n_ord + n_rec > 0x7fffffff) return fail_fmt(NABWA_EINVAL, "%lld records after %lld: a handle takes 2147483647 between create / clear", (long long)n_rec, (long long)b->n_ord);
 	const int64_t base = in_off[0], total = in_off[n_rec] - base;
 	if (stream_off > INT64_MAX / 2 - total) return fail_fmt(NABWA_EINVAL, "stream_off %lld: no stream is that long", (long long)stream_off);
-	HIP_CHECK(hipSetDevice(b->device));
+	HIP_CHECK(hipSetDevice(b->rs.device));
 	(void)hipGetLastError();                                   /* (an error some earlier call of the process left behind is not a launch of this call's) */
-	hipStream_t st = b->st;
-	if (int r = bai_reserve(b->cap_bytes, total, 0, st, { { &b->d_in, 1 } })) return r;
-	if (int r = bai_reserve(b->cap_rec, n_rec, 0, st, { { &b->d_off, 8 } }, 1)) return r;
-	if (int r = bai_reserve(b->cap_ord, b->n_ord + n_rec, b->n_ord, st, { { &b->a_key, 8 }, { &b->a_be, 8 }, { &b->a_us, 8 }, { &b->a_ue, 8 } })) return r;
+	hipStream_t st = b->rs.st;
+	if (int r = rec_reserve(b->cap_bytes, total, 0, st, BAI_FIT, { { &b->d_in, 1 } })) return r;
+	if (int r = rec_reserve(b->cap_rec, n_rec, 0, st, BAI_FIT, { { &b->d_off, 8 } }, 1)) return r;
+	if (int r = rec_reserve(b->cap_ord, b->n_ord + n_rec, b->n_ord, st, BAI_FIT, { { &b->a_key, 8 }, { &b->a_be, 8 }, { &b->a_us, 8 }, { &b->a_ue, 8 } })) return r;
 	StreamDrain drain{ st };
 	BaiParams P;
 	P.in = b->d_in.as<uint8_t>(); P.off = b->d_off.as<int64_t>(); P.base = base; P.stream_off = stream_off; P.last_key = b->n_ord ? b->last_key : 0;
 	P.n_rec = (int32_t)n_rec; P.n_ref = b->n_ref;
 	P.key = b->a_key.as<uint64_t>() + b->n_ord; P.be = b->a_be.as<uint64_t>() + b->n_ord; P.us = b->a_us.as<int64_t>() + b->n_ord; P.ue = b->a_ue.as<uint64_t>() + b->n_ord;
 	P.cnt = b->d_cnt.as<unsigned int>();
-	b->h_cnt[0] = 0xffffffffu; b->h_cnt[1] = 0;
-	HIP_CHECK(hipEventRecord(b->ev[0], st));
-	HIP_CHECK(hipMemcpyAsync(b->d_in.p, in + base, (size_t)total, hipMemcpyHostToDevice, st));
-	HIP_CHECK(hipMemcpyAsync(b->d_off.p, in_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
-	HIP_CHECK(hipMemcpyAsync(b->d_cnt.p, b->h_cnt, 2 * sizeof(unsigned int), hipMemcpyHostToDevice, st));
-	HIP_CHECK(hipEventRecord(b->ev[1], st));
-	const int64_t trips = (n_rec + BAI_GROUPS - 1) / BAI_GROUPS;
-	nabwa_launch_bai_sig(&P, (int)(trips < b->n_blocks ? trips : b->n_blocks), st);
+	unsigned int *h_cnt = b->rs.h_words;
+	h_cnt[0] = 0xffffffffu; h_cnt[1] = 0;
+	if (int r = rec_upload(b->rs, b->d_in, b->d_off, b->d_cnt.p, h_cnt, 2, n_rec, in, in_off)) return r;
+	nabwa_launch_bai_sig(&P, rec_grid(n_rec, REC_GROUPS, b->rs.n_blocks), st);
 	HIP_CHECK(hipGetLastError());
-	HIP_CHECK(hipEventRecord(b->ev[2], st));
-	HIP_CHECK(hipMemcpyAsync(b->h_cnt, b->d_cnt.p, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+	HIP_CHECK(hipEventRecord(b->rs.ev[2], st));
+	HIP_CHECK(hipMemcpyAsync(h_cnt, b->d_cnt.p, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
 	HIP_CHECK(hipStreamSynchronize(st));
-	if (b->h_cnt[0] != 0xffffffffu) {
-		const int64_t i = (int64_t)b->h_cnt[0];
+	if (h_cnt[0] != 0xffffffffu) {
+		const int64_t i = (int64_t)h_cnt[0];
 		if (i >= n_rec) return fail_fmt(NABWA_EDATA, "record %lld is damaged", (long long)i);
 		return damaged(i, in + in_off[i], in_off[i + 1] - in_off[i], b->n_ref, i ? key_of(in + in_off[i - 1]) : P.last_key);
 	}
 	if (!b->n_ord) b->first_start = stream_off;
-	b->n_ord += n_rec; b->n_no_coor += (int64_t)b->h_cnt[1];
+	b->n_ord += n_rec; b->n_no_coor += (int64_t)h_cnt[1];
 	b->last_end = stream_off + total; b->last_key = key_of(in + in_off[n_rec - 1]);
-	HIP_CHECK(hipEventElapsedTime(&b->ms[0], b->ev[0], b->ev[1]));
-	HIP_CHECK(hipEventElapsedTime(&b->ms[1], b->ev[1], b->ev[2]));
+	HIP_CHECK(hipEventElapsedTime(&b->ms[0], b->rs.ev[0], b->rs.ev[1]));
+	HIP_CHECK(hipEventElapsedTime(&b->ms[1], b->rs.ev[1], b->rs.ev[2]));
 	return NABWA_OK;
 }
 
@@ -195,9 +131,9 @@ extern "C" int nabwa_bai_finish(nabwa_bai_t *b, int64_t n_blk, const int64_t *bl
 	if (b->n_ord && (b->first_start < blk_uoff[0] || b->last_end > blk_uoff[n_blk]))
 		return fail_fmt(NABWA_EINVAL, "the records added lie at %lld .. %lld of the stream, the block table ends at %lld", (long long)b->first_start, (long long)b->last_end, (long long)blk_uoff[n_blk]);
 	const int64_t n = b->n_ord - b->n_no_coor, n_ref = b->n_ref;
-	HIP_CHECK(hipSetDevice(b->device));
+	HIP_CHECK(hipSetDevice(b->rs.device));
 	(void)hipGetLastError();                                   /* (an error some earlier call of the process left behind is not a launch of this call's) */
-	hipStream_t st = b->st;
+	hipStream_t st = b->rs.st;
 	int end_bit = 17;
 	while (end_bit < 48 && ((int64_t)1 << (end_bit - 16)) < n_ref) ++end_bit;
 	size_t tmp = 0, t2 = 0;
@@ -209,15 +145,10 @@ extern "C" int nabwa_bai_finish(nabwa_bai_t *b, int64_t n_blk, const int64_t *bl
 	}
 	HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)n_ref + 1, st));
 	tmp = t2 > tmp ? t2 : tmp;
-	if (int r = bai_reserve(b->cap_blk, n_blk + 1, 0, st, { { &b->f_blk_u, 8 }, { &b->f_blk_c, 8 } })) return r;
-	if (int r = bai_reserve(b->cap_fin, n, 0, st, { { &b->f_vb, 8 }, { &b->f_ve, 8 }, { &b->f_keys[0], 8 }, { &b->f_keys[1], 8 }, { &b->f_idx[0], 4 }, { &b->f_idx[1], 4 },
+	if (int r = rec_reserve(b->cap_blk, n_blk + 1, 0, st, BAI_FIT, { { &b->f_blk_u, 8 }, { &b->f_blk_c, 8 } })) return r;
+	if (int r = rec_reserve(b->cap_fin, n, 0, st, BAI_FIT, { { &b->f_vb, 8 }, { &b->f_ve, 8 }, { &b->f_keys[0], 8 }, { &b->f_keys[1], 8 }, { &b->f_idx[0], 4 }, { &b->f_idx[1], 4 },
 														 { &b->f_heads, 8 }, { &b->f_sc, 8 }, { &b->f_bin_c0, 4 } }, 1)) return r;
-	if (tmp > b->cap_tmp) {
-		HIP_CHECK(hipStreamSynchronize(st));
-		b->cap_tmp = 0;
-		if (int r = bai_grow(b->f_tmp, 0, tmp + tmp / 4, st)) return r;
-		b->cap_tmp = tmp + tmp / 4;
-	}
+	if (int r = rec_reserve_tmp(b->cap_tmp, tmp, b->f_tmp, st, BAI_FIT)) return r;
 	StreamDrain drain{ st };
 	BaiFin F;
 	memset(&F, 0, sizeof F);
@@ -230,7 +161,7 @@ extern "C" int nabwa_bai_finish(nabwa_bai_t *b, int64_t n_blk, const int64_t *bl
 	F.heads = b->f_heads.as<unsigned long long>(); F.sc = b->f_sc.as<unsigned long long>(); F.bin_c0 = b->f_bin_c0.as<uint32_t>();
 	F.ref_size = b->r_u64[0].as<unsigned long long>(); F.ref_nintv = b->r_u64[1].as<unsigned long long>();
 	F.ref_off = b->r_u64[2].as<unsigned long long>(); F.lin_off = b->r_u64[3].as<unsigned long long>();
-	HIP_CHECK(hipEventRecord(b->ev[0], st));
+	HIP_CHECK(hipEventRecord(b->rs.ev[0], st));
 	HIP_CHECK(hipMemcpyAsync(b->f_blk_u.p, blk_uoff, (size_t)(n_blk + 1) * 8, hipMemcpyHostToDevice, st));
 	HIP_CHECK(hipMemcpyAsync(b->f_blk_c.p, blk_coff, (size_t)(n_blk + 1) * 8, hipMemcpyHostToDevice, st));
 	HIP_CHECK(hipMemsetAsync(b->r_i32[0].p, 0xff, ((size_t)n_ref + 1) * 4, st));      /* maxwin: -1, a reference without records */
@@ -246,7 +177,7 @@ extern "C" int nabwa_bai_finish(nabwa_bai_t *b, int64_t n_blk, const int64_t *bl
 		HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(b->f_tmp.p, need, dk, dv, (int)n, 0, end_bit, st));
 	}
 	F.skey = dk.Current(); F.sidx = dv.Current();
-	HIP_CHECK(hipEventRecord(b->ev[1], st));
+	HIP_CHECK(hipEventRecord(b->rs.ev[1], st));
 	if (n) {
 		nabwa_launch_bai_step(NABWA_BAI_STEP_REF, &F, st);
 		nabwa_launch_bai_step(NABWA_BAI_STEP_HEAD, &F, st);
@@ -266,7 +197,7 @@ extern "C" int nabwa_bai_finish(nabwa_bai_t *b, int64_t n_blk, const int64_t *bl
 	}
 	HIP_CHECK(hipMemcpyAsync(b->h_tot + 1, F.ref_off + n_ref, 8, hipMemcpyDeviceToHost, st));
 	HIP_CHECK(hipMemcpyAsync(b->h_tot + 2, F.lin_off + n_ref, 8, hipMemcpyDeviceToHost, st));
-	HIP_CHECK(hipEventRecord(b->ev[2], st));
+	HIP_CHECK(hipEventRecord(b->rs.ev[2], st));
 	HIP_CHECK(hipStreamSynchronize(st));
 	const int64_t bytes = 8 + (int64_t)b->h_tot[1] + 8, n_lin = (int64_t)b->h_tot[2];
 	if (stats) {
@@ -278,18 +209,14 @@ extern "C" int nabwa_bai_finish(nabwa_bai_t *b, int64_t n_blk, const int64_t *bl
 	if (!out && cap == 0) return NABWA_OK;
 	if (cap < bytes) return fail_fmt(NABWA_ECAP, "the index has %lld bytes, the buffer %lld", (long long)bytes, (long long)cap);
 	if (n_lin > 0x7fffffff) return fail_fmt(NABWA_EINVAL, "%lld windows: a finish takes 2147483647", (long long)n_lin);
-	if (int r = bai_reserve(b->cap_lin, n_lin, 0, st, { { &b->f_lin, 8 } })) return r;
+	if (int r = rec_reserve(b->cap_lin, n_lin, 0, st, BAI_FIT, { { &b->f_lin, 8 } })) return r;
 	if (n_lin) {                                               /* the backward fill's scratch, now that the windows are known */
 		HIP_CHECK(hipcub::DeviceScan::InclusiveScan(nullptr, t2, (unsigned long long*)nullptr, (unsigned long long*)nullptr, BaiNextTouched(), (int)n_lin, st));
-		if (t2 > b->cap_tmp) {
-			b->cap_tmp = 0;
-			if (int r = bai_grow(b->f_tmp, 0, t2 + t2 / 4, st)) return r;
-			b->cap_tmp = t2 + t2 / 4;
-		}
+		if (int r = rec_reserve_tmp(b->cap_tmp, t2, b->f_tmp, st, BAI_FIT)) return r;
 	}
-	if (int r = bai_reserve(b->cap_out, bytes, 0, st, { { &b->f_out, 1 } })) return r;
+	if (int r = rec_reserve(b->cap_out, bytes, 0, st, BAI_FIT, { { &b->f_out, 1 } })) return r;
 	F.n_lin = n_lin; F.lin = b->f_lin.as<unsigned long long>(); F.out = b->f_out.as<uint32_t>();
-	HIP_CHECK(hipEventRecord(b->ev[3], st));
+	HIP_CHECK(hipEventRecord(b->rs.ev[3], st));
 	if (n_lin) {
 		HIP_CHECK(hipMemsetAsync(b->f_lin.p, 0xff, (size_t)n_lin * 8, st));
 		nabwa_launch_bai_step(NABWA_BAI_STEP_LIN, &F, st);
@@ -297,26 +224,26 @@ extern "C" int nabwa_bai_finish(nabwa_bai_t *b, int64_t n_blk, const int64_t *bl
 		size_t need = b->cap_tmp;
 		HIP_CHECK(hipcub::DeviceScan::InclusiveScan(b->f_tmp.p, need, F.lin, F.lin, BaiNextTouched(), (int)n_lin, st));
 	}
-	HIP_CHECK(hipEventRecord(b->ev[4], st));
+	HIP_CHECK(hipEventRecord(b->rs.ev[4], st));
 	nabwa_launch_bai_step(NABWA_BAI_STEP_WRITE_REF, &F, st);
 	if (n) nabwa_launch_bai_step(NABWA_BAI_STEP_WRITE_TUPLE, &F, st);
 	if (n_lin) nabwa_launch_bai_step(NABWA_BAI_STEP_WRITE_LIN, &F, st);
 	HIP_CHECK(hipGetLastError());
-	HIP_CHECK(hipEventRecord(b->ev[5], st));
+	HIP_CHECK(hipEventRecord(b->rs.ev[5], st));
 	HIP_CHECK(hipMemcpyAsync(out, b->f_out.p, (size_t)bytes, hipMemcpyDeviceToHost, st));
-	HIP_CHECK(hipEventRecord(b->ev[6], st));
+	HIP_CHECK(hipEventRecord(b->rs.ev[6], st));
 	HIP_CHECK(hipStreamSynchronize(st));
-	HIP_CHECK(hipEventElapsedTime(&b->ms[2], b->ev[0], b->ev[1]));
-	HIP_CHECK(hipEventElapsedTime(&b->ms[3], b->ev[1], b->ev[2]));
-	for (int k = 0; k < 3; ++k) HIP_CHECK(hipEventElapsedTime(&b->ms[4 + k], b->ev[3 + k], b->ev[4 + k]));
+	HIP_CHECK(hipEventElapsedTime(&b->ms[2], b->rs.ev[0], b->rs.ev[1]));
+	HIP_CHECK(hipEventElapsedTime(&b->ms[3], b->rs.ev[1], b->rs.ev[2]));
+	for (int k = 0; k < 3; ++k) HIP_CHECK(hipEventElapsedTime(&b->ms[4 + k], b->rs.ev[3 + k], b->rs.ev[4 + k]));
 	return NABWA_OK;
 }
 
 extern "C" int nabwa_bai_clear(nabwa_bai_t *b)
 {
 	if (!b) return nabwa_fail(NABWA_EINVAL, "null argument");
-	HIP_CHECK(hipSetDevice(b->device));
-	HIP_CHECK(hipStreamSynchronize(b->st));
+	HIP_CHECK(hipSetDevice(b->rs.device));
+	HIP_CHECK(hipStreamSynchronize(b->rs.st));
 	b->n_ord = 0; b->n_no_coor = 0; b->first_start = 0; b->last_end = 0; b->last_key = 0;
 	return NABWA_OK;
 }

@@ -10,43 +10,25 @@
 // it can from the arguments alone, before any device call.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
-#include <stdio.h>
 #include <string.h>
-#include <initializer_list>
-#include <utility>
-#include "../../include/nabwa.h"
 #include "launchers.hpp"
-#include "nabwa_internal.hpp"
-#include "dev_pool.hpp"
+#include "rec_stream.hpp"
 #include "markdup_body.hpp"
 
+#define MD_FIT "the records do not fit the device: a buffer of %lld bytes could not be had"
+
 struct nabwa_markdup {
-	int device = 0, n_blocks = 1;
+	RecStream rs;                                               /* h_words: n_tup, bad */
 	nabwa_markdup_opt_t opt = {};
-	DevStream st;
 	DevBuf d_in, d_off, d_end, d_c3, d_score, d_meta;           /* a call: its bytes, its offsets, its scratch */
 	DevBuf a_hi, a_lo, a_k3, a_link, d_dup;                     /* the arena: tuples, and a byte per ordinal twice */
 	DevBuf d_cnt, d_stats;                                      /* n_tup and bad; the counters */
 	DevBuf r_keys[2], r_idx[2], r_tmp;                          /* a resolve */
 	int64_t cap_bytes = 0, cap_rec = 0, cap_tup = 0, cap_ord = 0, cap_res = 0, cap_dup = 0; size_t cap_tmp = 0;
 	int64_t n_ord = 0, n_tup = 0;                               /* records and tuples added */
-	unsigned int *h_cnt = nullptr;                              /* pinned: n_tup, bad */
-	hipEvent_t ev[7] = {};
 	float ms[5] = { 0, 0, 0, 0, 0 };
-	~nabwa_markdup()
-	{
-		(void)hipSetDevice(device);
-		if (st.s) (void)hipStreamSynchronize(st.s);
-		if (h_cnt) (void)hipHostFree(h_cnt);
-		for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-	}
+	~nabwa_markdup() { rs.quiesce(); }
 };
-
-static int fail_fmt(int code, const char *fmt, long long a, long long b = 0, long long c = 0)
-{
-	char m[256]; snprintf(m, sizeof m, fmt, a, b, c);
-	return nabwa_fail(code, "%s", m);
-}
 
 extern "C" void nabwa_markdup_default_opt(nabwa_markdup_opt_t *o)
 {
@@ -60,23 +42,17 @@ extern "C" int nabwa_markdup_create(int device, const nabwa_markdup_opt_t *opt, 
 	if (!opt || !out) return nabwa_fail(NABWA_EINVAL, "null argument");
 	if (opt->min_qual < 0 || opt->min_qual > 255) return fail_fmt(NABWA_EINVAL, "min_qual %lld: a base quality, 0 .. 255", opt->min_qual);
 	if (opt->single_ends != NABWA_MARKDUP_ENDS_5P && opt->single_ends != NABWA_MARKDUP_ENDS_BOTH) return fail_fmt(NABWA_EINVAL, "single_ends %lld: NABWA_MARKDUP_ENDS_5P (0) or NABWA_MARKDUP_ENDS_BOTH (1)", opt->single_ends);
-	const hipError_t e0 = hipSetDevice(device);
-	if (e0 != hipSuccess) { (void)hipGetLastError(); return nabwa_hip_fail(e0, "hipSetDevice(device)", __FILE__, __LINE__); }
 	nabwa_markdup_t *m = new nabwa_markdup_t;
-	m->device = device; m->opt = *opt; m->opt.pad = 0;
-	int n_cu = 0;
-	hipError_t e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device);
-	m->n_blocks = 8 * (n_cu > 0 ? n_cu : 1);                  /* the persistent grid: eight workgroups of 256 fill a compute unit's wave slots */
-	if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->st.s, hipStreamNonBlocking);
-	if (e == hipSuccess) e = hipHostMalloc((void**)&m->h_cnt, 2 * sizeof(unsigned int), hipHostMallocDefault);
-	for (int k = 0; k < 7 && e == hipSuccess; ++k) e = hipEventCreate(&m->ev[k]);
-	int r = e == hipSuccess ? NABWA_OK : nabwa_hip_fail(e, "setting up the duplicate marking", __FILE__, __LINE__);
+	m->opt = *opt; m->opt.pad = 0;
+	/* the persistent grid: eight workgroups of 256 fill a compute unit's wave slots */
+	int r = m->rs.setup(device, 8, 2, 7, "setting up the duplicate marking");
+	hipError_t e = hipSuccess;
 	if (r == NABWA_OK) r = m->d_cnt.get(2 * sizeof(unsigned int));
 	if (r == NABWA_OK) r = m->d_stats.get(NABWA_MARKDUP_N_STATS * 8);
 	if (r == NABWA_OK) {
-		e = hipMemsetAsync(m->d_cnt.p, 0, 2 * sizeof(unsigned int), m->st);
-		if (e == hipSuccess) e = hipMemsetAsync(m->d_stats.p, 0, NABWA_MARKDUP_N_STATS * 8, m->st);
-		if (e == hipSuccess) e = hipStreamSynchronize(m->st);
+		e = hipMemsetAsync(m->d_cnt.p, 0, 2 * sizeof(unsigned int), m->rs.st);
+		if (e == hipSuccess) e = hipMemsetAsync(m->d_stats.p, 0, NABWA_MARKDUP_N_STATS * 8, m->rs.st);
+		if (e == hipSuccess) e = hipStreamSynchronize(m->rs.st);
 		if (e != hipSuccess) r = nabwa_hip_fail(e, "setting up the duplicate marking", __FILE__, __LINE__);
 	}
 	if (r != NABWA_OK) { delete m; return r; }
@@ -86,44 +62,13 @@ extern "C" int nabwa_markdup_create(int device, const nabwa_markdup_opt_t *opt, 
 
 extern "C" void nabwa_markdup_destroy(nabwa_markdup_t *m) { delete m; }
 
-/* b, which holds `keep` bytes worth keeping, becomes a buffer of at least `bytes`; out of device memory is the caller's to act on */
-static int md_grow(DevBuf &b, size_t keep, size_t bytes, hipStream_t st)
-{
-	if (!keep) { const hipError_t e = b.release(); if (e != hipSuccess) return nabwa_hip_fail(e, "hipFree", __FILE__, __LINE__); }
-	void *p = nullptr;
-	const hipError_t m = hipMalloc(&p, bytes ? bytes : 1);
-	if (m == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail_fmt(NABWA_ENOMEM, "the records do not fit the device: a buffer of %lld bytes could not be had", (long long)bytes); }
-	if (m != hipSuccess) return nabwa_hip_fail(m, "hipMalloc", __FILE__, __LINE__);
-	hipError_t e = hipSuccess;
-	if (keep && b.p) { e = hipMemcpyAsync(p, b.p, keep, hipMemcpyDeviceToDevice, st); if (e == hipSuccess) e = hipStreamSynchronize(st); }
-	if (e == hipSuccess) e = b.release();
-	if (e != hipSuccess) { (void)hipFree(p); return nabwa_hip_fail(e, "moving the arena", __FILE__, __LINE__); }
-	b.p = p;
-	return NABWA_OK;
-}
-/* `cap` units of `unit` bytes each in every buffer of `bufs` (what they hold of `have` units is kept) become at least `want`, a quarter more */
-static int md_reserve(int64_t &cap, int64_t want, int64_t have, hipStream_t st, std::initializer_list<std::pair<DevBuf*, int>> bufs, int extra = 0)
-{
-	if (want <= cap) return NABWA_OK;
-	HIP_CHECK(hipStreamSynchronize(st));
-	const int64_t to = want + want / 4;
-	cap = have;                                                /* (a failure half-way: what is kept still fits every buffer) */
-	for (const auto &b : bufs) if (int r = md_grow(*b.first, (size_t)have * (size_t)b.second, (size_t)(to + extra) * (size_t)b.second, st)) return r;
-	cap = to;
-	return NABWA_OK;
-}
-
 /* which kind of damage record i has, from its bytes on the host, for the message */
 static int damaged(int64_t i, const uint8_t *rec, int64_t size)
 {
-	uint32_t bs, w12, w16, L;
-	memcpy(&bs, rec, 4); memcpy(&w12, rec + 12, 4); memcpy(&w16, rec + 16, 4); memcpy(&L, rec + 20, 4);
-	if ((int64_t)bs + 4 != size) return fail_fmt(NABWA_EDATA, "record %lld: its block_size says %lld bytes, its offsets %lld", (long long)i, (long long)bs + 4, (long long)size);
-	const uint32_t l_name = w12 & 0xffu, n_cig = w16 & 0xffffu;
-	const uint64_t need = (uint64_t)MD_MIN_REC + l_name + 4 * (uint64_t)n_cig + ((uint64_t)L + 1) / 2 + L;
-	if (need > (uint64_t)size) return fail_fmt(NABWA_EDATA, "record %lld: its name, CIGAR, bases and qualities need %lld bytes, it has %lld", (long long)i, (long long)need, (long long)size);
+	if (int r = rec_damaged_head(i, rec, size)) return r;
+	REC_FIELDS(rec);
 	uint64_t n_read = 0;
-	for (uint32_t c = 0; c < n_cig; ++c) { uint32_t w; memcpy(&w, rec + MD_MIN_REC + l_name + 4 * c, 4); if (md_op_read(w & 15u)) n_read += w >> 4; }
+	for (uint32_t c = 0; c < n_cig; ++c) { const uint32_t w = rec_u32(rec + REC_MIN_REC + l_name + 4 * c); if (rec_op_read(w & 15u)) n_read += w >> 4; }
 	if (L > 0 && n_read != L) return fail_fmt(NABWA_EDATA, "record %lld: its CIGAR does not consume its %lld bases", (long long)i, (long long)L);
 	return fail_fmt(NABWA_EDATA, "record %lld: an unclipped end outside -2^30 .. 2^31 + 2^30", (long long)i);
 }
@@ -131,23 +76,18 @@ static int damaged(int64_t i, const uint8_t *rec, int64_t size)
 extern "C" int nabwa_markdup_add(nabwa_markdup_t *m, int64_t n_rec, const uint8_t *in, const int64_t *in_off)
 {
 	if (!m) return nabwa_fail(NABWA_EINVAL, "null argument");
-	if (n_rec < 0 || n_rec > 0x7fffffff) return fail_fmt(NABWA_EINVAL, "n_rec %lld: 0 .. 2147483647 records", (long long)n_rec);
-	if (!in_off || (n_rec && !in)) return nabwa_fail(NABWA_EINVAL, "null argument");
-	if (in_off[0] < 0) return nabwa_fail(NABWA_EINVAL, "the first offset is negative");
-	for (int64_t i = 0; i < n_rec; ++i) {
-		if (in_off[i + 1] <= in_off[i]) return fail_fmt(NABWA_EINVAL, "the offsets do not increase at record %lld", (long long)i);
-		if (in_off[i + 1] - in_off[i] < MD_MIN_REC) return fail_fmt(NABWA_EINVAL, "record %lld has %lld bytes: a BAM record has at least 36", (long long)i, (long long)(in_off[i + 1] - in_off[i]));
-	}
+	if (int r = rec_check_offsets(n_rec, in, in_off)) return r;
 	if (n_rec == 0) return NABWA_OK;
 	if (m->n_ord + n_rec > 0x7fffffff) return fail_fmt(NABWA_EINVAL, "%lld records after %lld: a handle takes 2147483647 between create / clear", (long long)n_rec, (long long)m->n_ord);
 	const int64_t base = in_off[0], total = in_off[n_rec] - base;
-	HIP_CHECK(hipSetDevice(m->device));
-	hipStream_t st = m->st;
-	if (int r = md_reserve(m->cap_bytes, total, 0, st, { { &m->d_in, 1 } })) return r;
-	if (int r = md_reserve(m->cap_rec, n_rec, 0, st, { { &m->d_off, 8 }, { &m->d_end, 8 }, { &m->d_c3, 4 }, { &m->d_score, 4 }, { &m->d_meta, 4 } }, 1)) return r;
-	if (int r = md_reserve(m->cap_ord, m->n_ord + n_rec, m->n_ord, st, { { &m->a_link, 1 } })) return r;
+	HIP_CHECK(hipSetDevice(m->rs.device));
+	hipStream_t st = m->rs.st;
+	unsigned int *h_cnt = m->rs.h_words;
+	if (int r = rec_reserve(m->cap_bytes, total, 0, st, MD_FIT, { { &m->d_in, 1 } })) return r;
+	if (int r = rec_reserve(m->cap_rec, n_rec, 0, st, MD_FIT, { { &m->d_off, 8 }, { &m->d_end, 8 }, { &m->d_c3, 4 }, { &m->d_score, 4 }, { &m->d_meta, 4 } }, 1)) return r;
+	if (int r = rec_reserve(m->cap_ord, m->n_ord + n_rec, m->n_ord, st, MD_FIT, { { &m->a_link, 1 } })) return r;
 	/* tuples: a fragment one, a pair of two records three */
-	if (int r = md_reserve(m->cap_tup, m->n_tup + (3 * n_rec + 1) / 2, m->n_tup, st, { { &m->a_hi, 8 }, { &m->a_lo, 8 }, { &m->a_k3, 8 } })) return r;
+	if (int r = rec_reserve(m->cap_tup, m->n_tup + (3 * n_rec + 1) / 2, m->n_tup, st, MD_FIT, { { &m->a_hi, 8 }, { &m->a_lo, 8 }, { &m->a_k3, 8 } })) return r;
 	StreamDrain drain{ st };
 	MdParams P;
 	P.in = m->d_in.as<uint8_t>(); P.off = m->d_off.as<int64_t>(); P.base = base; P.n_rec = (int32_t)n_rec;
@@ -157,35 +97,30 @@ extern "C" int nabwa_markdup_add(nabwa_markdup_t *m, int64_t n_rec, const uint8_
 	A.hi = m->a_hi.as<uint64_t>(); A.lo = m->a_lo.as<uint64_t>(); A.k3 = m->a_k3.as<uint64_t>(); A.link = m->a_link.as<uint8_t>();
 	A.n_tup = m->d_cnt.as<unsigned int>(); A.stats = m->d_stats.as<unsigned long long>(); A.ord_base = (uint32_t)m->n_ord;
 	unsigned int *d_bad = m->d_cnt.as<unsigned int>() + 1;
-	m->h_cnt[1] = 0xffffffffu;
-	HIP_CHECK(hipEventRecord(m->ev[0], st));
-	HIP_CHECK(hipMemcpyAsync(m->d_in.p, in + base, (size_t)total, hipMemcpyHostToDevice, st));
-	HIP_CHECK(hipMemcpyAsync(m->d_off.p, in_off, (size_t)(n_rec + 1) * 8, hipMemcpyHostToDevice, st));
-	HIP_CHECK(hipMemcpyAsync(d_bad, m->h_cnt + 1, sizeof(unsigned int), hipMemcpyHostToDevice, st));
-	HIP_CHECK(hipEventRecord(m->ev[1], st));
-	const int64_t trips = (n_rec + MD_GROUPS - 1) / MD_GROUPS;
-	nabwa_launch_markdup_sig(&P, (int)(trips < m->n_blocks ? trips : m->n_blocks), d_bad, st);
+	h_cnt[1] = 0xffffffffu;
+	if (int r = rec_upload(m->rs, m->d_in, m->d_off, d_bad, h_cnt + 1, 1, n_rec, in, in_off)) return r;
+	nabwa_launch_markdup_sig(&P, rec_grid(n_rec, REC_GROUPS, m->rs.n_blocks), d_bad, st);
 	HIP_CHECK(hipGetLastError());
-	HIP_CHECK(hipEventRecord(m->ev[2], st));
-	HIP_CHECK(hipMemcpyAsync(m->h_cnt + 1, d_bad, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+	HIP_CHECK(hipEventRecord(m->rs.ev[2], st));
+	HIP_CHECK(hipMemcpyAsync(h_cnt + 1, d_bad, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
 	HIP_CHECK(hipStreamSynchronize(st));
-	if (m->h_cnt[1] != 0xffffffffu) {
-		const int64_t i = (int64_t)m->h_cnt[1];
+	if (h_cnt[1] != 0xffffffffu) {
+		const int64_t i = (int64_t)h_cnt[1];
 		if (i >= n_rec) return fail_fmt(NABWA_EDATA, "record %lld is damaged", (long long)i);
 		return damaged(i, in + in_off[i], in_off[i + 1] - in_off[i]);
 	}
-	HIP_CHECK(hipEventRecord(m->ev[3], st));
+	HIP_CHECK(hipEventRecord(m->rs.ev[3], st));
 	nabwa_launch_markdup_emit(&P, &A, st);
 	HIP_CHECK(hipGetLastError());
-	HIP_CHECK(hipEventRecord(m->ev[4], st));
-	HIP_CHECK(hipMemcpyAsync(m->h_cnt, m->d_cnt.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+	HIP_CHECK(hipEventRecord(m->rs.ev[4], st));
+	HIP_CHECK(hipMemcpyAsync(h_cnt, m->d_cnt.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
 	HIP_CHECK(hipStreamSynchronize(st));
-	m->n_tup = (int64_t)m->h_cnt[0];
+	m->n_tup = (int64_t)h_cnt[0];
 	m->n_ord += n_rec;
 	float a = 0, b = 0;
-	HIP_CHECK(hipEventElapsedTime(&m->ms[0], m->ev[0], m->ev[1]));
-	HIP_CHECK(hipEventElapsedTime(&a, m->ev[1], m->ev[2]));
-	HIP_CHECK(hipEventElapsedTime(&b, m->ev[3], m->ev[4]));
+	HIP_CHECK(hipEventElapsedTime(&m->ms[0], m->rs.ev[0], m->rs.ev[1]));
+	HIP_CHECK(hipEventElapsedTime(&a, m->rs.ev[1], m->rs.ev[2]));
+	HIP_CHECK(hipEventElapsedTime(&b, m->rs.ev[3], m->rs.ev[4]));
 	m->ms[1] = a + b;
 	return NABWA_OK;
 }
@@ -194,25 +129,20 @@ extern "C" int nabwa_markdup_resolve(nabwa_markdup_t *m, uint8_t *dup, int64_t c
 {
 	if (!m || cap < 0 || (cap > 0 && !dup)) return nabwa_fail(NABWA_EINVAL, "null argument");
 	if (cap < m->n_ord) return fail_fmt(NABWA_ECAP, "dup[] holds %lld records, %lld were added", (long long)cap, (long long)m->n_ord);
-	HIP_CHECK(hipSetDevice(m->device));
-	hipStream_t st = m->st;
+	HIP_CHECK(hipSetDevice(m->rs.device));
+	hipStream_t st = m->rs.st;
 	const int64_t n = m->n_tup, n_ord = m->n_ord;
 	size_t tmp = 0;
 	if (n) {
 		hipcub::DoubleBuffer<uint64_t> dk(nullptr, nullptr); hipcub::DoubleBuffer<uint32_t> dv(nullptr, nullptr);
 		HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, dk, dv, (int)n, 0, 64, st));
 	}
-	if (int r = md_reserve(m->cap_res, n, 0, st, { { &m->r_keys[0], 8 }, { &m->r_keys[1], 8 }, { &m->r_idx[0], 4 }, { &m->r_idx[1], 4 } })) return r;
-	if (tmp > m->cap_tmp) {
-		HIP_CHECK(hipStreamSynchronize(st));
-		m->cap_tmp = 0;
-		if (int r = md_grow(m->r_tmp, 0, tmp + tmp / 4, st)) return r;
-		m->cap_tmp = tmp + tmp / 4;
-	}
-	if (int r = md_reserve(m->cap_dup, n_ord, 0, st, { { &m->d_dup, 1 } })) return r;
+	if (int r = rec_reserve(m->cap_res, n, 0, st, MD_FIT, { { &m->r_keys[0], 8 }, { &m->r_keys[1], 8 }, { &m->r_idx[0], 4 }, { &m->r_idx[1], 4 } })) return r;
+	if (int r = rec_reserve_tmp(m->cap_tmp, tmp, m->r_tmp, st, MD_FIT)) return r;
+	if (int r = rec_reserve(m->cap_dup, n_ord, 0, st, MD_FIT, { { &m->d_dup, 1 } })) return r;
 	StreamDrain drain{ st };
 	unsigned long long *d_stats = m->d_stats.as<unsigned long long>();
-	HIP_CHECK(hipEventRecord(m->ev[0], st));
+	HIP_CHECK(hipEventRecord(m->rs.ev[0], st));
 	HIP_CHECK(hipMemsetAsync(d_stats + NABWA_MARKDUP_STAT_DUP_FRAGMENTS, 0, 3 * 8, st));
 	if (n_ord) HIP_CHECK(hipMemsetAsync(m->d_dup.p, 0, (size_t)n_ord, st));
 	hipcub::DoubleBuffer<uint64_t> dk(m->r_keys[0].as<uint64_t>(), m->r_keys[1].as<uint64_t>());
@@ -228,7 +158,7 @@ extern "C" int nabwa_markdup_resolve(nabwa_markdup_t *m, uint8_t *dup, int64_t c
 			HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(m->r_tmp.p, need, dk, dv, (int)n, 0, 64, st));
 		}
 	}
-	HIP_CHECK(hipEventRecord(m->ev[1], st));
+	HIP_CHECK(hipEventRecord(m->rs.ev[1], st));
 	if (n) {
 		nabwa_launch_markdup_mark(n, dv.Current(), m->a_hi.as<uint64_t>(), m->a_lo.as<uint64_t>(), m->a_k3.as<uint64_t>(), m->d_dup.as<uint8_t>(), d_stats, st);
 		HIP_CHECK(hipGetLastError());
@@ -237,24 +167,24 @@ extern "C" int nabwa_markdup_resolve(nabwa_markdup_t *m, uint8_t *dup, int64_t c
 		nabwa_launch_markdup_prop(n_ord, m->a_link.as<uint8_t>(), m->d_dup.as<uint8_t>(), d_stats, st);
 		HIP_CHECK(hipGetLastError());
 	}
-	HIP_CHECK(hipEventRecord(m->ev[2], st));
+	HIP_CHECK(hipEventRecord(m->rs.ev[2], st));
 	if (n_ord) HIP_CHECK(hipMemcpyAsync(dup, m->d_dup.p, (size_t)n_ord, hipMemcpyDeviceToHost, st));
 	uint64_t s[NABWA_MARKDUP_N_STATS];
 	HIP_CHECK(hipMemcpyAsync(s, d_stats, sizeof s, hipMemcpyDeviceToHost, st));
-	HIP_CHECK(hipEventRecord(m->ev[3], st));
+	HIP_CHECK(hipEventRecord(m->rs.ev[3], st));
 	HIP_CHECK(hipStreamSynchronize(st));
 	if (stats) memcpy(stats, s, sizeof s);
-	for (int k = 0; k < 3; ++k) HIP_CHECK(hipEventElapsedTime(&m->ms[2 + k], m->ev[k], m->ev[k + 1]));
+	for (int k = 0; k < 3; ++k) HIP_CHECK(hipEventElapsedTime(&m->ms[2 + k], m->rs.ev[k], m->rs.ev[k + 1]));
 	return NABWA_OK;
 }
 
 extern "C" int nabwa_markdup_clear(nabwa_markdup_t *m)
 {
 	if (!m) return nabwa_fail(NABWA_EINVAL, "null argument");
-	HIP_CHECK(hipSetDevice(m->device));
-	HIP_CHECK(hipMemsetAsync(m->d_cnt.p, 0, 2 * sizeof(unsigned int), m->st));
-	HIP_CHECK(hipMemsetAsync(m->d_stats.p, 0, NABWA_MARKDUP_N_STATS * 8, m->st));
-	HIP_CHECK(hipStreamSynchronize(m->st));
+	HIP_CHECK(hipSetDevice(m->rs.device));
+	HIP_CHECK(hipMemsetAsync(m->d_cnt.p, 0, 2 * sizeof(unsigned int), m->rs.st));
+	HIP_CHECK(hipMemsetAsync(m->d_stats.p, 0, NABWA_MARKDUP_N_STATS * 8, m->rs.st));
+	HIP_CHECK(hipStreamSynchronize(m->rs.st));
 	m->n_ord = 0; m->n_tup = 0;
 	return NABWA_OK;
 }

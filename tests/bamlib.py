@@ -32,6 +32,22 @@ def tag_a(k, v):
     return k.encode() + b"A" + v.encode()
 
 
+HEAD_DAMAGE = ("block_size", "l_seq")
+
+
+def head_damaged(rec, kind, at):
+    """`rec` with one of the two kinds of damage that every record-stream module looks for (HEAD_DAMAGE) -> (the record, the whole text of
+    the library's error for it as record `at` of a call)"""
+    size = len(rec)
+    if kind == "block_size":
+        return struct.pack("<I", size - 4 + 1) + rec[4:], "record %d: its block_size says %d bytes, its offsets %d" % (at, size + 1, size)
+    l_name, n_cig = rec[12], struct.unpack_from("<H", rec, 16)[0]
+    l_seq = struct.unpack_from("<I", rec, 20)[0] + 1000
+    need = 36 + l_name + 4 * n_cig + (l_seq + 1) // 2 + l_seq
+    assert need > size
+    return rec[:20] + struct.pack("<I", l_seq) + rec[24:], "record %d: its name, CIGAR, bases and qualities need %d bytes, it has %d" % (at, need, size)
+
+
 def pack(records):
     off = np.zeros(len(records) + 1, np.int64)
     np.cumsum([len(r) for r in records], out=off[1:])

@@ -334,7 +334,7 @@ def _build(out, srcs, deps, flags):
     return out
 
 
-BODY = [os.path.join(CSRC, "damage_body.hpp"), os.path.join(CSRC, "finish_body.hpp"), os.path.join(CSRC, "wave_spmd.hpp"), os.path.join(EMU_DIR, "emu_hip.hpp"),
+BODY = [os.path.join(CSRC, "damage_body.hpp"), os.path.join(CSRC, "rec_body.hpp"), os.path.join(CSRC, "finish_body.hpp"), os.path.join(CSRC, "wave_spmd.hpp"), os.path.join(EMU_DIR, "emu_hip.hpp"),
         os.path.join(T.ROOT, "include", "nabwa.h")]
 
 

@@ -343,7 +343,7 @@ def _build(out, srcs, deps, flags):
     return out
 
 
-BODY = [os.path.join(CSRC, "markdup_body.hpp"), os.path.join(T.ROOT, "include", "nabwa.h")]
+BODY = [os.path.join(CSRC, "markdup_body.hpp"), os.path.join(CSRC, "rec_body.hpp"), os.path.join(T.ROOT, "include", "nabwa.h")]
 
 
 def load_emu():

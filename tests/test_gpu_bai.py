@@ -181,3 +181,17 @@ def test_a_larger_file_read_back_through_its_index():
         f = M.Bgzf(data)
         assert M.query(parsed, f, t, beg, end) == [r for r, e in zip(recs, ext) if e[0] == t and e[1] < end and e[2] > beg]      # M.scan, the extents taken once
         assert len(f.touched) < len(u) // 2
+
+
+@pytest.mark.parametrize("kind", B.HEAD_DAMAGE)
+def test_damage_in_the_head_of_the_middle_record_of_three(kind):
+    """the two kinds of damage that all record-stream modules look for: the whole message, and the handle as it was"""
+    good = [M.rec(0, 100, "25M"), M.rec(0, 200, "20M5S", name=b"s"), M.rec(1, 300, "25M", 16, name=b"t")]
+    bad, text = B.head_damaged(good[1], kind, 1)
+    u, c = M.table(M.HEADER + sum(len(r) for r in good) + 100, 97)
+    with nabwa.Bai(3) as b:
+        with pytest.raises(nabwa.NabwaError) as ex:
+            b.add(*B.pack([good[0], bad, good[2]]), M.HEADER)
+        assert ex.value.code == nabwa.EDATA and str(ex.value) == "libnabwa error %d: %s" % (nabwa.EDATA, text)
+        b.add(*B.pack(good), M.HEADER)
+        M.assert_same(b.finish(u, c), gpu(3, [(good, M.HEADER)], u, c), kind + ": as a fresh handle")

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import bam_sort_cases as S
+import bamlib as B
 import nabwa_testlib as T
 
 nabwa = importlib.import_module("network-aware-bwa_amd")
@@ -92,3 +93,18 @@ def test_a_block_size_off_by_one_is_edata_naming_the_lowest_record():
         with pytest.raises(nabwa.NabwaError) as e:
             nabwa.bam_sort(data.tobytes(), off)
         assert e.value.code == nabwa.EDATA and "record %d:" % lowest in str(e.value), str(e.value)
+
+
+def test_a_block_size_off_by_one_in_the_middle_record_of_three():
+    """the whole message, and the handle as it was: the sound records sorted as by a fresh handle"""
+    recs = S.mixed(3, seed=62)
+    bad, text = B.head_damaged(recs[1], "block_size", 1)
+    data, off = S.join(recs)
+    with nabwa.BamSort() as s:
+        with pytest.raises(nabwa.NabwaError) as e:
+            s.sort(S.join([recs[0], bad, recs[2]])[0].tobytes(), off)
+        assert e.value.code == nabwa.EDATA and str(e.value) == "libnabwa error %d: %s" % (nabwa.EDATA, text)
+        got = s.sort(data.tobytes(), off)
+    with nabwa.BamSort() as fresh:
+        want = fresh.sort(data.tobytes(), off)
+    assert len(got) == len(want) and all(np.array_equal(np.asarray(a), np.asarray(b)) for a, b in zip(got, want))

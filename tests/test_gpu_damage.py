@@ -9,6 +9,7 @@ import importlib
 import numpy as np
 import pytest
 
+import bamlib as B
 import damage_cases as D
 import nabwa_testlib as T
 
@@ -200,3 +201,18 @@ def test_the_nucleotide_reference_of_a_colour_index(ref, tmp_path):
     D.assert_same(gpu_tables(x, opt, recs, which_ref=1), want, "which_ref 1")
     D.assert_same(gpu_tables(x, opt, recs, which_ref=0), want, "which_ref 0 beside it")
     x.close()
+
+
+@pytest.mark.parametrize("kind", B.HEAD_DAMAGE)
+def test_damage_in_the_head_of_the_middle_record_of_three(ix, ref, kind):
+    """the two kinds of damage that all record-stream modules look for: the whole message, and the handle as it was"""
+    good = D.good_records(ref, 3)
+    bad, text = B.head_damaged(good[1], kind, 1)
+    with nabwa.Damage(ix) as d:
+        data, off = D.join([good[0], bad, good[2]])
+        with pytest.raises(nabwa.NabwaError) as ex:
+            d.add(data.tobytes(), off)
+        assert ex.value.code == nabwa.EDATA and str(ex.value) == "libnabwa error %d: %s" % (nabwa.EDATA, text)
+        data, off = D.join(good)
+        d.add(data.tobytes(), off)
+        D.assert_same(tables_of(d), gpu_tables(ix, D.opt_of(), good), kind + ": as a fresh handle")

@@ -168,3 +168,16 @@ def test_bam_sort_gives_the_permutation(mix):
         b = s.run(data, off, perm=True)
         assert len(a) == 3 and a[0] == out and b[0] == out and np.array_equal(b[3], perm)
     assert len(nabwa.bam_sort(b"", perm=True)[3]) == 0
+
+
+@pytest.mark.parametrize("kind", B.HEAD_DAMAGE)
+def test_damage_in_the_head_of_the_middle_record_of_three(kind):
+    """the two kinds of damage that all record-stream modules look for: the whole message, and the handle as it was"""
+    good, opt = [M.rec(0, 900, "25M"), M.rec(0, 900, "20M5S", name=b"s"), M.rec(0, 900, "25M", 16, name=b"t")], M.opt_of()
+    bad, text = B.head_damaged(good[1], kind, 1)
+    with handle(opt) as m:
+        with pytest.raises(nabwa.NabwaError) as ex:
+            m.add(*B.pack([good[0], bad, good[2]]))
+        assert ex.value.code == nabwa.EDATA and str(ex.value) == "libnabwa error %d: %s" % (nabwa.EDATA, text)
+        m.add(*B.pack(good))
+        M.assert_same(m.resolve(), gpu(opt, [good]), kind + ": as a fresh handle")
